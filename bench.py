@@ -15,9 +15,14 @@ vp9.c:565,882-892), so every rank decodes its own stream with no data-path
 collective (weak scaling); the barrier and the max-over-ranks timing reduction use
 torch.distributed (gloo, control plane only).
 
-Prints one JSON line (rank 0) with the driver's fields plus "roofline" (dominant
-kernel, algorithmic bytes / HIP-event kernel time vs the 8 TB/s HBM peak) and
-"cpu_baseline" (the scalar C oracle on a bounded sample of the same frames).
+A plain run (--gpus N --steps K --warmup W) stages the inputs, warms up, times the K
+steps and prints one JSON line (rank 0) with the driver's fields (metric, value, unit,
+ms_per_step, ...). --dump-outputs DIR then also writes what the last timed step left in
+its frame buffers (dump_outputs). --full adds everything else, in runs of their own:
+"roofline" (dominant kernel, algorithmic bytes / HIP-event kernel time vs the 8 TB/s HBM
+peak, from per-launch timing steps before the timed ones), "verify" (the timed frames
+against the CPU oracle), "cpu_baseline" (the scalar C oracle on a bounded sample of the
+same frames) and the host-entropy, decoder and FFHWAccel legs.
 """
 import argparse
 import importlib
@@ -53,6 +58,9 @@ SEED0 = 0x56503900 + CONFIG_INDEX
 # the PMC passes its traffic / issue fields come from
 TRAFFIC_PROFILE = "r06t/C3"
 POISON = 0xA5                  # fill byte of the frame buffers before the timed steps
+# --dump-outputs: seed of the sample positions, chroma samples per plane and frame (luma: 4x),
+# and the bound on everything written (under 64 MB)
+DUMP_SEED, DUMP_SAMPLES, DUMP_BYTES = 0x56503944, 16384, 56 << 20
 
 
 def frame_seed(rank, i, config_index=CONFIG_INDEX):
@@ -145,6 +153,96 @@ def aggregate(frames_per_rank, steps, world, elapsed_max):
     return total / elapsed_max, elapsed_max * 1000.0 / steps
 
 
+def serial_timing_steps(dev, args):
+    """--full / --serial-only: warmup + steps runs of the selected slot's batch with per-launch
+    HIP events, every launch enqueued on one stream; {kernel class: [ms, launches]} summed
+    over the steps."""
+    dev.set_timing(True)
+    for _ in range(args.warmup):
+        dev.run_batch()
+    dev.sync()
+    ksum = {}
+    for _ in range(args.steps):
+        dev.run_batch()
+        dev.sync()          # collects the per-launch HIP-event times of this step
+        for k, (ms, n) in dev.timing().items():
+            a = ksum.setdefault(k, [0.0, 0])
+            a[0] += ms
+            a[1] += n
+    return ksum
+
+
+def dump_outputs(v, dev, path, bufs, geom, chroma="420"):
+    """--dump-outputs: the frames in device buffers `bufs` (decode order) as a caller of the
+    timed path receives them (Device.download, visible Y / U / V), as float arrays of at most
+    DUMP_BYTES in all, the same positions in every run:
+    path/samples.npy   float32 [frames, 6 k]: per frame 4 k luma samples, then k of U and k of
+                       V, at positions drawn from default_rng([DUMP_SEED, frame index])
+    path/row_sums.npy  float64 [frames, rows]: the sum of every visible row of Y, then U, then V
+                       (every sample of every frame counts in one of them)
+    Returns {file name: shape}."""
+    import concurrent.futures
+    import threading
+    import numpy as np
+    W, H = geom[0], geom[1]
+    ssh, ssv = CHROMA[chroma]
+    n = len(bufs)
+    rows = H + 2 * ((H + ssv) >> ssv)
+    k = max(1, min(DUMP_SAMPLES, (DUMP_BYTES - 8 * n * rows) // (4 * 6 * n)))
+    samples = np.empty((n, 6 * k), np.float32)
+    sums = np.empty((n, rows), np.float64)
+    lock = threading.Lock()
+
+    def unit(j):
+        with lock:                                      # device downloads are serialised
+            planes = v.visible(dev.download(bufs[j]), W, H, ssh, ssv)
+        rng = np.random.default_rng([DUMP_SEED, j])
+        col = row = 0
+        for p, cnt in zip(planes, (4 * k, k, k)):
+            ys, xs = rng.integers(0, p.shape[0], cnt), rng.integers(0, p.shape[1], cnt)
+            samples[j, col:col + cnt] = p[ys, xs]
+            sums[j, row:row + p.shape[0]] = p.sum(axis=1, dtype=np.uint64)
+            col, row = col + cnt, row + p.shape[0]
+
+    with concurrent.futures.ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as ex:
+        list(ex.map(unit, range(n)))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "samples.npy"), samples)
+    np.save(os.path.join(path, "row_sums.npy"), sums)
+    return {"samples.npy": list(samples.shape), "row_sums.npy": list(sums.shape)}
+
+
+def rank_identity(v, rank, local_rank):
+    """A rank's place in the job and its GPU (one entry of the line's config.ranks)."""
+    info = {"rank": rank, "local_rank": local_rank, "device": _device_of(local_rank),
+            "host": os.uname().nodename}
+    info.update(_device_ids(v, info["device"]))
+    return info
+
+
+def result_line(args, world, fps, ms_per_step, geom, streams, ranks, t_gen, t_stage):
+    """The fields every run prints: the headline figure (value, ms_per_step) and what was run."""
+    W, H, BPP, LOG2_TILE_COLS, gop = geom
+    return {
+        "metric": "decoded frames/sec (bit-exact) 4K VP9 Profile-0 @ 1/2/4/8 MI355X; % HBM roofline",
+        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u8" if BPP == 8 else "u16", "data": "synthetic",
+        "config": {"workload": "%s: %dx%d VP9 Profile-%d %d-bit%s, %d tile columns, %s, %d frames per GPU per step, "
+                               "pass-1 packets resident in HBM"
+                               % (args.config, W, H, (0 if BPP == 8 else 2) | (args.chroma != "420"), BPP,
+                                  "" if args.chroma == "420" else " 4:%s:%s" % (args.chroma[1], args.chroma[2]),
+                                  1 << LOG2_TILE_COLS,
+                                  "all keyframes" if gop == 1 else "GOPs of key + %d P" % (gop - 1), args.frames),
+                   "global_batch": args.frames * world, "frames_per_gpu": args.frames,
+                   "parallelism": "frame-sharded x%d (independent %s, no collective)"
+                                  % (world, "keyframes" if gop == 1 else "GOPs"),
+                   "streams_per_gpu": streams, "batches_in_flight": args.inflight,
+                   "ranks": ranks,
+                   "host_gen_s": round(t_gen, 2), "host_stage_s": round(t_stage, 2)},
+    }
+
+
 def dominant_kernel(names, ksum):
     """The roofline's kernel class: the largest serialised time among the pixel kernels
     (the planner's span "k_plan" is excluded, see main)."""
@@ -159,6 +257,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C3", choices=sorted(CONFIGS))
     ap.add_argument("--frames", type=int, default=None, help="frames per GPU (default: the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the per-launch timing steps "
+                         "(roofline), the timed frames against the CPU oracle (verify), the CPU baseline and the "
+                         "host-entropy / decoder / FFHWAccel legs. The --cpu-* and --verify-* options below shape "
+                         "these legs and mean nothing without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the frames the last of them decoded to DIR/<name>.npy "
+                         "(rank 0; see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bounded CPU-baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--verify-all", action="store_true",
@@ -220,18 +326,7 @@ def main():
             dist.barrier()
 
     # per-launch HIP-event kernel timing (roofline): its own steps, launches enqueued one by one
-    dev.set_timing(True)
-    for _ in range(args.warmup):
-        dev.run_batch()
-    dev.sync()
-    ksum = {}
-    for _ in range(args.steps):
-        dev.run_batch()
-        dev.sync()          # collects the per-launch HIP-event times of this step
-        for k, (ms, n) in dev.timing().items():
-            a = ksum.setdefault(k, [0.0, 0])
-            a[0] += ms
-            a[1] += n
+    ksum = serial_timing_steps(dev, args) if args.full or args.serial_only else {}
 
     if args.serial_only:
         kl = {k: int(ksum[k][1] / args.steps) for k in ksum}
@@ -266,6 +361,26 @@ def main():
     names = list(alg.keys())
     fps, ms_per_step = aggregate(args.frames, args.steps, world, elapsed)
     streams = dev.groups()          # frame groups = concurrent HIP streams of the batch
+
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = (args.steps - 1) % args.inflight         # the slot of the last timed step
+        dumped = dump_outputs(v, dev, args.dump_outputs, range(last * args.frames, (last + 1) * args.frames),
+                              geom, args.chroma)
+    if not args.full:
+        # a plain run ends here: the headline figure alone
+        ranks = [rank_identity(v, rank, local_rank)]
+        if dist is not None:
+            ranks = [None] * world
+            dist.all_gather_object(ranks, rank_identity(v, rank, local_rank))
+        out = result_line(args, world, fps, ms_per_step, geom, streams, ranks, t_gen, t_stage)
+        out["dumped"] = dumped
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        dev.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # dominant kernel (largest device time; the timing steps run every launch on one stream,
     # so these are serialised launch durations, as under a rocprofv3 kernel trace). The
@@ -381,9 +496,7 @@ def main():
         verify = verify_frames(v, oracle, dev, frames, refs, geom, args, slots_run,
                                range(min(args.verify_frames_per_rank, len(frames))), threads=1)
         verify["rank"] = rank
-    rank_info = {"rank": rank, "local_rank": local_rank, "device": _device_of(local_rank),
-                 "host": os.uname().nodename}
-    rank_info.update(_device_ids(v, rank_info["device"]))
+    rank_info = rank_identity(v, rank, local_rank)
     ranks = [rank_info]
     if dist is not None:
         got = [None] * world
@@ -422,30 +535,16 @@ def main():
             hw["C2"] = hwaccel_rate(v, encode_sample(v, c2f, 32, 32), 1920, 1080, 8, args)
         e2e["hwaccel_path"] = hw
 
-    out = {
-        "metric": "decoded frames/sec (bit-exact) 4K VP9 Profile-0 @ 1/2/4/8 MI355X; % HBM roofline",
-        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "u8" if BPP == 8 else "u16", "data": "synthetic",
-        "config": {"workload": "%s: %dx%d VP9 Profile-%d %d-bit%s, %d tile columns, %s, %d frames per GPU per step, "
-                               "pass-1 packets resident in HBM"
-                               % (args.config, W, H, (0 if BPP == 8 else 2) | (args.chroma != "420"), BPP,
-                                  "" if args.chroma == "420" else " 4:%s:%s" % (args.chroma[1], args.chroma[2]),
-                                  1 << LOG2_TILE_COLS,
-                                  "all keyframes" if gop == 1 else "GOPs of key + %d P" % (gop - 1), args.frames),
-                   "global_batch": args.frames * world, "frames_per_gpu": args.frames,
-                   "parallelism": "frame-sharded x%d (independent %s, no collective)"
-                                  % (world, "keyframes" if gop == 1 else "GOPs"),
-                   "streams_per_gpu": streams, "batches_in_flight": args.inflight,
-                   "ranks": ranks,
-                   "host_gen_s": round(t_gen, 2), "host_stage_s": round(t_stage, 2)},
+    out = result_line(args, world, fps, ms_per_step, geom, streams, ranks, t_gen, t_stage)
+    out.update({
+        "dumped": dumped,
         "roofline": roofline,
         "cpu_baseline": cpu,
         "verify": verify,
         "verified_frames": verify["frames"] if verify else 0,
         "host_entropy": host,
         "e2e_decoder": e2e,
-    }
+    })
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dev is not None:

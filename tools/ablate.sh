@@ -9,6 +9,6 @@
 set -o pipefail
 O=gpurun_out/ablate_${1:-x}; mkdir -p $O
 for d in ${DBGS:-0 1 2 4 65536 131072 262144}; do
-  VP9HIP_DEBUG=$d timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --verify-frames 0 ${BARGS:-} > $O/dbg_$d.json 2> $O/dbg_$d.err || { echo "dbg=$d failed"; tail -3 $O/dbg_$d.err; exit 1; }
+  VP9HIP_DEBUG=$d timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --verify-frames 0 ${BARGS:-} > $O/dbg_$d.json 2> $O/dbg_$d.err || { echo "dbg=$d failed"; tail -3 $O/dbg_$d.err; exit 1; }
   python3 -c "import json;d=json.loads(open('$O/dbg_$d.json').read().strip().split(chr(10))[-1]);km=d['roofline']['kernel_ms'];print('dbg=$d', d['value'], d['ms_per_step'], {k: v for k, v in km.items() if v})"
 done

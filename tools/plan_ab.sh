@@ -10,7 +10,7 @@ for spec in "$@"; do
   t=${spec%%@*}; ev=""; [ "$t" != "$spec" ] && ev=${spec#*@}
   d=$(cd $OLDPWD && cd $t && pwd); tag=$(basename $d)${ev:+_$ev}
   (cd $d && env VP9HIP_PLAN_ONLY=1 $ev timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/$tag -o run --output-format csv \
-     -- python3 bench.py --inflight 1 --steps 6 --warmup 2 --no-cpu-baseline --verify-frames 0) > $O/$tag.log 2>&1 \
+     -- python3 bench.py --full --inflight 1 --steps 6 --warmup 2 --no-cpu-baseline --verify-frames 0) > $O/$tag.log 2>&1 \
      || { echo "$tag failed"; tail -5 $O/$tag.log; exit 1; }
   echo "== $tag $(grep -o '"value": [0-9.]*' $O/$tag.log | head -1)"
   python3 - "$O/$tag" <<'PY'
