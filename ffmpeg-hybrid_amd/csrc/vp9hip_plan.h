@@ -13,6 +13,11 @@
  * (phase, tcode, segment, txtp, SB) = the launch buckets of the host schedule. MC units
  * have their own count array (entry seg_pre1[seg] + slot_pos[slot]) and scan, in
  * (phase, segment, SB) order.
+ * An SB's tx blocks are enumerated once, by the counting kernel (k_psb): besides the counts it
+ * leaves one TxRec per tx block at slot * JCAP (txrec) and the record / intra job counts per
+ * slot (sb_tn). The emitting kernel (k_pjplan) reads exactly those records, so what is counted
+ * and what is emitted agree by construction; of the arena's JCAP records per slot only the
+ * ones written in the same run are ever read.
  */
 #ifndef VP9HIP_PLAN_H
 #define VP9HIP_PLAN_H
@@ -58,6 +63,21 @@ typedef struct PlanFrame {
 #define PLS_BOUNDS   128u         /* a planner index out of its buffer (internal, status[1]) */
 #define PLS_TOTAL    256u         /* a frame's eob / coefficient totals disagree with its counts */
 
+/* One tx block of an SB as k_psb enumerated it (decode order, the SB's records at
+ * slot * JCAP), all k_pjplan needs to emit the tx block's RJob and intra job word:
+ *   w: plane | tx size << 2 | ux0 << 12 | uy0 << 16 (the PJob word's fields); for an intra job
+ *      of this context also bit 31 (TXR_JOB) and pl_intra_job's other inputs: the intra mode
+ *      << 8, and bit 5 (TXR_RIGHT) when the tx block is not in the block's last tx column
+ *   m: eob (11 bits) | residual key tcode * 4 + txtp << 11 (5 bits) | emits a residual job
+ *      << 16 | rank among the SB's jobs of that key << 17 (10 bits: JCAP is 768 at 4:4:4) */
+typedef struct __attribute__((aligned(8))) TxRec { uint32_t w, m; } TxRec;
+#define TXR_JOB      (1u << 31)
+#define TXR_RIGHT    (1u << 5)
+#define TXR_EOB(m)   ((m) & 2047u)
+#define TXR_KEY(m)   (((m) >> 11) & 31u)
+#define TXR_EMIT(m)  (((m) >> 16) & 1u)
+#define TXR_RANK(m)  (((m) >> 17) & 1023u)
+
 /* Device buffers of a device-planned batch (all in the batch arena). */
 typedef struct PlanDev {
     const PlanFrame  *frames;
@@ -85,15 +105,15 @@ typedef struct PlanDev {
     /* products */
     SBRec *sbs; WGRec *wgs; PJob *pjobs; uint32_t *passes; LFRec *lfs; RJob *rjobs; McUnit *mcs;
     uint32_t *dlists;                /* intra step lists (device part of the lists array)    */
-    uint32_t *jobw;                  /* per slot: jcap intra job words (k_pjob -> k_plan)     */
-    uint32_t *sb_nj;                 /* per slot: intra jobs                                 */
+    TxRec    *txrec;                 /* per slot: jcap tx records (k_psb -> k_pjplan)         */
+    uint32_t *sb_tn;                 /* per slot: tx records written | intra jobs << 16      */
     const uint8_t *nz;               /* [5][4][1025][2] nonzero bounding boxes                */
     uint32_t jcap, rcap;             /* jobs / residual units per SB slot                    */
     uint32_t nslots;
     /* capacities: every planner write is checked against them; a violation sets a bit of
      * status[1] (and PLS_SCHED) instead of writing */
     uint32_t cap_cnt, cap_cntm, cap_rjobs, cap_mcs, cap_dlists, nkeys, nframes;
-    unsigned long long *prof;        /* diagnostics (VP9HIP_PLAN_PROF): k_plan cycles per phase, or null */
+    unsigned long long *prof;        /* diagnostics (VP9HIP_PLAN_PROF): k_psb / k_pjplan cycles per phase, or null */
     int dbg;                         /* diagnostics (VP9HIP_PLAN_DBG): ablation switches, timing only */
     int static_lists;                /* the intra step lists were staged by the host (static plan):  */
                                      /* no step keys; an intra-frame SB without intra jobs fails    */

@@ -7,13 +7,15 @@
 //   k_pblk   one thread per block: the SB slot of each block, the slots' block ranges,
 //            decode-order validation, eob entries per block
 //   (scan)   eob entries -> each block's first eob
-//   k_psb    one wave per SB: per-tx eobs -> coefficient total, residual-job counts per
-//            (tcode, txtp), MC-unit count, the intra 4x4-unit map
+//   k_psb    one wave per SB, the one enumeration of its tx blocks in decode order: eobs ->
+//            coefficient total, residual-job counts per (tcode, txtp), MC-unit count, the intra
+//            4x4-unit map, and one record per tx block (TxRec: eob, key, rank within the key,
+//            position, intra mode)
 //   (scan)   coefficients (decode order) -> each SB's first coefficient; counts -> record offsets
-//   k_pjob   one wave per SB: the tx blocks in decode order, eobs, coefficient offsets,
-//            residual jobs, intra job words with check_intra_mode resolved (vp9recon.c:37-221)
-//   k_plan   one wave per SB: the intra jobs' producers, heights, list-scheduled passes (the
-//            host's merge_mixed, restated wave-parallel), the SB's intra step
+//   k_pjplan one wave per SB: from the records, the residual jobs and the intra job words with
+//            check_intra_mode resolved (vp9recon.c:37-221); then the intra jobs' producers,
+//            heights, list-scheduled passes (the host's merge_mixed, restated wave-parallel),
+//            the SB's intra step
 //   k_pllf   one wave per SB: the LF program (vp9block.c:1142-1262, vp9lpf.c:31-230)
 //   k_plmc   one wave per SB of inter frames: MC units (vp9_mc_template.c:30-464)
 //   k_plevel one workgroup per level-scheduled inter frame: SB dependency levels along
@@ -86,7 +88,7 @@ DEV vp9h_block load_block(const vp9h_block *g)
     if (b.uvtx > 3) b.uvtx = 0;
     return b;
 }
-// The block fields k_plan's tx enumeration reads (16 bytes in LDS instead of 52).
+// The block fields the tx enumeration reads (16 bytes in LDS instead of 52).
 struct PBlk {
     uint16_t row, col;
     uint8_t bs, tx, uvtx, skip, intra, uvmode;
@@ -108,9 +110,17 @@ DEV bool block_ok(const vp9h_block &b)
 }
 
 // Per (block, plane) tx-block counts, packed all | eob << 10 | intra jobs << 20, and their
-// exclusive scan over the SB's blocks in decode order (pre[3 * nb] = totals).
+// exclusive scan over the SB's blocks in decode order (pre[3 * nb] = totals); ent: the tx grid
+// of each (block, plane) entry, so the per-tx code reads one word instead of redoing pl_txgrid:
+// txs | tx blocks per row << 2 | the entry's first 4x4 unit in its SB plane, x << 7, y << 11 |
+// the block's width in the plane (4x4 units) << 15
+#define ENT_TXS(e) ((int) ((e) & 3))
+#define ENT_NX(e)  ((int) (((e) >> 2) & 31))
+#define ENT_UX(e)  ((int) (((e) >> 7) & 15))
+#define ENT_UY(e)  ((int) (((e) >> 11) & 15))
+#define ENT_PW4(e) ((int) (((e) >> 15) & 31))
 template <int SSH, int SSV, class B>
-DEV uint32_t sb_prefix(const B *blk, int nb, int cols, int rows, bool mine, uint32_t *pre, int lane)
+DEV uint32_t sb_prefix(const B *blk, int nb, int cols, int rows, bool mine, uint32_t *pre, uint32_t *ent, int lane)
 {
     uint32_t v[3] = { 0, 0, 0 };
     if (lane < nb) {
@@ -119,6 +129,9 @@ DEV uint32_t sb_prefix(const B *blk, int nb, int cols, int rows, bool mine, uint
             const PlTxGrid g = pl_txgrid(b, p, cols, rows, SSH, SSV);
             const uint32_t n = (uint32_t) (g.nx * g.ny);
             v[p] = n | (b.skip ? 0u : n) << 10 | (b.intra && mine ? n : 0u) << 20;
+            const int sh = p ? SSH : 0, sv = p ? SSV : 0;
+            ent[3 * lane + p] = (uint32_t) g.txs | (uint32_t) (g.nx & 31) << 2 | (uint32_t) ((g.bx >> 2) & ((16 >> sh) - 1)) << 7 |
+                                (uint32_t) ((g.by >> 2) & ((16 >> sv) - 1)) << 11 | (uint32_t) (g.pw4 & 31) << 15;
         }
     }
     const uint32_t sum = v[0] + v[1] + v[2];
@@ -134,69 +147,11 @@ DEV uint32_t sb_prefix(const B *blk, int nb, int cols, int rows, bool mine, uint
     return tot;
 }
 
-// (block, plane) entry of tx t: the largest k with all-prefix(k) <= t
-DEV int sb_locate(const uint32_t *pre, int n3, uint32_t t)
-{
-    int lo = 0, hi = n3 - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((pre[mid] & 1023) <= t) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-struct Tx {
-    int b, p, k;            // block, plane, (block, plane) entry
-    int l, x, y;            // index in the plane's tx grid, position (4x4 units in the block)
-    PlTxGrid g;
-};
 // q = l / n for l < 4096, 1 <= n <= 16: the multiply by ceil(2^16 / n) is exact there
 DEV int udiv16(int l, int n)
 {
     return (int) (((uint32_t) l * ((65536u + (uint32_t) n - 1) / (uint32_t) n)) >> 16);
 }
-template <int SSH, int SSV, class B>
-DEV Tx sb_tx_at(const B *blk, const uint32_t *pre, int k, uint32_t t, int cols, int rows)
-{
-    Tx r;
-    r.k = k;
-    r.b = (k * 171) >> 9;                    // k / 3 for k < 192
-    r.p = r.k - 3 * r.b;
-    r.l = (int) (t - (pre[r.k] & 1023));
-    r.g = pl_txgrid(blk[r.b], r.p, cols, rows, SSH, SSV);
-    const int nx = r.g.nx > 0 ? r.g.nx : 1;
-    const int q = udiv16(r.l, nx);
-    r.x = (r.l - q * nx) << r.g.txs;
-    r.y = q << r.g.txs;
-    return r;
-}
-template <int SSH, int SSV>
-DEV Tx sb_tx(const vp9h_block *blk, const uint32_t *pre, int nb, uint32_t t, int cols, int rows)
-{
-    return sb_tx_at<SSH, SSV>(blk, pre, sb_locate(pre, 3 * nb, t), t, cols, rows);
-}
-
-// The eob of tx t (0 for skipped blocks), range-checked against the packet. (A frame whose
-// eob count disagrees with its packet shifts the later frames' eobs: k_pkeys' totals check
-// rejects the batch then, PLS_TOTAL.)
-template <class B> DEV int tx_eob(const PlanDev &D, const B &b, const Tx &tx, const uint32_t *pre, uint32_t b0, uint32_t &st)
-{
-    if (b.skip) return 0;
-    const uint32_t i = D.blk_eob0[b0 + tx.b] + ((pre[tx.k] & 1023) - (pre[3 * tx.b] & 1023)) + (uint32_t) tx.l;
-    if (i >= D.total_eobs) { st |= PLS_EOB; return 0; }
-    const int e = D.eobs[i];
-    if (e > (16 << (2 * tx.g.txs))) { st |= PLS_EOB; return 0; }
-    return e;
-}
-
-template <class B> DEV int tx_mode(const B &b, const Tx &tx, uint32_t &st)
-{
-    const int m = tx.p ? b.uvmode : b.mode[b.bs > VP9H_BS_8x8 && b.tx == 0 ? tx.y * 2 + tx.x : 0];
-    if (m > 9) { st |= PLS_MODE; return 0; }
-    return m;
-}
-
 DEV bool mc_refs_ok(const vp9h_block &b, const PlMcGeo &g)
 {
     if (b.ref[0] > 2 || (b.comp && b.ref[1] > 2)) return false;
@@ -274,74 +229,171 @@ __global__ __launch_bounds__(256) void k_pblk(PlanDev D)
     if (st) plan_fail(D, F, st);
 }
 
+// VP9HIP_PLAN_PROF: shader-clock cycles of each k_psb / k_pjplan phase, summed over the SBs
+#define PPT(k) do { if (D.prof) { const unsigned long long t_ = clock64(); \
+        if (lane == 0) atomicAdd(&D.prof[k], t_ - pt0); pt0 = t_; } } while (0)
+#define JA_TRX (1u << 30)     // PlanLds.ja: the 4x4 top-right lies inside the block (trx)
+
+// ------------------------------------------------------------------ the SB's tx enumeration
+// The front half of the enumeration of an SB's tx blocks in decode order: its blocks, the
+// per-(block, plane) prefix counts, the first tx of every (block, plane) entry (ost, for the
+// max-scan of sb_own) and the SB's window of eob entries.
+template <int JCAP> struct SbEnumLds {
+    PBlk blk[64];
+    uint32_t pre[3 * 64 + 1];
+    uint32_t ent[3 * 64];         // tx grid of each (block, plane) entry (ENT_*)
+    uint32_t eb[64];              // first eob entry of each block
+    alignas(4) uint16_t ost[JCAP];   // (block, plane) entry starting at tx t, else 0
+};
+struct SbEnum {
+    int nb, T;                    // blocks, tx blocks (clamped to JCAP)
+    uint32_t b0, tot;             // first block, sb_prefix's totals
+    uint32_t E0, E;               // the SB's eob entries: D.eobs[E0 .. E0 + E)
+};
+template <int SSH, int SSV, int JCAP>
+DEV SbEnum sb_enum(const PlanDev &D, const PlanFrame &F, const SbGeo &G, SbEnumLds<JCAP> &S, vp9h_block &own, uint32_t &st,
+                   int lane)
+{
+    SbEnum R;
+    R.nb = sb_blocks(D, G.slot, R.b0, st);
+    uint32_t be = 0;
+    if (lane < R.nb) {
+        own = load_block(&D.blocks[R.b0 + lane]);
+        S.blk[lane] = pblk(own);
+        be = D.blk_eob0[R.b0 + (uint32_t) lane];
+        S.eb[lane] = be;
+    }
+    // the SB's eob entries are contiguous in the packet (its coded blocks' tx in decode order)
+    R.E0 = rdl(be, 0);
+    const uint32_t E1 = R.nb ? D.blk_eob0[R.b0 + (uint32_t) R.nb] : R.E0;
+    R.E = E1 - R.E0;
+    if (E1 < R.E0 || R.E > (uint32_t) JCAP || E1 > D.total_eobs) { st |= PLS_EOB; R.E = 0; }
+    for (int i = lane; i < JCAP / 2; i += 64) ((uint32_t *) S.ost)[i] = 0;
+    wsync();
+    R.tot = sb_prefix<SSH, SSV>(S.blk, R.nb, F.mc.cols, F.mc.rows, G.mine, S.pre, S.ent, lane);
+    R.T = pl_min((int) (R.tot & 1023), JCAP);
+    // each non-empty (block, plane) entry marks its first tx (the ranges are disjoint)
+    if (lane < R.nb)
+        for (int p = 0; p < 3; p++) {
+            const int k = 3 * lane + p;
+            const uint32_t a0 = S.pre[k] & 1023, a1 = S.pre[k + 1] & 1023;
+            if (a1 > a0 && a0 < (uint32_t) R.T) S.ost[a0] = (uint16_t) k;
+        }
+    wsync();
+    return R;
+}
+// The (block, plane) entry of tx c + lane of a chunk of 64: a max-scan over the entries'
+// first tx (the largest k with pre[k] <= t); carry runs from chunk to chunk.
+DEV int sb_own(const uint16_t *ost, int c, int T, uint32_t &carry, int lane)
+{
+    const uint32_t v = c + lane < T ? ost[c + lane] : 0u;
+    const uint32_t incl = dpp_op<OP_MAX>(wscan_dpp<OP_MAX>(v), carry);
+    carry = rdl(incl, 63);
+    return (int) incl;
+}
+// The eob of tx t of the SB, in block b (0 for skipped blocks, which have no entries): one
+// load from the SB's eob window, range-checked against the window and the tx size. (A frame whose eob
+// count disagrees with its packet shifts the later frames' eobs: k_pkeys' totals check
+// rejects the batch then, PLS_TOTAL.)
+template <int JCAP>
+DEV int sb_tx_eob(const PlanDev &D, const SbEnumLds<JCAP> &S, const SbEnum &R, int b, int txs, uint32_t t, uint32_t &st)
+{
+    if (S.blk[b].skip) return 0;
+    const uint32_t i = S.eb[b] - R.E0 + t - (S.pre[3 * b] & 1023);
+    if (i >= R.E) { st |= PLS_EOB; return 0; }
+    const int e = D.eobs[R.E0 + i];
+    if (e > (16 << (2 * txs))) { st |= PLS_EOB; return 0; }
+    return e;
+}
+
 // ------------------------------------------------------------------ k_psb
-// Residual-job counts: lane k holds key k's count, one ballot per distinct key of a chunk.
+// The one enumeration of the SB's tx blocks: the counts the scans need (residual jobs per
+// key, coefficients, MC units), the intra unit map, and one TxRec per tx block for k_pjplan,
+// which emits from the records alone (what is counted is what is emitted).
+// Residual-job counts: lane k holds key k's count, one ballot per distinct key of a chunk;
+// a job's rank within its key is the count before the chunk plus its position in the ballot.
 // Intra unit map: ORed into IBC copies of the 24 map words (copy = lane & 3), so at most a
 // quarter of a chunk's lanes share an address. Round 4's per-lane map columns (6.2 KB of
 // LDS) removed the conflicts but cut occupancy from 32 to 15 waves per CU and made the
-// kernel 1.58x slower; the blocks are held as 16-byte PBlk for the same reason (LDS 2.2 KB
-// per workgroup: the 32-waves/CU cap binds, not LDS).
+// kernel 1.58x slower; the blocks are held as 16-byte PBlk for the same reason (LDS 3.9 KB
+// per workgroup at 4:2:0, 4.6 KB at 4:4:4: the 32-waves/CU cap binds, not LDS).
+// The kernel is bound by the instructions it issues (8 waves per SIMD hide its loads), so
+// per-tx work that k_pjplan can do from the record is left to it (pl_intra_job).
 #define IBC 4
 template <int SSH, int SSV>
 __global__ __launch_bounds__(64) void k_psb(PlanDev D)
 {
     constexpr int CW = 16 >> SSH, CH = 16 >> SSV, JCAP = 256 + 2 * CW * CH;
-    __shared__ PBlk blk[64];
-    __shared__ uint32_t pre[3 * 64 + 1];
+    __shared__ SbEnumLds<JCAP> S;
     __shared__ uint32_t ibw[24 * IBC];
-    const PlanFrame &F = D.frames[blockIdx.y];
+    const PlanFrame F = D.frames[blockIdx.y];     // by value, before any store: one batch of scalar loads
+    const PlMcGeo &mcg = D.frames[blockIdx.y].mc; // the reference scales are indexed: left in memory
     const int s = blockIdx.x, lane = threadIdx.x;
     if (s >= F.sb_cols * F.sb_rows) return;
+    unsigned long long pt0 = D.prof ? clock64() : 0;
     const SbGeo G = sb_geo(F, s);
     const int cols = F.mc.cols, rows = F.mc.rows;
-    uint32_t st = 0, b0;
-    const int nb = sb_blocks(D, G.slot, b0, st);
+    uint32_t st = 0;
     if (lane < 24 * IBC / 2) { ibw[2 * lane] = 0; ibw[2 * lane + 1] = 0; }
     vp9h_block own;
-    if (lane < nb) {
-        own = load_block(&D.blocks[b0 + lane]);
-        blk[lane] = pblk(own);
-    }
-    wsync();
-    const uint32_t tot = sb_prefix<SSH, SSV>(blk, nb, cols, rows, G.mine, pre, lane);
-    const uint32_t T = pl_min((int) (tot & 1023), JCAP);
-    uint32_t ncoef = 0, kcnt = 0;
-    for (uint32_t t0 = 0; t0 < T; t0 += 64) {
-        const uint32_t t = t0 + (uint32_t) lane;
+    const SbEnum R = sb_enum<SSH, SSV>(D, F, G, S, own, st, lane);
+    const int nb = R.nb, T = R.T;
+    const bool rec_ok = inb(D, G.slot, D.nslots, 4u);
+    TxRec *rec = D.txrec + (size_t) G.slot * JCAP;
+    PPT(0);
+    uint32_t ncoef = 0, kcnt = 0, ocarry = 0;
+    for (int c = 0; c < T; c += 64) {
+        const int t = c + lane;
+        const int k = sb_own(S.ost, c, T, ocarry, lane);
         int key = -1;
+        uint32_t w = 0, m = 0;
         if (t < T) {
-            const Tx tx = sb_tx_at<SSH, SSV>(blk, pre, sb_locate(pre, 3 * nb, t), t, cols, rows);
-            const PBlk &b = blk[tx.b];
-            const int e = tx_eob(D, b, tx, pre, b0, st);
+            const int bi = (k * 171) >> 9, p = k - 3 * bi;      // k / 3 for k < 192
+            const uint32_t en = S.ent[k];
+            const PBlk &b = S.blk[bi];
+            const int sh = p ? SSH : 0, sv = p ? SSV : 0, txs = ENT_TXS(en), step = 1 << txs;
+            const int l = t - (int) (S.pre[k] & 1023), nx = pl_max(ENT_NX(en), 1), q = udiv16(l, nx);
+            const int x = (l - q * nx) << txs, y = q << txs;        // 4x4 units in the block
+            const int e = sb_tx_eob(D, S, R, bi, txs, (uint32_t) t, st);
             ncoef += (uint32_t) e;
-            int txtp = 0;
+            int mode = 0, txtp = 0;
             if (b.intra) {
-                const int mode = tx_mode(b, tx, st);
-                txtp = tx.p || tx.g.txs == 3 ? 0 : pl_intra_txfm_type(mode);
+                mode = p ? b.uvmode : b.mode[b.bs > VP9H_BS_8x8 && b.tx == 0 ? y * 2 + x : 0];
+                if (mode > 9) { st |= PLS_MODE; mode = 0; }
+                txtp = p || txs == 3 ? 0 : pl_intra_txfm_type(mode);
             }
-            if (e && G.mine) key = (F.lossless ? 4 : tx.g.txs) * 4 + txtp;
-            if (b.intra && G.mine) {            // the job's 4x4 units in the SB plane's unit map
-                const int sh = tx.p ? SSH : 0, sv = tx.p ? SSV : 0;
+            const int ux0 = ENT_UX(en) + x, uy0 = ENT_UY(en) + y;
+            m = (uint32_t) e | (uint32_t) ((F.lossless ? 4 : txs) * 4 + txtp) << 11;
+            if (e && G.mine) { key = (int) TXR_KEY(m); m |= 1u << 16; }
+            w = (uint32_t) p | (uint32_t) txs << 2 | (uint32_t) (ux0 & 15) << 12 | (uint32_t) (uy0 & 15) << 16;
+            if (b.intra && G.mine) {
+                // the job's 4x4 units in the SB plane's unit map
                 const int units = 16 >> sh, unitsv = 16 >> sv;
-                const int ux0 = ((tx.g.bx - G.sbx * (64 >> sh)) >> 2) + tx.x, uy0 = ((tx.g.by - G.sby * (64 >> sv)) >> 2) + tx.y;
-                uint32_t m = 0;
-                for (int u = ux0; u < ux0 + tx.g.step && u < units; u++) m |= 1u << u;
-                for (int v = uy0; v < uy0 + tx.g.step && v < unitsv; v++)
-                    atomicOr(&ibw[(tx.p * 8 + (v >> 1)) * IBC + (lane & (IBC - 1))], m << ((v & 1) * 16));
+                uint32_t um = 0;
+                for (int u = ux0; u < ux0 + step && u < units; u++) um |= 1u << u;
+                for (int v = uy0; v < uy0 + step && v < unitsv; v++)
+                    atomicOr(&ibw[(p * 8 + (v >> 1)) * IBC + (lane & (IBC - 1))], um << ((v & 1) * 16));
+                // pl_intra_job's other inputs: k_pjplan resolves check_intra_mode
+                w |= (uint32_t) mode << 8 | (x < ENT_PW4(en) - 1 ? TXR_RIGHT : 0u) | TXR_JOB;
             }
         }
+        // counts and ranks within each key, in decode order: one ballot per distinct key
         uint64_t pend = __ballot(key >= 0);
         while (pend) {
             const int kk = rdl(key, __builtin_ctzll(pend));
-            const uint64_t m = __ballot(key == kk);
-            if (lane == kk) kcnt += (uint32_t) __popcll(m);
-            pend &= ~m;
+            const uint64_t mk = __ballot(key == kk);
+            const uint32_t base = rdl(kcnt, kk);
+            if (key == kk) m |= (base + mbcnt(mk)) << 17;
+            if (lane == kk) kcnt += (uint32_t) __popcll(mk);
+            pend &= ~mk;
         }
+        if (t < T && rec_ok) { TxRec r; r.w = w; r.m = m; rec[t] = r; }
     }
+    PPT(1);
     // MC units of the SB's inter blocks
     uint32_t nmc = 0;
     if (lane < nb && G.mine && !own.intra) {
-        if (mc_refs_ok(own, F.mc)) nmc = (uint32_t) pl_mc_block(own, F.mc, 0, [](const McUnit &) {});
+        if (mc_refs_ok(own, mcg)) nmc = (uint32_t) pl_mc_block(own, mcg, 0, [](const McUnit &) {});
         else st |= PLS_REF;
     }
     nmc = wsum(nmc);
@@ -359,23 +411,15 @@ __global__ __launch_bounds__(64) void k_psb(PlanDev D)
         const uint32_t ci = D.seg_pre1[G.seg] + D.slot_pos[G.slot];
         if (inb(D, ci, D.cap_cntm, 2u)) D.cntm[ci] = nmc;
     }
-    if (lane < 24 && inb(D, G.slot, D.nslots, 4u)) D.ibits[(size_t) G.slot * 24 + lane] = ib;
+    if (lane < 24 && rec_ok) D.ibits[(size_t) G.slot * 24 + lane] = ib;
+    if (lane == 0 && rec_ok) D.sb_tn[G.slot] = (uint32_t) T | (uint32_t) pl_min((int) (R.tot >> 20), JCAP) << 16;
     if (lane == 0 && inb(D, G.dord, D.nslots, 8u)) D.sb_ncoef[G.dord] = ncoef;
     if (st) plan_fail(D, F, st);
+    PPT(2);
 }
 
-// ------------------------------------------------------------------ k_plan
-// k_pjob's LDS: the SB's blocks and its tx enumeration.
-template <int JCAP> struct PJobLds {
-    PBlk blk[64];
-    uint32_t pre[3 * 64 + 1];
-    uint16_t et[JCAP];            // eob per tx (decode order)
-    uint16_t co[JCAP];            // SB-relative first coefficient per tx; first the raw eobs
-    uint16_t ost[JCAP];           // (block, plane) entry starting at tx t, else 0
-    uint8_t  own[JCAP];           // (block, plane) entry of tx t (max-scan of ost)
-    uint32_t eb[64];              // first eob entry of each block
-};
-// k_plan's LDS: the unit map, then the heights, then the priority order with the pass of
+// ------------------------------------------------------------------ k_pjplan
+// plan_sb's LDS: the unit map, then the heights, then the priority order with the pass of
 // each job share one region, each dead before the next is written (7.2 KB at 4:2:0; with ord
 // and sch after the heights 8.75 KB: 17 instead of 21 workgroups per CU)
 template <int JCAP> struct alignas(16) PlanLds {   // 16: jmap rows are stored 16 bytes at a time
@@ -399,7 +443,6 @@ template <int JCAP> struct alignas(16) PlanLds {   // 16: jmap rows are stored 1
     } u;
 };
 static_assert(sizeof(uint16_t[3][256]) <= sizeof(uint32_t[256 + 2 * 64]), "the unit map fits the heights' region");
-#define JA_TRX (1u << 30)
 // unit-map entry: job | units to its right edge << 10 | units to its bottom edge << 13 (0..7
 // each: a job is at most 8 units wide); 0xffff (job 1023 > JCAP) marks a unit no job covers
 #define JM_ENT(j, r, b) ((uint32_t) (j) | (uint32_t) (r) << 10 | (uint32_t) (b) << 13)
@@ -411,214 +454,147 @@ DEV uint32_t needs_of(uint32_t a)
 }
 DEV uint32_t wor(uint32_t v) { return rdl(wscan_dpp<OP_OR>(v), 63); }
 
-// VP9HIP_PLAN_PROF: shader-clock cycles of each k_plan phase, summed over the SBs
-#define PPT(k) do { if (D.prof) { const unsigned long long t_ = clock64(); \
-        if (lane == 0) atomicAdd(&D.prof[k], t_ - pt0); pt0 = t_; } } while (0)
-
-// One wave per SB: the SB's tx blocks in decode order (the (block, plane) entry of each
-// by a max-scan), their eobs and coefficient offsets, the residual jobs (every coded tx,
-// bucketed by transform), and the intra jobs' words with check_intra_mode resolved, for
-// k_plan. Small LDS (4.8 KB at 4:2:0): a kernel of its own so this per-tx work runs at full
-// occupancy instead of with k_plan's scheduling state.
-// ja: k_pjplan's LDS job words (the intra job words go there, not to D.jobw); returns the
-// SB's intra job count for k_plan's part, -1 past the frame
+// One wave per SB: the residual jobs (every coded tx block, bucketed by transform) and the
+// intra job words of the SB, from k_psb's records alone: no block, no eob entry is read again.
+// A job's position is its key's scanned base (lanes 0..19 hold the 20 bases, fetched by key
+// across lanes) plus its rank in the record, so every counted position is written, with an
+// eob-0 job where the coefficient check fails.
+// The wave's loads are issued in three batches, not one chain per chunk: the SB's header
+// words with the first chunk of records (its address needs only the slot; lanes past the
+// record count are masked afterwards), then the key bases with the other chunks, then the
+// nonzero boxes of every chunk; the stores follow (six chunks at a time: one group at 4:2:0,
+// two at 4:4:4, whose records would not fit the registers). Bounds failures are reported at the end
+// (an atomic in between would turn the later uniform loads into dependent vector loads).
+// ja: k_pjplan's LDS job words; returns the SB's intra job count
 template <int SSH, int SSV>
-DEV int pjob_sb(const PlanDev &D, PJobLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> &S, uint32_t *ja)
+DEV int pjob_sb(const PlanDev &D, const PlanFrame &F, uint32_t *ja)
 {
-    constexpr int CW = 16 >> SSH, CH = 16 >> SSV, JCAP = 256 + 2 * CW * CH;
-    const PlanFrame &F = D.frames[blockIdx.y];
+    constexpr int CW = 16 >> SSH, CH = 16 >> SSV, JCAP = 256 + 2 * CW * CH, NCH = 6;
     const int s = blockIdx.x, lane = threadIdx.x;
-    if (s >= F.sb_cols * F.sb_rows) return -1;
     unsigned long long pt0 = D.prof ? clock64() : 0;
     const SbGeo G = sb_geo(F, s);
-    const int cols = F.mc.cols, rows = F.mc.rows;
     const uint32_t slot = G.slot;
-    uint32_t st = 0, b0;
-    const int nb = sb_blocks(D, slot, b0, st);
-    st = 0;                                   // reported by k_psb
-    if (lane < nb) S.blk[lane] = pblk(load_block(&D.blocks[b0 + lane]));
-    wsync();
-    const uint32_t tot = sb_prefix<SSH, SSV>(S.blk, nb, cols, rows, G.mine, S.pre, lane);
-    const int T = pl_min((int) (tot & 1023), JCAP), NJ = pl_min((int) (tot >> 20), JCAP);
-    // the (block, plane) entry of every tx: each non-empty entry marks its first tx (ranges
-    // are disjoint), a max-scan fills the rest (= sb_locate's largest k with pre[k] <= t)
-    for (int t = lane; t < T; t += 64) S.ost[t] = 0;
-    wsync();
-    if (lane < nb)
-        for (int p = 0; p < 3; p++) {
-            const int k = 3 * lane + p;
-            const uint32_t a0 = S.pre[k] & 1023, a1 = S.pre[k + 1] & 1023;
-            if (a1 > a0 && a0 < (uint32_t) T) S.ost[a0] = (uint16_t) k;
-        }
-    wsync();
-    {
-        uint32_t carry = 0;
-        for (int c = 0; c < T; c += 64) {
-            const uint32_t v = c + lane < T ? S.ost[c + lane] : 0u;
-            const uint32_t incl = dpp_op<OP_MAX>(wscan_dpp<OP_MAX>(v), carry);
-            if (c + lane < T) S.own[c + lane] = (uint8_t) incl;
-            carry = rdl(incl, 63);
-        }
-    }
-    wsync();
-    PPT(0);
-
-    // ---- eobs and SB-relative coefficient offsets (decode order). The SB's eob entries are
-    // contiguous in the packet (its coded blocks' tx in decode order): one coalesced load
-    // into LDS, then each tx picks its entry (skipped blocks have none)
-    {
-        const uint32_t be = lane <= nb ? D.blk_eob0[b0 + (uint32_t) lane] : 0u;      // nb + 1 entries
-        if (lane < nb) S.eb[lane] = be;
-        const uint32_t E0 = rdl(be, 0), E1 = rdl(be, nb);
-        uint32_t E = E1 - E0;
-        if (E1 < E0 || E > (uint32_t) JCAP || E1 > D.total_eobs) { st |= PLS_EOB; E = 0; }
-        for (uint32_t i = (uint32_t) lane; i < E; i += 64) S.co[i] = D.eobs[E0 + i];
-        wsync();
-        for (int t = lane; t < T; t += 64) {
-            const int k = S.own[t], b = (k * 171) >> 9;
-            const PBlk &bk = S.blk[b];
-            int e = 0;
-            if (!bk.skip) {
-                const uint32_t i = S.eb[b] - E0 + (uint32_t) t - (S.pre[3 * b] & 1023);
-                const int txs = (k - 3 * b) ? bk.uvtx : bk.tx;
-                if (i < E) e = S.co[i];
-                else st |= PLS_EOB;
-                if (e > (16 << (2 * txs))) { st |= PLS_EOB; e = 0; }
-            }
-            S.et[t] = (uint16_t) e;
-        }
-    }
-    wsync();
-    {
-        uint32_t carry = 0;
-        for (int c = 0; c < T; c += 64) {
-            const uint32_t v = c + lane < T ? S.et[c + lane] : 0u;
-            const uint32_t incl = wscan_incl(v, lane);
-            if (c + lane < T) S.co[c + lane] = (uint16_t) (carry + incl - v);
-            carry += rdl(incl, 63);
-        }
-    }
-    // record bases of the SB: lanes 0..19 residual keys (tcode * 4 + txtp), lane 20 MC units;
-    // rl: the end of the key's range (k_psb's count), which no emitted job may pass
-    uint32_t rb = 0, rl = 0;
+    uint32_t st = 0, bf = 0;                  // PLS_* bits, status[1] bits of failed bounds
+    if (slot >= D.nslots) bf |= 4u;
+    if (G.dord >= D.nslots) bf |= 32u;
+    const TxRec *rec = D.txrec + (size_t) slot * JCAP;
+    TxRec x[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) x[c].w = x[c].m = 0;
+    if (!bf) x[0] = rec[lane];
+    const uint32_t tn = bf ? 0u : D.sb_tn[slot];
+    const uint32_t coef_sb = bf ? 0u : D.sb_coef0[G.dord];
+    // record bases of the SB's residual keys (tcode * 4 + txtp) in lanes 0..19
+    uint32_t rb = 0;
     if (lane < 20) {
         const uint32_t ci = cnt_idx(D, F, G.seg, slot, lane >> 2, lane & 3);
-        if (inb(D, ci, D.cap_cnt, 16u)) { rb = D.cnt0[ci]; rl = rb + D.cnt[ci]; }
-    } else if (lane == 20) {
-        const uint32_t ci = D.seg_pre1[G.seg] + D.slot_pos[slot];
-        rb = inb(D, ci, D.cap_cntm, 16u) ? D.cntm0[ci] : 0u;
+        if (ci < D.cap_cnt) rb = D.cnt0[ci];
+        else bf |= 16u;
     }
-    const uint32_t coef_sb = inb(D, G.dord, D.nslots, 32u) ? D.sb_coef0[G.dord] : 0u;
+    const int T = pl_min((int) (tn & 0xffff), JCAP), NJ = pl_min((int) (tn >> 16), JCAP);
+    if (lane >= T) x[0].w = x[0].m = 0;
     const uint32_t rbase = slot * D.rcap;
+    const uint16_t *nz16 = (const uint16_t *) D.nz;        // nzc | nzr << 8 per (key, eob)
+    const int cols = F.mc.cols, rows = F.mc.rows, tx0l = G.tile_sb0 * 64;
+    uint32_t carry = 0;                       // SB-relative first coefficient of the chunk
     unsigned long long ibytes = 0;
-    wsync();
-    PPT(1);
-
-    // ---- residual jobs (every coded tx block) and intra jobs with their unit map
-    const int tx0l = G.tile_sb0 * 64;
-    for (int c = 0; c < T; c += 64) {
-        const int t = c + lane;
-        int key = -1;
-        RJob r;
-        if (t < T) {
-            const Tx tx = sb_tx_at<SSH, SSV>(S.blk, S.pre, S.own[t], (uint32_t) t, cols, rows);
-            const PBlk &b = S.blk[tx.b];
-            const int p = tx.p, sh = p ? SSH : 0, sv = p ? SSV : 0, txs = tx.g.txs;
-            const int e0 = S.et[t];
-            int mode = 0, txtp = 0;
-            if (b.intra) {
-                mode = tx_mode(b, tx, st);
-                txtp = p || txs == 3 ? 0 : pl_intra_txfm_type(mode);
-            }
-            const int tcode = F.lossless ? 4 : txs;
-            const int ux0 = ((tx.g.bx - G.sbx * (64 >> sh)) >> 2) + tx.x, uy0 = ((tx.g.by - G.sby * (64 >> sv)) >> 2) + tx.y;
-            const uint32_t roff = rbase + pl_resid_unit(p, ux0, uy0, SSH, SSV);
-            if (e0 && G.mine) {
-                uint32_t coef = coef_sb + S.co[t];
-                int e = e0;
-                if (coef + (uint32_t) e > D.total_coefs) { st |= PLS_COEF; e = 0; coef = 0; }
-                r.coef = coef;
-                r.eob = (uint16_t) e;
-                r.frame = (uint16_t) F.frame;
-                r.ptx = (uint8_t) (p | tcode << 2 | (b.intra ? 0 : 1) << 5 | txtp << 6);
-                r.nzc = D.nz[(((tcode * 4 + txtp) * 1025) + e) * 2];
-                r.nzr = D.nz[(((tcode * 4 + txtp) * 1025) + e) * 2 + 1];
-                r.pad = 0;
-                if (b.intra) r.dst = roff;
-                else {
-                    r.dst = (uint32_t) ((size_t) (tx.g.by + tx.y * 4) * F.pitch[p ? 1 : 0] + tx.g.bx + tx.x * 4);
-                    ibytes += (unsigned long long) (2 * (16 << (2 * txs)) * F.bypp);
-                }
-                key = tcode * 4 + txtp;
-            }
-            if (b.intra && G.mine) {
-                const int j = (int) (S.pre[tx.k] >> 20) + tx.l;
-                const int pw8 = p ? cols * 8 >> SSH : cols * 8, ph8 = p ? rows * 8 >> SSV : rows * 8;
-                const PlIntra pi = pl_intra_job(p, txs, mode, e0, tx.g.bx + tx.x * 4, tx.g.by + tx.y * 4, tx.x, tx.g.pw4,
-                                                p ? tx0l >> SSH : tx0l, pw8, ph8, ux0, uy0);
-                if (j < JCAP) {
-                    if (ja) ja[j] = pi.a | (pi.trx ? JA_TRX : 0u);
-                    else D.jobw[(size_t) slot * JCAP + (uint32_t) j] = pi.a | (pi.trx ? JA_TRX : 0u);
-                }
-            }
+    int nj = 0;
+    for (int g0 = 0; g0 < T; g0 += 64 * NCH) {            // groups of NCH chunks
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+        if (g0 || c) {
+            x[c].w = x[c].m = 0;
+            if (g0 + c * 64 + lane < T) x[c] = rec[g0 + c * 64 + lane];
         }
-        // ranks within each key, in decode order: one ballot per distinct key of the chunk
-        uint64_t pend = __ballot(key >= 0);
-        uint32_t pos = 0, lim = 0;
-        while (pend) {
-            const int l0 = __builtin_ctzll(pend);
-            const int kk = rdl(key, l0);
-            const uint64_t m = __ballot(key == kk);
-            const uint32_t base = rdl(rb, kk), end = rdl(rl, kk);
-            if (key == kk) { pos = base + mbcnt(m); lim = end; }
-            if (lane == kk) rb += (uint32_t) __popcll(m);
-            pend &= ~m;
+    PPT(3);
+    // pass 1: coefficient offsets, nonzero boxes, the intra job words
+    uint32_t coef[NCH], nzv[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        if (g0 + c * 64 >= T) break;
+        const uint32_t w = x[c].w, m = x[c].m;
+        const uint32_t e0 = TXR_EOB(m), key = TXR_KEY(m);
+        const uint32_t incl = wscan_incl(e0, lane);
+        uint32_t cf = coef_sb + carry + incl - e0, e = e0;
+        carry += rdl(incl, 63);
+        if (TXR_EMIT(m) && cf + e > D.total_coefs) { st |= PLS_COEF; e = 0; cf = 0; x[c].m = m & ~2047u; }
+        coef[c] = cf;
+        nzv[c] = TXR_EMIT(m) ? nz16[key * 1025 + e] : 0u;
+        const uint64_t mj = __ballot((w & TXR_JOB) != 0);
+        if (w & TXR_JOB) {
+            // check_intra_mode resolved (vp9recon.c:37-221) from the record's inputs
+            const int p = w & 3, txs = (w >> 2) & 3, ux0 = (w >> 12) & 15, uy0 = (w >> 16) & 15;
+            const int sh = p ? SSH : 0, sv = p ? SSV : 0;
+            const int pw8 = p ? cols * 8 >> SSH : cols * 8, ph8 = p ? rows * 8 >> SSV : rows * 8;
+            const PlIntra pi = pl_intra_job(p, txs, (int) ((w >> 8) & 15), (int) e0, G.sbx * (64 >> sh) + ux0 * 4,
+                                            G.sby * (64 >> sv) + uy0 * 4, 0, (w & TXR_RIGHT) ? 2 : 1, p ? tx0l >> SSH : tx0l,
+                                            pw8, ph8, ux0, uy0);
+            ja[nj + (int) mbcnt(mj)] = pi.a | (pi.trx ? JA_TRX : 0u);      // at most T <= JCAP
         }
-        if (key >= 0 && pos >= lim) { st |= PLS_EOB; key = -1; }   // more jobs than k_psb counted
-        if (key >= 0 && inb(D, pos, D.cap_rjobs, 64u)) D.rjobs[pos] = r;
+        nj += __popcll(mj);
+    }
+    PPT(4);
+    // pass 2: the residual jobs
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        if (g0 + c * 64 >= T) break;
+        const uint32_t w = x[c].w, m = x[c].m, key = TXR_KEY(m);
+        const uint32_t base = (uint32_t) __shfl((int) rb, (int) key);
+        if (TXR_EMIT(m)) {
+            const int p = w & 3, txs = (w >> 2) & 3, ux0 = (w >> 12) & 15, uy0 = (w >> 16) & 15;
+            const int sh = p ? SSH : 0, sv = p ? SSV : 0;
+            const bool intra = (w & TXR_JOB) != 0;
+            uint32_t dst;
+            if (intra) dst = rbase + pl_resid_unit(p, ux0, uy0, SSH, SSV);
+            else {
+                dst = (uint32_t) ((size_t) (G.sby * (64 >> sv) + uy0 * 4) * F.pitch[p ? 1 : 0] + G.sbx * (64 >> sh) + ux0 * 4);
+                ibytes += (unsigned long long) (2 * (16 << (2 * txs)) * F.bypp);
+            }
+            // RJob: coef, dst, eob | frame << 16, ptx | nzc << 8 | nzr << 16 (pad 0)
+            const uint32_t ptx = (uint32_t) p | (key >> 2) << 2 | (intra ? 0u : 1u) << 5 | (key & 3) << 6;
+            const uint32_t pos = base + TXR_RANK(m);
+            if (pos < D.cap_rjobs)
+                *(uint4 *) &D.rjobs[pos] = make_uint4(coef[c], dst, TXR_EOB(m) | (uint32_t) (F.frame & 0xffff) << 16,
+                                                      ptx | nzv[c] << 8);
+            else bf |= 64u;
+        }
+    }
+    PPT(5);
     }
     for (int d = 32; d; d >>= 1) ibytes += __shfl_xor(ibytes, d);
-    if (lane == 0) {
-        if (!ja) D.sb_nj[slot] = (uint32_t) (G.mine ? NJ : 0);
-        if (ibytes && inb(D, (uint32_t) F.frame, D.nframes, 2048u)) atomicAdd(&D.fbytes[2 * F.frame], ibytes);
+    if (lane == 0 && ibytes) {
+        if ((uint32_t) F.frame < D.nframes) atomicAdd(&D.fbytes[2 * F.frame], ibytes);
+        else bf |= 2048u;
     }
+    bf = wor(bf);
+    if (lane == 0 && bf) { atomicOr(&D.status[1], bf); atomicOr(&D.status[0], PLS_BOUNDS); }
     st = wor(st);
     if (lane == 0 && st) plan_fail(D, F, st);
-    PPT(2);
-    return G.mine ? NJ : 0;
+    return pl_min(nj, NJ);
 }
-template <int SSH, int SSV>
-__global__ __launch_bounds__(64) void k_pjob(PlanDev D)
-{
-    __shared__ PJobLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> S;
-    pjob_sb<SSH, SSV>(D, S, nullptr);
-}
+static_assert(sizeof(RJob) == 16 && offsetof(RJob, eob) == 8 && offsetof(RJob, frame) == 10 && offsetof(RJob, ptx) == 12 &&
+              offsetof(RJob, nzc) == 13 && offsetof(RJob, nzr) == 14, "pjob_sb stores an RJob as one uint4");
 
 // One wave per SB: producers of every intra job, heights, priority order, list-scheduled
 // passes (the host's merge_mixed), the PJob / pass records, the SB's records, its level
-// dependencies and intra step. Jobs come from k_pjob (D.jobw); the unit map is rebuilt.
+// dependencies and intra step. The job words are in S.ja already (pjob_sb), nj of them.
 // (Two SBs per wave with the second's job words loaded under the first's scheduling cut the
 // first load's share of a wave's cycles from 31 to 20 %, but not the kernel: 2,880 -> 2,926 us
 // per C3 batch. The waves' time goes to dependent LDS chains at 6 waves per SIMD, LDS-bound.)
-// nj >= 0 (k_pjplan): the SB's job words are in S.ja already, nj of them
 template <int SSH, int SSV>
-DEV void plan_sb(const PlanDev &D, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> &S, int nj)
+DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> &S, int nj)
 {
     constexpr int CW = 16 >> SSH, CH = 16 >> SSV, JCAP = 256 + 2 * CW * CH, NCH = JCAP / 64;
-    const PlanFrame &F = D.frames[blockIdx.y];
     const int s = blockIdx.x, lane = threadIdx.x;
-    if (s >= F.sb_cols * F.sb_rows) return;
     unsigned long long pt0 = D.prof ? clock64() : 0;
     const SbGeo G = sb_geo(F, s);
     const uint32_t slot = G.slot;
     const uint32_t rbase = slot * D.rcap;
     uint32_t st = 0;
-    const int NJ = pl_min(nj >= 0 ? nj : (int) D.sb_nj[slot], JCAP);
+    const int NJ = pl_min(nj, JCAP);
     for (int i = lane; i < 3 * 256 / 8; i += 64) ((uint4 *) &S.u.jmap[0][0])[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
-    if (nj < 0)
-        for (int j = lane; j < NJ; j += 64) S.ja[j] = D.jobw[(size_t) slot * JCAP + (uint32_t) j];
     wsync();
-    PPT(8);
+    PPT(6);
     // the unit map: each job's 4x4 units hold JM_ENT(job, units to the job's right edge, units
     // to its bottom edge), so the producer walk below steps past a producer's extent from the
     // entry alone (one LDS read per producer instead of the entry and the job's word)
@@ -647,7 +623,7 @@ DEV void plan_sb(const PlanDev &D, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> 
         }
     }
     wsync();
-    PPT(9);
+    PPT(7);
 
     // ---- producers of every intra job (the pixels its substituted mode reads)
     // The units job j reads are pl_local_reads' runs: the top row (uy0 - 1, from ux0 - 1 with
@@ -712,7 +688,7 @@ DEV void plan_sb(const PlanDev &D, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> 
         for (int j = lane; j < NJ; j += 64) S.u.b.h.hgt[j] = 1;
     }
     wsync();
-    PPT(3);
+    PPT(8);
     // ---- heights (longest path to a sink). Producers precede their consumers (d < j), so
     // the chunks of 64 jobs are finished last to first: a chunk's consumers in later chunks
     // are final, and the chunk relaxes until none of its own jobs rises (at most one round
@@ -734,7 +710,7 @@ DEV void plan_sb(const PlanDev &D, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> 
             if (!__any(ch)) break;
         }
     }
-    PPT(4);
+    PPT(9);
     // ---- priority order: height descending, then decode order. The heights go to registers
     // first: the order and the pass words overlay them (NCH = JCAP / 64 chunks)
     int hreg[NCH];
@@ -776,7 +752,7 @@ DEV void plan_sb(const PlanDev &D, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> 
     wsync();
     for (int j = lane; j < NJ; j += 64) S.u.b.h.os.sch[j] = 0xffff;
     wsync();
-    PPT(5);
+    PPT(10);
     // ---- list scheduling (merge_mixed): each pass takes, in priority order, every ready job
     // (all producers in earlier passes) that still fits in 64 lanes; lane groups by size
     uint32_t *gpass = D.passes + (size_t) slot * JCAP;
@@ -877,7 +853,7 @@ DEV void plan_sb(const PlanDev &D, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> 
         w.sb[0] = slot;
         D.wgs[slot] = w;
     }
-    PPT(6);
+    PPT(11);
 
     // ---- cross-SB reads of level-scheduled inter frames: left / top / top-left SBs whose
     // intra units this SB's jobs read (the host's umap levels)
@@ -897,7 +873,7 @@ DEV void plan_sb(const PlanDev &D, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> 
             });
         }
     dmask = wor(dmask);
-    PPT(7);
+    PPT(12);
 
 
     // ---- the SB's intra step (diagonal phases; level phases in k_plevel) and batch totals
@@ -915,38 +891,25 @@ DEV void plan_sb(const PlanDev &D, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> 
     }
     st = wor(st);
     if (lane == 0 && st) plan_fail(D, F, st);
-    PPT(10);
+    PPT(13);
 }
-template <int SSH, int SSV>
-__global__ __launch_bounds__(64) void k_plan(PlanDev D)
-{
-    __shared__ PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> S;
-    plan_sb<SSH, SSV>(D, S, -1);
-}
-// k_pjob and k_plan of one SB in one wave: the intra job words stay in LDS (no D.jobw round
-// trip through HBM, one wave start instead of two). k_pjob's LDS overlays k_plan's unit
-// map / schedule region, which k_plan writes only after the job words are in place, so the
-// fused wave keeps k_plan's 7.2 KB (4:2:0). VP9HIP_PLAN_DBG bit 3: the two kernels.
+// pjob_sb and plan_sb of one SB in one wave: the intra job words stay in LDS (no round trip
+// through HBM, one wave start instead of two); plan_sb's 7.2 KB (4:2:0) is all the LDS.
 template <int SSH, int SSV>
 __global__ __launch_bounds__(64) void k_pjplan(PlanDev D)
 {
-    constexpr int JCAP = 256 + 2 * (16 >> SSH) * (16 >> SSV);
-    typedef PlanLds<JCAP> PL;
-    __shared__ union alignas(16) {
-        PL pl;
-        struct { uint32_t ja[JCAP]; PJobLds<JCAP> pj; } pjx;   // pj over pl.u
-    } U;
-    static_assert(offsetof(PL, u) == sizeof(uint32_t) * JCAP, "k_pjob's LDS overlays k_plan's union, not its job words");
-    const int nj = pjob_sb<SSH, SSV>(D, U.pjx.pj, U.pl.ja);
-    if (nj < 0) return;
+    __shared__ PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> S;
+    const PlanFrame F = D.frames[blockIdx.y];     // by value, before any store: one batch of scalar loads
+    if ((int) blockIdx.x >= F.sb_cols * F.sb_rows) return;
+    const int nj = pjob_sb<SSH, SSV>(D, F, S.ja);
     wsync();
-    plan_sb<SSH, SSV>(D, U.pl, nj);
+    plan_sb<SSH, SSV>(D, F, S, nj);
 }
 
 // ------------------------------------------------------------------ k_plmc
 // MC units of the SB's inter blocks in decode order (vp9_mc_template.c:30-464), one wave per
 // SB of the batch's inter frames. A kernel of its own: the unit emission is large code that
-// keyframe batches never run, and it needs none of k_plan's LDS.
+// keyframe batches never run, and it needs none of k_pjplan's LDS.
 template <int SSH, int SSV>
 __global__ __launch_bounds__(64) void k_plmc(PlanDev D)
 {
@@ -1122,8 +1085,8 @@ __global__ __launch_bounds__(256) void k_plists(PlanDev D)
 
 // ------------------------------------------------------------------ k_psort
 // Static step lists (keyframe batches): one workgroup per intra step, its SBs reordered by
-// the length of their pass chains, longest first (sb_kpos: the SB's passes, from k_plan; a
-// per-pass row count was measured 2 % slower in k_plan's scheduling loop for the same order).
+// the length of their pass chains, longest first (sb_kpos: the SB's passes, from k_pjplan; a
+// per-pass row count was measured 2 % slower in its scheduling loop for the same order).
 // A k_plf launch lasts until its slowest chain ends; chains dispatched in descending length
 // start the long ones first, and the short ones fill the CUs behind them (longest-processing-
 // time order). Counting sort over 256 bins (passes, longest first; more than 255 share the
@@ -1175,7 +1138,7 @@ __global__ __launch_bounds__(1024) void k_psort(PlanDev D, const uint32_t *ko)
 // frames the planner rejected (fbad != 0: the frame's packet is inconsistent) are
 // neutralised here: no intra passes (WGRec), and their residual jobs write nothing but
 // zeros into the spare scratch slot (slot nslots) from no coefficients. The other frames'
-// records address only their own data (k_pjob), so they reconstruct as if alone; a status
+// records address only their own data (k_pjplan), so they reconstruct as if alone; a status
 // that names no frame (PLS_BOUNDS, PLS_TOTAL) neutralises the whole batch (every WGRec, the summary's
 // residual ranges). The status is re-copied into the summary (k_plists' bound checks come
 // after k_pkeys), which the host reads when it next waits for the batch (vp9hip_sync /
@@ -1207,17 +1170,13 @@ __global__ __launch_bounds__(256) void k_pguard(PlanDev D, uint32_t *summary, in
     if (slot < D.nslots) { D.wgs[slot].njobs = 0; D.wgs[slot].npass = 0; }
 }
 
-// stage 0: k_psb; 1: k_pjob, k_plan, then k_pllf (filtered frames) and k_plmc (inter frames)
+// stage 0: k_psb; 1: k_pjplan, then k_pllf (filtered frames) and k_plmc (inter frames)
 template <int SSH, int SSV>
 void launch_sb_kernels(hipStream_t st, const PlanDev &D, int max_sb, int nframes, int stage, int flags)
 {
     const dim3 g(max_sb, nframes);
     if (stage == 0) { hipLaunchKernelGGL((k_psb<SSH, SSV>), g, dim3(64), 0, st, D); return; }
-    if (D.dbg & 8) {                                             // VP9HIP_PLAN_DBG bit 3: unfused
-        hipLaunchKernelGGL((k_pjob<SSH, SSV>), g, dim3(64), 0, st, D);
-        hipLaunchKernelGGL((k_plan<SSH, SSV>), g, dim3(64), 0, st, D);
-    } else
-        hipLaunchKernelGGL((k_pjplan<SSH, SSV>), g, dim3(64), 0, st, D);
+    hipLaunchKernelGGL((k_pjplan<SSH, SSV>), g, dim3(64), 0, st, D);
     if (flags & 1) hipLaunchKernelGGL((k_pllf<SSH, SSV>), g, dim3(64), 0, st, D);
     if (flags & 2) hipLaunchKernelGGL((k_plmc<SSH, SSV>), g, dim3(64), 0, st, D);
 }

@@ -71,7 +71,7 @@ int vp9hip_launch_plf(int fmt, hipStream_t st, const PlfLaunch *pl, const uint32
 
 namespace {
 
-// K_PLAN: the device planner (k_pblk, scans, k_psb, k_plan, k_plevel, k_pkeys, k_plists) of a run
+// K_PLAN: the device planner (k_pblk, scans, k_psb, k_pjplan, k_plevel, k_pkeys, k_plists) of a run
 enum { K_MC, K_RESID, K_PRED, K_LF, K_PLF, K_LFR, K_PLAN, K_N };
 const char *const kname[K_N] = { "k_mc", "k_resid", "k_pred", "k_lf", "k_plf", "k_lfr", "k_plan" };
 
@@ -180,7 +180,7 @@ struct Staged {
     size_t o_pf = 0, o_blocks = 0, o_eobs = 0, o_slotpos = 0, o_segpre = 0, o_segsz = 0, o_segpre1 = 0, o_cntm = 0, o_cntm0 = 0, o_gidx = 0, o_bneob = 0,
            o_beob0 = 0, o_sbfirst = 0, o_sbncoef = 0, o_sbcoef0 = 0, o_cnt = 0, o_cnt0 = 0, o_ibits = 0,
            o_sbinfo = 0, o_sbkey = 0, o_sbkpos = 0, o_expko = 0, o_keycnt = 0, o_keyoff = 0, o_status = 0, o_fbytes = 0, o_fbad = 0,
-           o_summary = 0, o_scan = 0, zero_bytes = 0, o_jobw = 0, o_sbnj = 0;
+           o_summary = 0, o_scan = 0, zero_bytes = 0, o_txrec = 0, o_sbtn = 0;
     size_t scan_bytes = 0, summary_words = 0;
     uint32_t *summary_h = nullptr;                            // pinned readback of the summary
     size_t summary_cap = 0;
@@ -309,7 +309,7 @@ struct vp9hip_ctx {
     uint8_t *nz = nullptr;              // nonzero bounding boxes per (tcode, txtp, eob) (device, planner)
     bool host_plan = false;             // VP9HIP_HOST_PLAN=1: plan batches on host threads (A/B, tests)
     hipEvent_t pev[2] = {};             // device planner timing (timing runs)
-    unsigned long long *plan_prof = nullptr;   // VP9HIP_PLAN_PROF: k_plan phase cycles (device)
+    unsigned long long *plan_prof = nullptr;   // VP9HIP_PLAN_PROF: planner phase cycles (device)
     bool plan_timed = false;
     int dbg = 0;                        // VP9HIP_DEBUG: ablation switches for profiling only
     bool use_graph = true;              // VP9HIP_GRAPH=0 disables graph replay
@@ -323,7 +323,7 @@ struct vp9hip_ctx {
     bool edge = true;                   // VP9HIP_EDGE=0: no SB edge columns (4:2:0 tile loader)
     bool resid_multi = true;            // VP9HIP_RESID_MULTI=0: one residual launch per tx size
     bool stage_trace = false;           // VP9HIP_STAGE_TRACE=1: host time of staging / planning
-    bool plan_prof_on = false;          // VP9HIP_PLAN_PROF=1: k_plan phase cycles
+    bool plan_prof_on = false;          // VP9HIP_PLAN_PROF=1: planner phase cycles
     int plan_dbg = 0;                   // VP9HIP_PLAN_DBG: planner ablations (timing only)
     bool plan_only = false;             // VP9HIP_PLAN_ONLY=1: run the planner alone (diagnostics)
     bool plan_reuse = false;            // VP9HIP_PLAN_REUSE=1: a static-plan batch's reruns skip the planner
@@ -1457,8 +1457,8 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
     s.o_lfs = o; o = al(o + (size_t) NS * sizeof(LFRec));
     s.o_pjobs = o; o = al(o + (size_t) NS * s.jcap * sizeof(PJob));
     s.o_passes = o; o = al(o + (size_t) NS * s.jcap * 4);
-    s.o_jobw = o; o = al(o + (size_t) NS * s.jcap * 4);
-    s.o_sbnj = o; o = al(o + (size_t) NS * 4);
+    s.o_txrec = o; o = al(o + (size_t) NS * s.jcap * sizeof(TxRec));    // k_psb's tx records: only the ones
+    s.o_sbtn = o; o = al(o + (size_t) NS * 4);                          // written per SB are ever touched
     s.o_rjobs = o; o = al(o + (ne + 1) * sizeof(RJob));
     s.o_mcs = o; o = al(o + (nmc + 1) * sizeof(McUnit));
     s.cap_mcs = (uint32_t) (nmc + 1);
@@ -1572,7 +1572,7 @@ static int frame_verdicts(Staged &s, const uint32_t *sm, int good)
 // planner status (AVERROR_INVALIDDATA: the batch was neutralised by k_pguard; kept in
 // s.status and returned by every later check until the slot is restaged) and the
 // algorithmic byte totals. Consistency of the step lists with the staged launch list rests
-// on k_plan's PLS_SCHED check (with static lists k_plan does not count keys, so the summary's
+// on k_pjplan's PLS_SCHED check (with static lists it does not count keys, so the summary's
 // key offsets are only used to locate the byte totals).
 static void print_plan_prof(vp9hip_ctx *c, const Staged &s);
 static int finish_summary(vp9hip_ctx *c, Staged &s)
@@ -1613,17 +1613,26 @@ static int finish_summary(vp9hip_ctx *c, Staged &s)
     return 0;
 }
 
-// VP9HIP_PLAN_PROF=1: the planner's per-SB phase cycles of the last run (k_pjob phases 0-2,
-// k_plan 3-10), summed over the SBs, on stderr. The caller has waited for the planner.
+// VP9HIP_PLAN_PROF=1: the planner's per-SB phase cycles of the last run, summed over the SBs,
+// on stderr. k_psb: 0 blocks, prefix counts, entry starts, eob window; 1 the tx loop (eobs,
+// keys, ranks, unit map, records); 2 MC count and outputs. k_pjplan: 3 header words, key
+// bases, record loads; 4 coefficient offsets, nonzero boxes, intra job words; 5 residual job
+// stores; 6 unit-map clear; 7 unit map; 8 producers; 9 heights; 10 priority order; 11 list
+// scheduling; 12 cross-SB reads; 13 intra step. The shares are of wave cycles, and the two
+// kernels run at different occupancy: compare within a kernel. A wave's wait for
+// earlier loads is charged to the phase in which it waits. The caller has waited for the
+// planner.
 static void print_plan_prof(vp9hip_ctx *c, const Staged &s)
 {
     unsigned long long pc[16];
     if (hipMemcpy(pc, c->plan_prof, sizeof(pc), hipMemcpyDeviceToHost) != hipSuccess) return;
     double tot = 0;
-    for (int k = 0; k < 11; k++) tot += (double) pc[k];
+    const int NP = 14;
+    for (int k = 0; k < NP; k++) tot += (double) pc[k];
     fprintf(stderr, "vp9hip plan phases (%% of planner SB cycles, %.3g cycles/SB%s):", tot / std::max<uint32_t>(1, s.nslots),
             s.stat ? ", static plan" : "");
-    for (int k = 0; k < 11; k++) fprintf(stderr, " %d:%.1f", k, 100.0 * (double) pc[k] / std::max(1.0, tot));
+    for (int k = 0; k < NP; k++)
+        fprintf(stderr, "%s %d:%.1f", k == 0 ? " k_psb" : k == 3 ? " | k_pjplan" : "", k, 100.0 * (double) pc[k] / std::max(1.0, tot));
     fprintf(stderr, "\n");
 }
 
@@ -1681,8 +1690,8 @@ static int plan_dev(vp9hip_ctx *c)
     D.rjobs = (RJob *) (A + s.o_rjobs);
     D.mcs = (McUnit *) (A + s.o_mcs);
     D.dlists = (uint32_t *) (A + s.o_lists) + s.host_lists;
-    D.jobw = (uint32_t *) (A + s.o_jobw);
-    D.sb_nj = (uint32_t *) (A + s.o_sbnj);
+    D.txrec = (TxRec *) (A + s.o_txrec);
+    D.sb_tn = (uint32_t *) (A + s.o_sbtn);
     D.nz = c->nz;
     D.jcap = (uint32_t) s.jcap;
     D.rcap = (uint32_t) s.rcap;
