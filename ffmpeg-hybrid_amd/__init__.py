@@ -107,7 +107,8 @@ class FrameInfo(ctypes.Structure):
                 ("error_res", ctypes.c_int32), ("refresh_ctx", ctypes.c_int32), ("parallel", ctypes.c_int32),
                 ("ctx_id", ctypes.c_int32), ("allow_hp", ctypes.c_int32), ("interp", ctypes.c_int32),
                 ("comp_mode", ctypes.c_int32), ("tx_mode", ctypes.c_int32),
-                ("header_size", ctypes.c_uint32), ("compressed_header_size", ctypes.c_uint32)]
+                ("header_size", ctypes.c_uint32), ("compressed_header_size", ctypes.c_uint32),
+                ("colorspace", ctypes.c_int32), ("full_range", ctypes.c_int32)]
 
 
 class EncParams(ctypes.Structure):
@@ -128,7 +129,7 @@ _lib_handle = None
 # (frame_tensors) needs torch imported before this library is loaded.
 _torch_first = False
 
-ABI_VERSION = 2                # VP9HIP_ABI_VERSION of include/vp9hip.h these bindings mirror
+ABI_VERSION = 3                # VP9HIP_ABI_VERSION of include/vp9hip.h these bindings mirror
 PIPELINE_SLOTS = 3             # VP9HIP_PIPELINE_SLOTS: batch slots the decoder / adapter rotate
 # Exported symbols of include/vp9hip.h (checked by the CPU test suite).
 ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit_frame",
@@ -148,7 +149,9 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9h_ivf_write_frame_header", "vp9h_webm_probe", "vp9h_webm_read_header", "vp9h_webm_read_frame",
                "vp9hip_decoder_defaults", "vp9hip_decoder_open", "vp9hip_decoder_close", "vp9hip_decoder_context",
                "vp9hip_decoder_send_packet", "vp9hip_decoder_receive_frame", "vp9hip_decoder_release",
-               "vp9hip_decoder_flush"]
+               "vp9hip_decoder_flush",
+               "vp9h_stream_set_color", "vp9hip_out_layout", "vp9hip_out_coefs", "vp9hip_convert_frames",
+               "vp9hip_decoder_convert"]
 
 
 def lib():
@@ -162,7 +165,8 @@ def lib():
     _torch_first = "torch" in sys.modules
     L = ctypes.CDLL(LIB_PATH)
     # the struct mirrors below are the header's of this ABI version (vp9h_synth_params and
-    # vp9h_enc_params grew in version 2): a library built from another header is refused
+    # vp9h_enc_params grew in version 2, vp9h_frame_info and vp9hip_decoded_frame in 3): a
+    # library built from another header is refused
     if L.vp9hip_abi_version() != ABI_VERSION:
         raise Vp9HipUnavailable("libvp9hip.so ABI version %d, these bindings need %d: rebuild it (%s)"
                                 % (L.vp9hip_abi_version(), ABI_VERSION, LIB_PATH))
@@ -259,6 +263,15 @@ def lib():
     L.vp9hip_decoder_receive_frame.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo)]
     L.vp9hip_decoder_release.argtypes = [vp, ctypes.c_int]
     L.vp9hip_decoder_flush.argtypes = [vp]
+    L.vp9h_stream_set_color.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+    L.vp9hip_out_layout.argtypes = [ctypes.POINTER(OutDesc), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    L.vp9hip_out_layout.restype = ctypes.c_int64
+    L.vp9hip_out_coefs.argtypes = [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    L.vp9hip_convert_frames.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(OutDesc),
+                                        ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_decoder_convert.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
     _lib_handle = L
     return L
 
@@ -290,7 +303,18 @@ class DecoderParams(ctypes.Structure):
 class DecodedFrameInfo(ctypes.Structure):
     _fields_ = [("buf", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("bpp", ctypes.c_int32), ("ss_h", ctypes.c_int32), ("ss_v", ctypes.c_int32),
-                ("pts", ctypes.c_int64)]
+                ("pts", ctypes.c_int64), ("colorspace", ctypes.c_int32), ("full_range", ctypes.c_int32)]
+
+
+class OutDesc(ctypes.Structure):
+    """vp9hip_out_desc: the format and layout of converted frames."""
+    _fields_ = [("format", ctypes.c_int32), ("colorspace", ctypes.c_int32), ("full_range", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("pitch", ctypes.c_int64),
+                ("frame_stride", ctypes.c_int64)]
+
+
+# VP9HIP_OUT_*: the names Device.convert / Decoder.convert take
+OUT_FORMATS = {"semiplanar": 0, "rgb24": 1, "rgbp_u8": 2, "rgbp_f16": 3}
 
 
 def _check(fn, r):
@@ -399,6 +423,11 @@ class Stream:
         if threads != 1:
             self.set_threads(threads)
 
+    def set_color(self, colorspace, full_range):
+        """Encoding: the colour space code (0..5, 7 = RGB) and range bit the following intra
+        frames code (vp9h_stream_set_color; the default is 2 = BT.709, limited)."""
+        _check("vp9h_stream_set_color", lib().vp9h_stream_set_color(self._s, int(colorspace), int(bool(full_range))))
+
     def set_threads(self, n):
         """Tile-column threads of decode (vp9h_stream_set_threads)."""
         _check("vp9h_stream_set_threads", lib().vp9h_stream_set_threads(self._s, int(n)))
@@ -458,6 +487,24 @@ def superframe_join(frames):
     return b"".join(bytes(f) for f in frames) + idx
 
 
+def out_coefs(colorspace, full_range, bpp, out_bits):
+    """((CY, CRV, CGU, CGV, CBU), shift) of the integer colour matrix (vp9hip_out_coefs)."""
+    c, sh = (ctypes.c_int32 * 5)(), ctypes.c_int32()
+    _check("vp9hip_out_coefs", lib().vp9hip_out_coefs(int(colorspace), int(bool(full_range)), int(bpp), int(out_bits),
+                                                       c, ctypes.byref(sh)))
+    return tuple(c), sh.value
+
+
+def out_layout(fmt, width, height, bpp=8, ss_h=1, ss_v=1, pitch=0, frame_stride=0):
+    """(bytes per frame, pitch, plane offsets) of one converted frame (vp9hip_out_layout);
+    fmt is a key of OUT_FORMATS."""
+    d = OutDesc(OUT_FORMATS[fmt], 2, 0, int(width), int(height), int(pitch), int(frame_stride))
+    p, off = ctypes.c_int64(), (ctypes.c_int64 * 3)()
+    n = _check("vp9hip_out_layout", lib().vp9hip_out_layout(ctypes.byref(d), int(bpp), int(ss_h), int(ss_v),
+                                                             ctypes.byref(p), off))
+    return n, p.value, tuple(off)
+
+
 def alloc_planes(width, height, bpp, ss_h=1, ss_v=1, pad=64):
     """Host planes padded to 64 luma pixels (the layout the oracle expects)."""
     dt = np.uint8 if bpp == 8 else np.uint16
@@ -489,6 +536,25 @@ def device_info(device):
     bus, name = ctypes.create_string_buffer(64), ctypes.create_string_buffer(256)
     _check("vp9hip_device_info", lib().vp9hip_device_info(device, bus, 64, name, 256))
     return bus.value.decode(), name.value.decode()
+
+
+def _enqueue_for_torch(ctx_stream, stream, launch):
+    """Run launch(hipStream_t handle or None) so that it is ordered like work on torch's current
+    stream. An explicit `stream` handle, or a current stream of torch's own, is used as it is.
+    torch's default stream is the null stream, which the C ABI cannot name (NULL selects the
+    context's main stream, a non-blocking one): then the launch goes to the context's main
+    stream `ctx_stream`, which first waits for torch's stream and is waited for by it afterwards."""
+    import torch
+    if stream is not None:
+        return launch(stream)
+    cur = torch.cuda.current_stream()
+    if cur.cuda_stream:
+        return launch(cur.cuda_stream)
+    ext = torch.cuda.ExternalStream(ctx_stream)
+    ext.wait_stream(cur)
+    r = launch(None)
+    cur.wait_stream(ext)
+    return r
 
 
 class Device:
@@ -657,6 +723,70 @@ class Device:
             out.append(torch.as_tensor(_View(), device=device or "cuda"))
         return out
 
+    @staticmethod
+    def _convert_out(n, fmt, w, h, bpp, ss_h, ss_v, out, pitch, frame_stride):
+        """The destination of a conversion: (storage tensor, result, pitch, frame stride). The
+        storage is a flat uint8 tensor (allocated, or `out` itself: a contiguous uint8 cuda
+        tensor of at least the layout's bytes); the result is the strided view(s) of it that
+        convert() returns."""
+        import torch
+        nbytes, pitch, off = out_layout(fmt, w, h, bpp, ss_h, ss_v, pitch, frame_stride)
+        stride = frame_stride or nbytes
+        total = (n - 1) * stride + nbytes
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device="cuda")
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+                  and out.numel() >= total):
+            raise ValueError("convert: out must be a contiguous uint8 cuda tensor of at least %d bytes" % total)
+        flat = out.view(-1)
+        if fmt == "rgb24":
+            return flat, flat.as_strided((n, h, w, 3), (stride, pitch, 3, 1)), pitch, stride
+        if fmt == "rgbp_u8":
+            return flat, flat.as_strided((n, 3, h, w), (stride, off[1], pitch, 1)), pitch, stride
+        if fmt == "rgbp_f16":
+            if flat.data_ptr() & 1 or stride & 1:
+                raise ValueError("convert: half output needs an even address and frame stride")
+            half = flat[:total // 2 * 2].view(torch.float16)
+            return flat, half.as_strided((n, 3, h, w), (stride // 2, off[1] // 2, pitch // 2, 1)), pitch, stride
+        cw, ch = (w + ss_h) >> ss_h, (h + ss_v) >> ss_v
+        if bpp == 8:
+            return flat, (flat.as_strided((n, h, w), (stride, pitch, 1)),
+                          flat[off[1]:].as_strided((n, ch, cw, 2), (stride, pitch, 2, 1))), pitch, stride
+        if flat.data_ptr() & 1 or stride & 1:
+            raise ValueError("convert: 16-bit output needs an even address and frame stride")
+        wide = flat[:total // 2 * 2].view(torch.int16)
+        return flat, (wide.as_strided((n, h, w), (stride // 2, pitch // 2, 1)),
+                      wide[off[1] // 2:].as_strided((n, ch, cw, 2), (stride // 2, pitch // 2, 2, 1))), pitch, stride
+
+    def convert(self, bufs, fmt, colorspace=2, full_range=False, size=None, out=None, stream=None,
+                pitch=0, frame_stride=0):
+        """Convert device buffers `bufs` (any order) to `fmt` on the GPU (vp9hip_convert_frames):
+        "rgb24" -> (N,H,W,3) uint8, "rgbp_u8" -> (N,3,H,W) uint8, "rgbp_f16" -> (N,3,H,W)
+        float16 in [0,1], "semiplanar" -> (y, uv) views of one allocation, (N,H,W) and
+        (N,CH,CW,2), uint8 (NV12 style) or, above 8 bits, int16 storage of the MSB-aligned
+        samples (P010 style) as frame_tensors does. colorspace is the VP9 code (1..5, 7 = RGB
+        planes), size the visible (width, height) (default: the configured size). `out` is a
+        contiguous uint8 cuda tensor to write into (else one is allocated); pitch / frame_stride
+        as in vp9hip_out_desc (0 = tight). Runs in the order of torch's current stream (or on
+        `stream`, a hipStream_t handle; see _enqueue_for_torch) and does not wait: order it after the frames' producer (sync(), or
+        vp9hip_slot_stream_wait), as for frame_tensors. Needs torch imported before the library
+        was loaded (see _torch_first)."""
+        if not _torch_first:
+            raise Vp9HipUnavailable("convert: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        import torch
+        bufs = [int(b) for b in bufs]
+        w, h = size if size is not None else (self.w, self.h)
+        d = OutDesc(OUT_FORMATS[fmt], int(colorspace), int(bool(full_range)), int(w), int(h), int(pitch), int(frame_stride))
+        if not bufs:
+            raise Vp9HipError("vp9hip_convert_frames", EINVAL)
+        flat, res, _, _ = self._convert_out(len(bufs), fmt, w, h, self.bpp, self.ss_h, self.ss_v, out, pitch, frame_stride)
+        arr = (ctypes.c_int * len(bufs))(*bufs)
+        _check("vp9hip_convert_frames", _enqueue_for_torch(
+            self.frame_device(0)[3], stream,
+            lambda st: lib().vp9hip_convert_frames(self._c, arr, len(bufs), ctypes.byref(d), flat.data_ptr(), st)))
+        return res
+
     def upload(self, buf, planes):
         planes = [np.ascontiguousarray(p) for p in planes]
         ptrs, ls = self._plane_args(planes)
@@ -771,6 +901,33 @@ class Decoder:
 
     def context(self):
         return ctypes.c_void_p(lib().vp9hip_decoder_context(self._d))
+
+    def convert(self, infos, fmt, out=None):
+        """Convert the frames of receive_frame(download=False) (their DecodedFrameInfos, all of
+        one size, colour space and range) to `fmt` as Device.convert does, with the frames' own
+        colour description (vp9hip_decoder_convert), on torch's current stream; waits for it
+        and releases the buffers. Returns the tensor(s)."""
+        if not _torch_first:
+            raise Vp9HipUnavailable("convert: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        import torch
+        infos = list(infos)
+        if not infos:
+            raise Vp9HipError("vp9hip_decoder_convert", EINVAL)
+        arr = (DecodedFrameInfo * len(infos))(*infos)
+        f = infos[0]
+        flat, res, pitch, stride = Device._convert_out(len(infos), fmt, f.width, f.height, f.bpp, f.ss_h, f.ss_v,
+                                                       out, 0, 0)
+        main = ctypes.c_void_p()
+        _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
+                                                                (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
+        _check("vp9hip_decoder_convert", _enqueue_for_torch(
+            main.value, None,
+            lambda st: lib().vp9hip_decoder_convert(self._d, arr, len(infos), OUT_FORMATS[fmt], flat.data_ptr(), 0, 0, st)))
+        torch.cuda.current_stream().synchronize()
+        for i in infos:
+            self.release(i.buf)
+        return res
 
     def flush(self):
         _check("vp9hip_decoder_flush", lib().vp9hip_decoder_flush(self._d))

@@ -420,6 +420,7 @@ typedef struct SegFeat { int q_en, q, lf_en, lf, ref_en, ref, skip; } SegFeat;
 /* the frame header (s->s.h), persistent across frames like the reference's */
 typedef struct Hdr {
     int profile, keyframe, intraonly, invisible, errorres, w, h, bpp, ss_h, ss_v;
+    int colorspace, fullrange;           /* the 3-bit colour space code and the range bit (vp9.c:457-517) */
     int resetctx, refreshmask, refidx[3], signbias[3];
     int hp, filtermode, allowcomp, fixcompref, varcompref[2];
     int refreshctx, parallel, ctxid, ctxid_raw;
@@ -437,6 +438,7 @@ typedef struct Hdr {
 
 struct vp9h_stream {
     int tile_threads;                    /* decode: tile columns walked concurrently (1: serial) */
+    int enc_colorspace, enc_fullrange;   /* encode: what the colour config codes (vp9h_stream_set_color) */
     Hdr h;
     SavedCtx ctx[4];
     struct { int valid, w, h, bpp, ss_h, ss_v; } slot[8];
@@ -459,6 +461,7 @@ int vp9h_stream_open(vp9h_stream **out)
     for (int i = 0; i < 4; i++) ctx_reset(&s->ctx[i]);
     s->h.sharpness = -1;
     s->tile_threads = 1;
+    s->enc_colorspace = 2;               /* BT.709, limited range */
     *out = s;
     return 0;
 }
@@ -1633,19 +1636,22 @@ static void set_qmul_lf(Walk *w)
 
 /* color config (read_colorspace_details, vp9.c:457-517). Profiles 1 / 3 code the
  * subsampling (4:2:2 / 4:4:0 / 4:4:4; 8-bit 4:2:0 is refused there, 10/12-bit 4:2:0 in
- * profile 3 is accepted, as in the reference) or RGB (4:4:4). The encoder writes BT.709
- * YUV with the packet's subsampling. Returns 0 or -1 (invalid). */
+ * profile 3 is accepted, as in the reference) or RGB (4:4:4, always full range). The
+ * encoder writes the stream's colour space and range (vp9h_stream_set_color; BT.709 limited
+ * by default) with the packet's subsampling. Returns 0 or -1 (invalid). */
 static int walk_color(Bits *b, Hdr *h, int prof)
 {
     int bits = 0;
     if (prof >= 2) bits = 1 + bits_rw(b, 1, h->bpp == 12);
     h->bpp = 8 + 2 * bits;
-    if (bits_rw(b, 3, 2) == 7) {                                  /* RGB: profiles 1 / 3 only */
+    h->colorspace = bits_rw(b, 3, h->colorspace);
+    if (h->colorspace == 7) {                                     /* RGB: profiles 1 / 3 only */
         if (!(prof & 1)) return -1;
+        h->fullrange = 1;
         h->ss_h = h->ss_v = 0;
         return bits_rw(b, 1, 0) ? -1 : 0;                         /* reserved bit */
     }
-    bits_rw(b, 1, 0);                                             /* color range */
+    h->fullrange = bits_rw(b, 1, h->fullrange);
     if (prof & 1) {
         h->ss_h = bits_rw(b, 1, h->ss_h);
         h->ss_v = bits_rw(b, 1, h->ss_v);
@@ -1699,6 +1705,8 @@ static long walk_uncompressed(Walk *w, Bits *b, int *existing)
             } else {
                 h->ss_h = h->ss_v = 1;
                 h->bpp = 8;
+                h->colorspace = 1;                                 /* BT.470BG, limited, as the reference sets here */
+                h->fullrange = 0;
             }
             h->refreshmask = bits_rw(b, 8, h->refreshmask);
             fw = bits_rw(b, 16, h->w - 1) + 1;
@@ -2231,6 +2239,14 @@ static int walk_tiles_mt(Walk *w, BC *coders, int nthreads)
     return r;
 }
 
+int vp9h_stream_set_color(vp9h_stream *s, int colorspace, int full_range)
+{
+    if (!s || colorspace < 0 || colorspace > 7 || colorspace == 6) return VP9HIP_EINVAL;
+    s->enc_colorspace = colorspace;
+    s->enc_fullrange = colorspace == 7 || full_range;
+    return 0;
+}
+
 int vp9h_stream_set_threads(vp9h_stream *s, int n)
 {
     if (!s || n < 1 || n > 64) return VP9HIP_EINVAL;
@@ -2337,6 +2353,8 @@ static void fill_info(const Walk *w, vp9h_frame_info *info)
     info->interp = h->filtermode;
     info->comp_mode = h->comppred;
     info->tx_mode = h->txmode;
+    info->colorspace = h->colorspace;
+    info->full_range = h->fullrange;
 }
 
 static void fill_packet(Walk *w, vp9h_frame *out)
@@ -2417,6 +2435,8 @@ static int decode_headers(vp9h_stream *st, const uint8_t *data, size_t size, vp9
             info->show_existing_frame = 1;
             info->show_slot = existing;
             info->show_frame = 1;
+            info->colorspace = st->h.colorspace;                        /* the stream's, as avctx keeps them */
+            info->full_range = st->h.fullrange;
         }
         free(w);
         return r;
@@ -2603,6 +2623,7 @@ int vp9h_stream_encode(vp9h_stream *st, const vp9h_frame *pkt, const vp9h_enc_pa
     }
     if (!pkt || ep->base_q_idx < 0 || ep->base_q_idx > 255) return VP9HIP_EINVAL;
     if (pkt->ss_h > 1 || pkt->ss_v > 1 || (pkt->bpp != 8 && pkt->bpp != 10 && pkt->bpp != 12)) return VP9HIP_ENOSYS;
+    if (st->enc_colorspace == 7 && (pkt->ss_h || pkt->ss_v)) return VP9HIP_EINVAL;   /* RGB is 4:4:4 */
     const int inter = !pkt->keyframe && !pkt->intraonly;
     const int retain = st->segref && (!st->h.seg_enabled || !st->h.seg_update_map);
     const int last_keyframe = h->keyframe, last_invisible = h->invisible;
@@ -2614,6 +2635,7 @@ int vp9h_stream_encode(vp9h_stream *st, const vp9h_frame *pkt, const vp9h_enc_pa
     if (h->intraonly) h->invisible = 1;                       /* intra_only is coded in hidden frames only */
     h->errorres = ep->error_res;
     h->w = pkt->width; h->h = pkt->height; h->bpp = pkt->bpp; h->ss_h = pkt->ss_h; h->ss_v = pkt->ss_v;
+    h->colorspace = st->enc_colorspace; h->fullrange = st->enc_fullrange;
     h->refreshctx = ep->refresh_ctx; h->parallel = ep->parallel;
     h->ctxid_raw = ep->ctx_id & 3;
     h->resetctx = ep->reset_ctx & 3;
@@ -2807,12 +2829,18 @@ int vp9h_frame_peek(const uint8_t *data, size_t size, vp9h_frame_info *info)
     int type = key ? 0 : 1;
     if (key) {
         info->refresh_mask = 0xff;
+        Bits c = b;                                                     /* the colour config, if it is all there */
+        if (bits_rw(&c, 24, 0) == 0x498342 && walk_color(&c, &h, prof) == 0 && !c.err) {
+            info->colorspace = h.colorspace;
+            info->full_range = h.fullrange;
+        }
     } else {
         const int intraonly = info->show_frame ? 0 : bits_rw(&b, 1, 0);
         if (!info->error_res) bits_rw(&b, 2, 0);                        /* reset_frame_context */
         if (intraonly) {
             if (bits_rw(&b, 24, 0) != 0x498342) return VP9HIP_EINVALIDDATA;
             if (prof >= 1 && walk_color(&b, &h, prof) < 0) return VP9HIP_EINVALIDDATA;
+            if (prof >= 1) { info->colorspace = h.colorspace; info->full_range = h.fullrange; }
             info->refresh_mask = bits_rw(&b, 8, 0);
             type = 3;
         } else {

@@ -1,0 +1,69 @@
+/*
+ * Output conversion, host side: the layout of a converted frame and the integer colour
+ * matrix (include/vp9hip.h, DESIGN.md "Output conversion"). No device code: the kernel
+ * (vp9hip_convert.hip) takes what these two compute as arguments.
+ */
+#include <math.h>
+#include <string.h>
+
+#include "../../../include/vp9hip.h"
+
+int64_t vp9hip_out_layout(const vp9hip_out_desc *d, int bpp, int ss_h, int ss_v, int64_t *pitch,
+                          int64_t plane_offset[3])
+{
+    if (!d || d->width <= 0 || d->height <= 0 || d->pitch < 0 || d->frame_stride < 0) return VP9HIP_EINVAL;
+    if ((bpp != 8 && bpp != 10 && bpp != 12) || ss_h < 0 || ss_h > 1 || ss_v < 0 || ss_v > 1) return VP9HIP_EINVAL;
+    const int64_t w = d->width, h = d->height;
+    const int64_t cw = (w + ss_h) >> ss_h, ch = (h + ss_v) >> ss_v;
+    const int64_t bs = bpp > 8 ? 2 : 1;
+    int64_t row, rows;
+    switch (d->format) {
+    case VP9HIP_OUT_SEMIPLANAR: row = (w > 2 * cw ? w : 2 * cw) * bs; rows = h + ch; break;
+    case VP9HIP_OUT_RGB24:      row = 3 * w; rows = h; break;
+    case VP9HIP_OUT_RGBP_U8:    row = w; rows = 3 * h; break;
+    case VP9HIP_OUT_RGBP_F16:   row = 2 * w; rows = 3 * h; break;
+    default: return VP9HIP_EINVAL;
+    }
+    int64_t p = d->pitch ? d->pitch : row;
+    if (p < row || (p != row && (p & 15))) return VP9HIP_EINVAL;
+    const int64_t bytes = p * rows;
+    if (d->frame_stride && d->frame_stride < bytes) return VP9HIP_EINVAL;
+    if (pitch) *pitch = p;
+    if (plane_offset) {
+        if (d->format == VP9HIP_OUT_SEMIPLANAR) {
+            plane_offset[0] = 0; plane_offset[1] = p * h; plane_offset[2] = p * h + bs;
+        } else if (d->format == VP9HIP_OUT_RGB24) {
+            plane_offset[0] = 0; plane_offset[1] = 1; plane_offset[2] = 2;
+        } else {
+            plane_offset[0] = 0; plane_offset[1] = p * h; plane_offset[2] = 2 * p * h;
+        }
+    }
+    return bytes;
+}
+
+int vp9hip_out_coefs(int colorspace, int full_range, int bpp, int out_bits, int32_t c[5], int32_t *shift)
+{
+    if (!c || !shift || (bpp != 8 && bpp != 10 && bpp != 12) || (out_bits != 8 && out_bits != bpp)) return VP9HIP_EINVAL;
+    double kr, kb;
+    switch (colorspace) {
+    case 1: case 3: kr = .299;  kb = .114;  break;   /* BT.470BG / SMPTE-170M (BT.601) */
+    case 2:         kr = .2126; kb = .0722; break;   /* BT.709     */
+    case 4:         kr = .212;  kb = .087;  break;   /* SMPTE-240M */
+    case 5:         kr = .2627; kb = .0593; break;   /* BT.2020 NCL */
+    case 7:                                          /* RGB planes: no matrix */
+        memset(c, 0, 5 * sizeof(c[0]));
+        *shift = bpp - out_bits;
+        return 0;
+    default: return VP9HIP_EINVAL;
+    }
+    const int s = 14 + bpp - out_bits;
+    const double m = (double) ((1 << out_bits) - 1), up = (double) (1 << (bpp - 8));
+    const double sy = full_range ? m / (double) ((1 << bpp) - 1) : m / (219. * up);
+    const double sc = full_range ? m / (double) ((1 << bpp) - 1) : m / (224. * up);
+    const double kg = 1. - kr - kb, one = (double) (1 << s);
+    const double x[5] = { sy, 2. * (1. - kr) * sc, 2. * kb * (1. - kb) / kg * sc, 2. * kr * (1. - kr) / kg * sc,
+                          2. * (1. - kb) * sc };
+    for (int i = 0; i < 5; i++) c[i] = (int32_t) floor(x[i] * one + .5);
+    *shift = s;
+    return 0;
+}

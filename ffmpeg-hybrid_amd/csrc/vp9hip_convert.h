@@ -1,0 +1,31 @@
+// Output conversion (vp9hip_convert.hip): what the runtime hands the launcher.
+#ifndef VP9HIP_CONVERT_H
+#define VP9HIP_CONVERT_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define CVT_MAX_FRAMES 32              // frames per launch (blockIdx.z): their buffers are kernel arguments
+
+struct CvtArgs {
+    const uint8_t *src[CVT_MAX_FRAMES];  // the frames' device buffers
+    uint8_t *dst;                      // frame 0 of this launch
+    int64_t frame_stride, pitch;       // destination, bytes
+    int64_t plane;                     // destination bytes from one plane to the next (planar RGB: G, B; semi-planar: UV)
+    int64_t src_off[3];                // source planes inside a buffer, bytes
+    int32_t src_pitch[2];              // luma / chroma source pitch, bytes
+    int32_t w, h, cw, ch;              // visible luma / chroma size
+    int32_t c[5];                      // CY, CRV, CGU, CGV, CBU (vp9hip_out_coefs)
+    int32_t shift, rnd;                // >> shift after + rnd (matrix: 2^(shift-1); RGB source: its depth reduction)
+    int32_t yoff, coff;                // luma black level, chroma mid level
+    int32_t maxv;                      // largest output code
+    int32_t rgb;                       // source planes are G, B, R: no matrix
+    int32_t msb;                       // semi-planar: samples << msb (16 - bpp above 8 bits)
+    float   fscale;                    // half output: float(1.0 / maxv)
+};
+
+// One launch over n <= CVT_MAX_FRAMES frames of `format` (VP9HIP_OUT_*); hbd: 16-bit source
+// samples. Returns the launch's hipError_t.
+hipError_t vp9hip_convert_launch(const CvtArgs &a, int format, int hbd, int ss_h, int ss_v, int n, hipStream_t st);
+
+#endif

@@ -48,7 +48,7 @@ using vp9hip::ParsePool;
 
 namespace {
 struct Pending { vp9h_frame pkt; LFrame f; };   // f.refs: -1 for keyframes / intra-only
-struct Out { int buf; int64_t pts; bool submitted; uint64_t id; };
+struct Out { int buf; int64_t pts; bool submitted; uint64_t id; int cs, full; };   // cs / full: the frame's colour space, range
 // Batches are numbered as launched (1, 2, ...) and rotate over VP9HIP_PIPELINE_SLOTS batch
 // slots (vp9hip::Ledger), so batches k + 1 and k + 2 are staged and planned while batch k's
 // pixel kernels run. A frame's batch is the one that wrote its buffer (Ledger::seq_of). A
@@ -165,7 +165,7 @@ static int consume_one(vp9hip_decoder *d, ParseJob &j)
         const int b = d->configured ? d->slot[info.show_slot & 7] : -1;
         if (b < 0) return VP9HIP_EINVALIDDATA;
         d->pins[b]++;
-        d->outq.push_back({ b, j.pts, d->batch.empty(), d->led.holder(b) });
+        d->outq.push_back({ b, j.pts, d->batch.empty(), d->led.holder(b), info.colorspace, info.full_range });
         return 0;
     }
     const bool intra = f.keyframe || f.intraonly;
@@ -206,7 +206,7 @@ static int consume_one(vp9hip_decoder *d, ParseJob &j)
     d->batch.push_back(q);
     if (info.show_frame) {
         d->pins[out]++;
-        d->outq.push_back({ out, j.pts, false, q.f.id });
+        d->outq.push_back({ out, j.pts, false, q.f.id, info.colorspace, info.full_range });
     }
     if ((int) d->batch.size() >= d->p.max_batch) return submit(d);
     return 0;
@@ -359,6 +359,8 @@ extern "C" int vp9hip_decoder_receive_frame(vp9hip_decoder *d, vp9hip_decoded_fr
     out->ss_h = d->css_h;
     out->ss_v = d->css_v;
     out->pts = o.pts;
+    out->colorspace = o.cs;
+    out->full_range = o.full;
     return 0;                      // the buffer stays pinned until vp9hip_decoder_release
 }
 
@@ -367,6 +369,31 @@ extern "C" int vp9hip_decoder_release(vp9hip_decoder *d, int buf)
     if (!d || buf < 0 || buf >= d->nbufs || d->pins[buf] <= 0) return VP9HIP_EINVAL;
     d->pins[buf]--;
     return 0;
+}
+
+// Received frames to an output format (vp9hip_convert_frames). They are complete (their batch
+// was checked by receive_frame), so nothing is ordered here.
+extern "C" int vp9hip_decoder_convert(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n, int format,
+                                      void *dst_dev, int64_t pitch, int64_t frame_stride, void *stream)
+{
+    if (!d || !frames || n <= 0 || !d->configured) return VP9HIP_EINVAL;
+    std::vector<int> bufs(n);
+    for (int i = 0; i < n; i++) {
+        const vp9hip_decoded_frame &f = frames[i];
+        if (f.buf < 0 || f.buf >= d->nbufs || d->pins[f.buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+        if (f.width != frames[0].width || f.height != frames[0].height || f.colorspace != frames[0].colorspace ||
+            f.full_range != frames[0].full_range) return VP9HIP_EINVAL;
+        bufs[i] = f.buf;
+    }
+    vp9hip_out_desc o;
+    memset(&o, 0, sizeof(o));
+    o.format = format;
+    const int cs = frames[0].colorspace;
+    o.colorspace = cs == 0 || cs == 6 ? 2 : cs;    // unknown / reserved: BT.709
+    o.full_range = frames[0].full_range;
+    o.width = frames[0].width; o.height = frames[0].height;
+    o.pitch = pitch; o.frame_stride = frame_stride;
+    return vp9hip_convert_frames(d->ctx, bufs.data(), n, &o, dst_dev, stream);
 }
 
 // avcodec_flush_buffers (vp9.c:1865-1883): drop the decoder delay and the reference

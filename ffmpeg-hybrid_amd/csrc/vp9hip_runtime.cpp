@@ -40,6 +40,7 @@
 #include "vp9hip_work.h"
 #include "vp9hip_planlogic.h"
 #include "vp9hip_plan.h"
+#include "vp9hip_convert.h"
 
 extern "C" {
 int vp9hip_launch_resid_multi(int hb, hipStream_t st, const uint32_t *off, const uint32_t *n, const RJob *jobs,
@@ -2887,6 +2888,53 @@ extern "C" int vp9hip_frame_device(vp9hip_ctx *c, int buf, void *planes[3], ptrd
     if (width) *width = c->buf_wh[buf].first;
     if (height) *height = c->buf_wh[buf].second;
     if (stream) *stream = (void *) c->st;
+    return 0;
+}
+
+// Output conversion (vp9hip_convert.hip): frames bufs[0 .. n-1] into dst_dev, enqueued on
+// `stream` (NULL: the current slot's main stream). Everything is validated before the first
+// launch, so a refused call writes nothing. The buffers' pointers travel as kernel
+// arguments, CVT_MAX_FRAMES per launch: no device table, no copy, nothing to free.
+extern "C" int vp9hip_convert_frames(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d, void *dst_dev,
+                                     void *stream)
+{
+    if (!c || !bufs || n <= 0 || !d || !dst_dev || c->bufs.empty()) return VP9HIP_EINVAL;
+    if (d->width <= 0 || d->height <= 0 || d->width > c->w || d->height > c->h) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (bufs[i] < 0 || bufs[i] >= (int) c->bufs.size()) return VP9HIP_EINVAL;
+    int64_t pitch = 0, off[3];
+    const int64_t bytes = vp9hip_out_layout(d, c->bpp, c->ss_h, c->ss_v, &pitch, off);
+    if (bytes < 0) return VP9HIP_EINVAL;
+    const int64_t stride = d->frame_stride ? d->frame_stride : bytes;
+    const bool rgb_out = d->format != VP9HIP_OUT_SEMIPLANAR;
+    const bool wide = d->format == VP9HIP_OUT_RGBP_F16 || (!rgb_out && c->hb);   // 16-bit output elements
+    if (wide && (((uintptr_t) dst_dev | (uintptr_t) stride) & 1)) return VP9HIP_EINVAL;
+    CvtArgs a;
+    memset(&a, 0, sizeof(a));
+    a.frame_stride = stride; a.pitch = pitch; a.plane = off[1];
+    for (int p = 0; p < 3; p++) a.src_off[p] = (int64_t) c->plane_off[p];
+    a.src_pitch[0] = c->pitch[0] * c->bypp; a.src_pitch[1] = c->pitch[1] * c->bypp;
+    a.w = d->width; a.h = d->height;
+    a.cw = (d->width + c->ss_h) >> c->ss_h; a.ch = (d->height + c->ss_v) >> c->ss_v;
+    a.msb = c->hb ? 16 - c->bpp : 0;
+    if (rgb_out) {
+        const int ob = d->format == VP9HIP_OUT_RGBP_F16 ? c->bpp : 8;
+        if (vp9hip_out_coefs(d->colorspace, d->full_range, c->bpp, ob, a.c, &a.shift) < 0) return VP9HIP_EINVAL;
+        a.rgb = d->colorspace == 7;
+        a.rnd = a.shift > 0 ? 1 << (a.shift - 1) : 0;
+        a.yoff = d->full_range ? 0 : 16 << (c->bpp - 8);
+        a.coff = 1 << (c->bpp - 1);
+        a.maxv = (1 << ob) - 1;
+        a.fscale = (float) (1.0 / a.maxv);
+    }
+    hipSetDevice(c->dev);
+    hipStream_t st = stream ? (hipStream_t) stream : c->st;
+    for (int i0 = 0; i0 < n; i0 += CVT_MAX_FRAMES) {
+        const int k = std::min(n - i0, CVT_MAX_FRAMES);
+        for (int i = 0; i < k; i++) a.src[i] = c->bufs[bufs[i0 + i]];
+        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
+        HIPCHK(vp9hip_convert_launch(a, d->format, c->hb, c->ss_h, c->ss_v, k, st));
+    }
     return 0;
 }
 

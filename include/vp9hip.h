@@ -33,7 +33,10 @@ extern "C" {
 /* 2: vp9h_synth_params / vp9h_enc_params end in a vp9h_seg_params; vp9hip_test_hooks,
  * vp9hip_batch_frame_status and VP9HIP_PIPELINE_SLOTS added. Callers check
  * vp9hip_abi_version() == VP9HIP_ABI_VERSION before passing structs. */
-#define VP9HIP_ABI_VERSION 2
+/* 3: vp9h_frame_info and vp9hip_decoded_frame end in colorspace / full_range;
+ * vp9h_stream_set_color and the output conversion (vp9hip_out_desc, vp9hip_convert_frames,
+ * vp9hip_decoder_convert) added. */
+#define VP9HIP_ABI_VERSION 3
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
 #define VP9HIP_EINVAL       (-22)          /* AVERROR(EINVAL)   */
@@ -234,6 +237,53 @@ int  vp9hip_download_frame(vp9hip_ctx *ctx, int buf, uint8_t *const planes[3],
  */
 int  vp9hip_frame_device(vp9hip_ctx *ctx, int buf, void *planes[3], ptrdiff_t linesize[3],
                          int *width, int *height, void **stream);
+
+/* ---- output conversion: decoded planes -> what GPU consumers read -------------------
+ * The reference leaves this to libswscale / the hwcontext's transfer; here the frames stay
+ * on the device, so the crop, chroma upsample, colour matrix and range expansion run there.
+ * The arithmetic is integer and exact (DESIGN.md "Output conversion"): chroma is the nearest
+ * sample U[y >> ss_v][x >> ss_h]; 14 fractional coefficient bits, round half up, clip. */
+enum { VP9HIP_OUT_SEMIPLANAR,  /* Y plane, then interleaved UV plane, at the source's subsampling:
+                                  NV12/NV16/NV24 for 8-bit; 16-bit MSB-aligned (P010/P012 style,
+                                  sample << (16 - bpp)) above 8 bits */
+       VP9HIP_OUT_RGB24,       /* packed R,G,B u8, H x W x 3 */
+       VP9HIP_OUT_RGBP_U8,     /* planar u8, 3 x H x W */
+       VP9HIP_OUT_RGBP_F16 };  /* planar IEEE half in [0,1], 3 x H x W */
+typedef struct vp9hip_out_desc {
+    int32_t format;            /* VP9HIP_OUT_*                                          */
+    int32_t colorspace;        /* VP9 code 1..5 or 7 (ignored for SEMIPLANAR); 0/6: EINVAL */
+    int32_t full_range;
+    int32_t width, height;     /* visible size to convert (<= the configured size)      */
+    int64_t pitch;             /* bytes per output row, 0 = tight; must be a multiple of 16 if not tight */
+    int64_t frame_stride;      /* bytes between frames, 0 = tight                        */
+} vp9hip_out_desc;
+/* Host only. The layout of one converted frame of a bpp / ss_h / ss_v source: returns its
+ * bytes (pitch x rows of all planes) or VP9HIP_EINVAL; *pitch is the row pitch in effect and
+ * plane_offset the byte offsets of its planes (R, G, B; or Y, the UV plane, and V's first
+ * sample inside it; RGB24: 0, 1, 2). The tight pitch is the widest row: 3 w (RGB24), w (u8
+ * planes), 2 w (half planes); SEMIPLANAR uses one pitch for both planes, the larger of the Y
+ * row and the UV row (2 chroma samples per chroma column), and has (h + chroma rows) rows. */
+int64_t vp9hip_out_layout(const vp9hip_out_desc *d, int bpp, int ss_h, int ss_v,
+                          int64_t *pitch, int64_t plane_offset[3]);
+/* Host only. The integer matrix of colour space 1..5 (VP9 codes: 1 / 3 BT.601, 2 BT.709,
+ * 4 SMPTE-240M, 5 BT.2020 NCL) for bpp-bit samples and out_bits-bit output (8, or bpp for
+ * the half format): c = CY, CRV, CGU, CGV, CBU, each floor(x * 2^shift + 0.5) with
+ * shift = 14 + bpp - out_bits. Code 7 (RGB planes G, B, R) has no matrix: c is zero and
+ * shift = bpp - out_bits. Codes 0 and 6: VP9HIP_EINVAL. */
+int     vp9hip_out_coefs(int colorspace, int full_range, int bpp, int out_bits, int32_t c[5], int32_t *shift);
+/* Convert the visible d->width x d->height pixels of device buffers bufs[0 .. n-1] (any
+ * order, repeats allowed) into n frames at dst_dev (device memory, laid out as
+ * vp9hip_out_layout says, frame i at i * frame_stride), in one launch per 32 frames. Enqueues
+ * on `stream` (a hipStream_t; NULL: the current slot's main stream) and returns without
+ * waiting. It orders nothing itself: the caller orders it after the frames' producer with
+ * vp9hip_slot_stream_wait or a sync, exactly as for vp9hip_frame_device. Bytes outside the
+ * visible rows and columns (pitch padding, frame_stride gaps) are not written.
+ * VP9HIP_EINVAL: a buffer index out of range, a size above the configured one, n <= 0, a
+ * NULL dst_dev, a layout vp9hip_out_layout refuses, or a dst_dev / frame_stride that is odd
+ * for a 16-bit output. */
+int  vp9hip_convert_frames(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip_out_desc *d,
+                           void *dst_dev, void *stream);
+
 /* Upload host planes into device buffer `buf` (test hook for reference frames). */
 int  vp9hip_upload_frame(vp9hip_ctx *ctx, int buf, const uint8_t *const planes[3],
                          const ptrdiff_t linesize[3]);
@@ -364,6 +414,13 @@ void vp9h_stream_close(vp9h_stream *s);
  * entropy-decoded concurrently, as decode_tiles_mt does with slice threads
  * (vp9.c:1441-1520, launched at 1777-1806). The packet is the serial walk's, byte for byte. */
 int  vp9h_stream_set_threads(vp9h_stream *s, int n);
+/* Encoding streams: the colour space (VP9 code: 0 unknown, 1 BT.470BG/601, 2 BT.709,
+ * 3 SMPTE-170M/601, 4 SMPTE-240M, 5 BT.2020 NCL, 7 RGB) and range bit that the colour config
+ * of the following keyframes / intra-only frames codes (read_colorspace_details,
+ * vp9.c:457-517). Default 2, 0. Code 6 (reserved): VP9HIP_EINVAL. Code 7 has no range bit
+ * (full range) and vp9h_stream_encode accepts it only for 4:4:4 packets (profile 1 / 3),
+ * else it returns VP9HIP_EINVAL. */
+int  vp9h_stream_set_color(vp9h_stream *s, int colorspace, int full_range);
 
 /* What the frame header decided beyond the packet (reference slot bookkeeping for the
  * device buffers, vp9.c:1686-1691, 1845-1849). */
@@ -377,6 +434,10 @@ typedef struct vp9h_frame_info {
     int32_t error_res, refresh_ctx, parallel, ctx_id;
     int32_t allow_hp, interp, comp_mode, tx_mode;
     uint32_t header_size, compressed_header_size;
+    int32_t colorspace, full_range; /* the stream's colour space code and range in effect for  */
+                                   /* this frame (avctx->colorspace / color_range: kept over  */
+                                   /* inter frames and show_existing_frame; RGB is full range; */
+                                   /* a profile-0 intra-only frame sets BT.601 limited)        */
 } vp9h_frame_info;
 
 /* Parse one frame (one superframe part) of the stream: the packet, or for
@@ -450,7 +511,10 @@ int  vp9h_frame_type(const uint8_t *data, size_t size);
  * stream state (vp9.c:519-611, what vp9.c knows before ff_thread_finish_setup):
  * show_existing_frame + show_slot, show_frame, error_res, refresh_mask, and ref_slot /
  * sign_bias of inter frames; the other fields are zero. Returns 0 keyframe, 1 inter frame,
- * 2 show_existing_frame, 3 intra-only frame, or AVERROR_INVALIDDATA. */
+ * 2 show_existing_frame, 3 intra-only frame, or AVERROR_INVALIDDATA. Being stateless, it
+ * fills colorspace / full_range only for frames whose header codes them (keyframes, and
+ * intra-only frames in profiles 1-3) and leaves 0 otherwise: the values in effect for any
+ * other frame are the stream's (vp9h_stream_decode / vp9h_stream_decode_begin). */
 int  vp9h_frame_peek(const uint8_t *data, size_t size, vp9h_frame_info *info);
 
 /* Split a superframe into its frames (vp9_superframe_split_bsf,
@@ -534,6 +598,7 @@ typedef struct vp9hip_decoded_frame {
     int32_t buf;                   /* device buffer of vp9hip_decoder_context()              */
     int32_t width, height, bpp, ss_h, ss_v;
     int64_t pts;
+    int32_t colorspace, full_range; /* vp9h_frame_info's, of the frame in this buffer         */
 } vp9hip_decoded_frame;
 void vp9hip_decoder_defaults(vp9hip_decoder_params *p);
 int  vp9hip_decoder_open(const vp9hip_decoder_params *p, vp9hip_decoder **out);
@@ -544,6 +609,15 @@ int  vp9hip_decoder_send_packet(vp9hip_decoder *d, const uint8_t *data, size_t s
 /* The next output frame; its buffer stays valid until vp9hip_decoder_release. */
 int  vp9hip_decoder_receive_frame(vp9hip_decoder *d, vp9hip_decoded_frame *out);
 int  vp9hip_decoder_release(vp9hip_decoder *d, int buf);
+/* Convert n received frames (all of one size, colour space and range, else VP9HIP_EINVAL)
+ * to `format` (VP9HIP_OUT_*) at dst_dev with vp9hip_convert_frames; pitch / frame_stride as
+ * in vp9hip_out_desc. Colour space and range are the frames'; an unknown colour space (code
+ * 0 or 6) converts as BT.709. Received frames are complete (receive_frame checked their
+ * batch), so this only enqueues on `stream` (NULL: the context's main stream) and returns:
+ * the buffers must stay un-released (vp9hip_decoder_release) until the work on `stream` has
+ * finished. */
+int  vp9hip_decoder_convert(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n, int format,
+                            void *dst_dev, int64_t pitch, int64_t frame_stride, void *stream);
 /* avcodec_flush_buffers: drop queued frames and reference state (seek). */
 int  vp9hip_decoder_flush(vp9hip_decoder *d);
 
