@@ -151,7 +151,7 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9hip_decoder_send_packet", "vp9hip_decoder_receive_frame", "vp9hip_decoder_release",
                "vp9hip_decoder_flush",
                "vp9h_stream_set_color", "vp9hip_out_layout", "vp9hip_out_coefs", "vp9hip_convert_frames",
-               "vp9hip_decoder_convert"]
+               "vp9hip_decoder_convert", "vp9hip_convert_frames_scaled", "vp9hip_decoder_convert_scaled"]
 
 
 def lib():
@@ -272,6 +272,11 @@ def lib():
                                         ctypes.c_void_p, ctypes.c_void_p]
     L.vp9hip_decoder_convert.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
+    L.vp9hip_convert_frames_scaled.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(OutDesc),
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_decoder_convert_scaled.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_void_p]
     _lib_handle = L
     return L
 
@@ -758,8 +763,16 @@ class Device:
         return flat, (wide.as_strided((n, h, w), (stride // 2, pitch // 2, 1)),
                       wide[off[1] // 2:].as_strided((n, ch, cw, 2), (stride // 2, pitch // 2, 2, 1))), pitch, stride
 
+    @staticmethod
+    def _resize_arg(fn, resize):
+        """(OW, OH) of a resize argument; outside 1..16384 is refused as the library refuses it."""
+        ow, oh = (int(x) for x in resize)
+        if not (1 <= ow <= 16384 and 1 <= oh <= 16384):
+            raise Vp9HipError(fn, EINVAL)
+        return ow, oh
+
     def convert(self, bufs, fmt, colorspace=2, full_range=False, size=None, out=None, stream=None,
-                pitch=0, frame_stride=0):
+                pitch=0, frame_stride=0, resize=None):
         """Convert device buffers `bufs` (any order) to `fmt` on the GPU (vp9hip_convert_frames):
         "rgb24" -> (N,H,W,3) uint8, "rgbp_u8" -> (N,3,H,W) uint8, "rgbp_f16" -> (N,3,H,W)
         float16 in [0,1], "semiplanar" -> (y, uv) views of one allocation, (N,H,W) and
@@ -767,7 +780,10 @@ class Device:
         samples (P010 style) as frame_tensors does. colorspace is the VP9 code (1..5, 7 = RGB
         planes), size the visible (width, height) (default: the configured size). `out` is a
         contiguous uint8 cuda tensor to write into (else one is allocated); pitch / frame_stride
-        as in vp9hip_out_desc (0 = tight). Runs in the order of torch's current stream (or on
+        as in vp9hip_out_desc (0 = tight). resize=(OW, OH) resamples the visible picture to OW x OH
+        with the exact box filter in the same launch (vp9hip_convert_frames_scaled; the shapes,
+        `out`, pitch and frame_stride are then the output's, the UV view (N,OCH,OCW,2)); a given
+        resize always takes that kernel, None is the unscaled one. Runs in the order of torch's current stream (or on
         `stream`, a hipStream_t handle; see _enqueue_for_torch) and does not wait: order it after the frames' producer (sync(), or
         vp9hip_slot_stream_wait), as for frame_tensors. Needs torch imported before the library
         was loaded (see _torch_first)."""
@@ -778,13 +794,18 @@ class Device:
         bufs = [int(b) for b in bufs]
         w, h = size if size is not None else (self.w, self.h)
         d = OutDesc(OUT_FORMATS[fmt], int(colorspace), int(bool(full_range)), int(w), int(h), int(pitch), int(frame_stride))
+        fn = "vp9hip_convert_frames" if resize is None else "vp9hip_convert_frames_scaled"
         if not bufs:
-            raise Vp9HipError("vp9hip_convert_frames", EINVAL)
-        flat, res, _, _ = self._convert_out(len(bufs), fmt, w, h, self.bpp, self.ss_h, self.ss_v, out, pitch, frame_stride)
+            raise Vp9HipError(fn, EINVAL)
+        ow, oh = (w, h) if resize is None else self._resize_arg(fn, resize)
+        flat, res, _, _ = self._convert_out(len(bufs), fmt, ow, oh, self.bpp, self.ss_h, self.ss_v, out, pitch, frame_stride)
         arr = (ctypes.c_int * len(bufs))(*bufs)
-        _check("vp9hip_convert_frames", _enqueue_for_torch(
-            self.frame_device(0)[3], stream,
-            lambda st: lib().vp9hip_convert_frames(self._c, arr, len(bufs), ctypes.byref(d), flat.data_ptr(), st)))
+        if resize is None:
+            call = lambda st: lib().vp9hip_convert_frames(self._c, arr, len(bufs), ctypes.byref(d), flat.data_ptr(), st)
+        else:
+            call = lambda st: lib().vp9hip_convert_frames_scaled(self._c, arr, len(bufs), ctypes.byref(d), ow, oh,
+                                                                 flat.data_ptr(), st)
+        _check(fn, _enqueue_for_torch(self.frame_device(0)[3], stream, call))
         return res
 
     def upload(self, buf, planes):
@@ -902,28 +923,33 @@ class Decoder:
     def context(self):
         return ctypes.c_void_p(lib().vp9hip_decoder_context(self._d))
 
-    def convert(self, infos, fmt, out=None):
+    def convert(self, infos, fmt, out=None, resize=None):
         """Convert the frames of receive_frame(download=False) (their DecodedFrameInfos, all of
         one size, colour space and range) to `fmt` as Device.convert does, with the frames' own
-        colour description (vp9hip_decoder_convert), on torch's current stream; waits for it
-        and releases the buffers. Returns the tensor(s)."""
+        colour description (vp9hip_decoder_convert; with resize=(OW, OH)
+        vp9hip_decoder_convert_scaled), on torch's current stream; waits for it and releases
+        the buffers. Returns the tensor(s)."""
         if not _torch_first:
             raise Vp9HipUnavailable("convert: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
                                     "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
         import torch
         infos = list(infos)
+        fn = "vp9hip_decoder_convert" if resize is None else "vp9hip_decoder_convert_scaled"
         if not infos:
-            raise Vp9HipError("vp9hip_decoder_convert", EINVAL)
+            raise Vp9HipError(fn, EINVAL)
         arr = (DecodedFrameInfo * len(infos))(*infos)
         f = infos[0]
-        flat, res, pitch, stride = Device._convert_out(len(infos), fmt, f.width, f.height, f.bpp, f.ss_h, f.ss_v,
-                                                       out, 0, 0)
+        ow, oh = (f.width, f.height) if resize is None else Device._resize_arg(fn, resize)
+        flat, res, pitch, stride = Device._convert_out(len(infos), fmt, ow, oh, f.bpp, f.ss_h, f.ss_v, out, 0, 0)
         main = ctypes.c_void_p()
         _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
                                                                 (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
-        _check("vp9hip_decoder_convert", _enqueue_for_torch(
-            main.value, None,
-            lambda st: lib().vp9hip_decoder_convert(self._d, arr, len(infos), OUT_FORMATS[fmt], flat.data_ptr(), 0, 0, st)))
+        if resize is None:
+            call = lambda st: lib().vp9hip_decoder_convert(self._d, arr, len(infos), OUT_FORMATS[fmt], flat.data_ptr(), 0, 0, st)
+        else:
+            call = lambda st: lib().vp9hip_decoder_convert_scaled(self._d, arr, len(infos), OUT_FORMATS[fmt], ow, oh,
+                                                                  flat.data_ptr(), 0, 0, st)
+        _check(fn, _enqueue_for_torch(main.value, None, call))
         torch.cuda.current_stream().synchronize()
         for i in infos:
             self.release(i.buf)

@@ -28,4 +28,17 @@ struct CvtArgs {
 // samples. Returns the launch's hipError_t.
 hipError_t vp9hip_convert_launch(const CvtArgs &a, int format, int hbd, int ss_h, int ss_v, int n, hipStream_t st);
 
+// The fused box-filter resize (vp9hip_convert_scale.hip). c.w / c.h / c.cw / c.ch stay the
+// visible source size; c.pitch / c.plane / c.frame_stride describe the out_w x out_h output.
+struct CvtScaleArgs {
+    CvtArgs c;
+    int32_t ow, oh;                    // output luma (and RGB) size
+    int32_t cow, coh;                  // size the chroma planes are resampled to (RGB: ow, oh; semi-planar: OCW, OCH)
+    double  rcp[2];                    // 1.0 / (w h), 1.0 / (cw ch): the quotient's estimate, corrected in the kernel
+    double  rx[2], ry[2];              // 1.0 / ow, 1.0 / cow and 1.0 / oh, 1.0 / coh: the footprints' bounds, likewise
+};
+
+// One launch of k_convert_scale over n <= CVT_MAX_FRAMES frames.
+hipError_t vp9hip_convert_scale_launch(const CvtScaleArgs &a, int format, int hbd, int n, hipStream_t st);
+
 #endif

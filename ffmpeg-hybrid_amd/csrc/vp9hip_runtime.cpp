@@ -2891,25 +2891,31 @@ extern "C" int vp9hip_frame_device(vp9hip_ctx *c, int buf, void *planes[3], ptrd
     return 0;
 }
 
-// Output conversion (vp9hip_convert.hip): frames bufs[0 .. n-1] into dst_dev, enqueued on
-// `stream` (NULL: the current slot's main stream). Everything is validated before the first
-// launch, so a refused call writes nothing. The buffers' pointers travel as kernel
-// arguments, CVT_MAX_FRAMES per launch: no device table, no copy, nothing to free.
-extern "C" int vp9hip_convert_frames(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d, void *dst_dev,
-                                     void *stream)
+// Output conversion (vp9hip_convert.hip, vp9hip_convert_scale.hip): frames bufs[0 .. n-1] into
+// dst_dev, enqueued on `stream` (NULL: the current slot's main stream). Everything is
+// validated before the first launch, so a refused call writes nothing. The buffers' pointers
+// travel as kernel arguments, CVT_MAX_FRAMES per launch: no device table, no copy, nothing to
+// free.
+//
+// convert_args: the checks and the kernel arguments both entry points share. The output is
+// out_w x out_h (the visible size itself for the unscaled call); *stride is the frame stride
+// in effect.
+static int convert_args(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d, int out_w, int out_h,
+                        void *dst_dev, CvtArgs &a, int64_t *stride_out)
 {
     if (!c || !bufs || n <= 0 || !d || !dst_dev || c->bufs.empty()) return VP9HIP_EINVAL;
     if (d->width <= 0 || d->height <= 0 || d->width > c->w || d->height > c->h) return VP9HIP_EINVAL;
     for (int i = 0; i < n; i++)
         if (bufs[i] < 0 || bufs[i] >= (int) c->bufs.size()) return VP9HIP_EINVAL;
+    vp9hip_out_desc o = *d;
+    o.width = out_w; o.height = out_h;
     int64_t pitch = 0, off[3];
-    const int64_t bytes = vp9hip_out_layout(d, c->bpp, c->ss_h, c->ss_v, &pitch, off);
+    const int64_t bytes = vp9hip_out_layout(&o, c->bpp, c->ss_h, c->ss_v, &pitch, off);
     if (bytes < 0) return VP9HIP_EINVAL;
     const int64_t stride = d->frame_stride ? d->frame_stride : bytes;
     const bool rgb_out = d->format != VP9HIP_OUT_SEMIPLANAR;
     const bool wide = d->format == VP9HIP_OUT_RGBP_F16 || (!rgb_out && c->hb);   // 16-bit output elements
     if (wide && (((uintptr_t) dst_dev | (uintptr_t) stride) & 1)) return VP9HIP_EINVAL;
-    CvtArgs a;
     memset(&a, 0, sizeof(a));
     a.frame_stride = stride; a.pitch = pitch; a.plane = off[1];
     for (int p = 0; p < 3; p++) a.src_off[p] = (int64_t) c->plane_off[p];
@@ -2927,6 +2933,17 @@ extern "C" int vp9hip_convert_frames(vp9hip_ctx *c, const int *bufs, int n, cons
         a.maxv = (1 << ob) - 1;
         a.fscale = (float) (1.0 / a.maxv);
     }
+    *stride_out = stride;
+    return 0;
+}
+
+extern "C" int vp9hip_convert_frames(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d, void *dst_dev,
+                                     void *stream)
+{
+    CvtArgs a;
+    int64_t stride;
+    const int r = convert_args(c, bufs, n, d, d ? d->width : 0, d ? d->height : 0, dst_dev, a, &stride);
+    if (r < 0) return r;
     hipSetDevice(c->dev);
     hipStream_t st = stream ? (hipStream_t) stream : c->st;
     for (int i0 = 0; i0 < n; i0 += CVT_MAX_FRAMES) {
@@ -2934,6 +2951,36 @@ extern "C" int vp9hip_convert_frames(vp9hip_ctx *c, const int *bufs, int n, cons
         for (int i = 0; i < k; i++) a.src[i] = c->bufs[bufs[i0 + i]];
         a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
         HIPCHK(vp9hip_convert_launch(a, d->format, c->hb, c->ss_h, c->ss_v, k, st));
+    }
+    return 0;
+}
+
+// The same with the box-filter resize to out_width x out_height fused in (k_convert_scale).
+extern "C" int vp9hip_convert_frames_scaled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d,
+                                            int out_width, int out_height, void *dst_dev, void *stream)
+{
+    if (out_width < 1 || out_width > 16384 || out_height < 1 || out_height > 16384) return VP9HIP_EINVAL;
+    CvtScaleArgs s;
+    int64_t stride;
+    memset(&s, 0, sizeof(s));
+    const int r = convert_args(c, bufs, n, d, out_width, out_height, dst_dev, s.c, &stride);
+    if (r < 0) return r;
+    CvtArgs &a = s.c;
+    s.ow = out_width; s.oh = out_height;
+    const bool semi = d->format == VP9HIP_OUT_SEMIPLANAR;      // chroma keeps the subsampling; RGB resamples it to the output size
+    s.cow = semi ? (out_width + c->ss_h) >> c->ss_h : out_width;
+    s.coh = semi ? (out_height + c->ss_v) >> c->ss_v : out_height;
+    s.rcp[0] = 1.0 / ((double) a.w * (double) a.h);
+    s.rcp[1] = 1.0 / ((double) a.cw * (double) a.ch);
+    s.rx[0] = 1.0 / s.ow; s.rx[1] = 1.0 / s.cow;
+    s.ry[0] = 1.0 / s.oh; s.ry[1] = 1.0 / s.coh;
+    hipSetDevice(c->dev);
+    hipStream_t st = stream ? (hipStream_t) stream : c->st;
+    for (int i0 = 0; i0 < n; i0 += CVT_MAX_FRAMES) {
+        const int k = std::min(n - i0, CVT_MAX_FRAMES);
+        for (int i = 0; i < k; i++) a.src[i] = c->bufs[bufs[i0 + i]];
+        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
+        HIPCHK(vp9hip_convert_scale_launch(s, d->format, c->hb, k, st));
     }
     return 0;
 }

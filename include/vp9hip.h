@@ -35,7 +35,8 @@ extern "C" {
  * vp9hip_abi_version() == VP9HIP_ABI_VERSION before passing structs. */
 /* 3: vp9h_frame_info and vp9hip_decoded_frame end in colorspace / full_range;
  * vp9h_stream_set_color and the output conversion (vp9hip_out_desc, vp9hip_convert_frames,
- * vp9hip_decoder_convert) added. */
+ * vp9hip_decoder_convert) added. vp9hip_convert_frames_scaled / vp9hip_decoder_convert_scaled
+ * came later as new symbols only: no struct changed, so the version stayed. */
 #define VP9HIP_ABI_VERSION 3
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -283,6 +284,44 @@ int     vp9hip_out_coefs(int colorspace, int full_range, int bpp, int out_bits, 
  * for a 16-bit output. */
 int  vp9hip_convert_frames(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip_out_desc *d,
                            void *dst_dev, void *stream);
+/*
+ * Box-filter resize, fused into the conversion (one launch per 32 frames crops, resamples
+ * and converts; the full-size frame is never written). The definition is integer and exact,
+ * like the rest of the conversion (DESIGN.md "Box-filter resize").
+ *
+ * box(P, ow, oh) resamples a visible plane P of w x h integer samples to ow x oh: the exact
+ * area mean, rounded once.
+ *   wx(ox, sx) = max(0, min((ox+1) w, (sx+1) ow) - max(ox w, sx ow))
+ *       the overlap of [ox w, (ox+1) w) and [sx ow, (sx+1) ow); one ox's weights sum to w.
+ *       wy(oy, sy) is the same with h and oh.
+ *   A(ox, oy)  = sum_sy wy(oy, sy) sum_sx wx(ox, sx) P[sy][sx]       exact integers, < 2^63
+ *   box        = (A + (w h >> 1)) / (w h)                            floor: round half up
+ * There is no intermediate rounding and no normalised weight, so every evaluation order
+ * gives the same integers. The same formula serves every ratio: with ow == w and oh == h it
+ * is the identity, and upscaling is nearest-neighbour with blended seams (an output sample
+ * inside one source sample copies it, one across a boundary blends the two by area); bilinear
+ * or bicubic upscaling is not offered.
+ *
+ * For a visible source of w x h luma and cw x ch chroma (cw = (w + ss_h) >> ss_h) and an
+ * output of OW x OH:
+ *   SEMIPLANAR: Y' = box(Y, OW, OH), U' = box(U, OCW, OCH), V' = box(V, OCW, OCH) with
+ *       OCW = (OW + ss_h) >> ss_h, OCH = (OH + ss_v) >> ss_v; then interleaved and
+ *       << (16 - bpp) above 8 bits as without a resize.
+ *   RGB24, RGBP_U8, RGBP_F16: all three planes are resampled to the output size, box(Y, OW,
+ *       OH), box(U, OW, OH), box(V, OW, OH) (the chroma plane is taken to cover the same
+ *       picture area as luma: siting is not coded); the three planes, at the source's depth,
+ *       then go through the conversion's arithmetic unchanged, as a 4:4:4 source would:
+ *       matrix, clip, code-7 pass-through, the half multiply.
+ * Only the visible d->width x d->height (the top-left crop) contributes: samples of the
+ * 64-padding, or of a configured size larger than the visible one, never enter a sum.
+ *
+ * d->width / d->height stay the visible source size; the output is laid out as
+ * vp9hip_out_layout says for a desc of out_width x out_height with d's pitch / frame_stride.
+ * Checked as vp9hip_convert_frames before the first launch (a refused call writes nothing);
+ * out_width / out_height outside 1..16384: VP9HIP_EINVAL.
+ */
+int  vp9hip_convert_frames_scaled(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip_out_desc *d,
+                                  int out_width, int out_height, void *dst_dev, void *stream);
 
 /* Upload host planes into device buffer `buf` (test hook for reference frames). */
 int  vp9hip_upload_frame(vp9hip_ctx *ctx, int buf, const uint8_t *const planes[3],
@@ -618,6 +657,11 @@ int  vp9hip_decoder_release(vp9hip_decoder *d, int buf);
  * finished. */
 int  vp9hip_decoder_convert(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n, int format,
                             void *dst_dev, int64_t pitch, int64_t frame_stride, void *stream);
+/* The same through vp9hip_convert_frames_scaled: the frames resampled to out_width x
+ * out_height; pitch / frame_stride describe that output. */
+int  vp9hip_decoder_convert_scaled(vp9hip_decoder *dec, const vp9hip_decoded_frame *frames, int n, int format,
+                                   int out_width, int out_height, void *dst_dev,
+                                   int64_t pitch, int64_t frame_stride, void *stream);
 /* avcodec_flush_buffers: drop queued frames and reference state (seek). */
 int  vp9hip_decoder_flush(vp9hip_decoder *d);
 
