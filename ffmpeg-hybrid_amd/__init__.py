@@ -277,6 +277,7 @@ def lib():
     L.vp9hip_decoder_convert_scaled.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_void_p]
+    L.vp9hip_resid4_host.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
     _lib_handle = L
     return L
 
@@ -326,6 +327,21 @@ def _check(fn, r):
     if r < 0:
         raise Vp9HipError(fn, r)
     return r
+
+
+def resid4_host(bpp, tcode, txtp, eobs, coefs):
+    """The 4x4 residual kernels' lane routine run on the host (vp9hip_resid4_host): coefs is
+    (n, 16) scan-order coefficients (int16 at 8 bits, int32 above), eobs (n,) in 1..16; returns
+    the (n, 16) int32 residuals, column-major (x * 4 + y), before the int16 saturation."""
+    hb = int(bpp > 8)
+    coefs = np.ascontiguousarray(coefs, np.int32 if hb else np.int16)
+    eobs = np.ascontiguousarray(eobs, np.uint8)
+    n = len(eobs)
+    assert coefs.shape == (n, 16)
+    res = np.empty((n, 16), np.int32)
+    _check("vp9hip_resid4_host", lib().vp9hip_resid4_host(hb, tcode, txtp, n, eobs.ctypes.data, coefs.ctypes.data,
+                                                          res.ctypes.data))
+    return res
 
 
 def synth_params(width, height, bpp=8, **kw):

@@ -1,8 +1,9 @@
 // gfx950 (MI355X) kernels of the VP9 hybrid decoder pixel path.
 //
 //   k_resid / k_resid_dev / k_resid_multi — inverse DCT / ADST / WHT of every coded tx block
-//              (vp9dsp_template.c:1155-1754): one lane per column, 64 / N jobs per wave,
-//              LDS transpose; intra residuals to int16 scratch, inter ones added in place.
+//              (vp9dsp_template.c:1155-1754): 8x8 to 32x32 one lane per column, 64 / N jobs
+//              per wave, LDS transpose; 4x4 and WHT one lane per block, in registers
+//              (vp9hip_resid4.h); intra residuals to int16 scratch, inter ones added in place.
 //   k_pred   — intra prediction passes of an SB (vp9recon.c:235-364, the 15 predictors of
 //              vp9dsp_template.c:28-1106 as a per-pixel formula table) + residual add.
 //   k_lf     — the deblocking filter of one SB (ff_vp9_loopfilter_sb, vp9lpf.c:183-230) on
@@ -22,9 +23,10 @@
 #include <algorithm>
 #include <cstdlib>
 
-#define VP9T_STORAGE static __constant__ const
+#define VP9T_STORAGE static __constant__ constexpr
 #include "vp9_tables.h"
 #include "vp9hip_work.h"
+#include "vp9hip_resid4.h"
 
 // The Makefile compiles this file once per KPART (0..5), each object holding a subset of
 // the launchers below and so of the kernel instantiations (parallel builds); without KPART
@@ -60,41 +62,10 @@ DEV void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Transform arithmetic policy. 8-bit: uint32 bit patterns (defined wrap-around,
-// identical to the reference's `x * 11585U` products cast back to int) with an
-// arithmetic rounding shift. High bit depth: int64.
-struct M32 {
-    typedef uint32_t T;
-    static DEV T in(int32_t v) { return (uint32_t) v; }
-    static DEV T r14(T v) { return (uint32_t) ((int32_t) (v + 8192u) >> 14); }
-};
-struct M64 {
-    typedef int64_t T;
-    static DEV T in(int32_t v) { return (int64_t) v; }
-    static DEV T r14(T v) { return (v + 8192) >> 14; }
-};
-
+// Transform arithmetic policies M32 / M64, idct4, iadst4 and iwht4: vp9hip_resid4.h
 #define R(x) M::r14(x)
 #define C(k) ((T) (k))
 
-// vp9dsp_template.c:1202-1216
-template <class M> DEV void idct4(typename M::T *io)
-{
-    typedef typename M::T T;
-    T t0 = R((io[0] + io[2]) * C(11585)), t1 = R((io[0] - io[2]) * C(11585));
-    T t2 = R(io[1] * C(6270) - io[3] * C(15137)), t3 = R(io[1] * C(15137) + io[3] * C(6270));
-    io[0] = t0 + t3; io[1] = t1 + t2; io[2] = t1 - t2; io[3] = t0 - t3;
-}
-// vp9dsp_template.c:1218-1232
-template <class M> DEV void iadst4(typename M::T *io)
-{
-    typedef typename M::T T;
-    T t0 = C(5283) * io[0] + C(15212) * io[2] + C(9929) * io[3];
-    T t1 = C(9929) * io[0] - C(5283) * io[2] - C(15212) * io[3];
-    T t2 = C(13377) * (io[0] - io[2] + io[3]);
-    T t3 = C(13377) * io[1];
-    io[0] = R(t0 + t3); io[1] = R(t1 + t3); io[2] = R(t2); io[3] = R(t0 + t1 - t3);
-}
 // vp9dsp_template.c:1236-1270
 template <class M> DEV void idct8(typename M::T *io)
 {
@@ -366,16 +337,6 @@ template <class M> DEV void idct32(typename M::T *io)
 #undef R
 #undef C
 
-// iwht4_1d (vp9dsp_template.c:1719-1748), int temporaries
-DEV void iwht4(int32_t *io, int pass)
-{
-    uint32_t t0, t1, t2, t3, t4;
-    if (pass == 0) { t0 = io[0] >> 2; t1 = io[3] >> 2; t2 = io[1] >> 2; t3 = io[2] >> 2; }
-    else { t0 = io[0]; t1 = io[3]; t2 = io[1]; t3 = io[2]; }
-    t0 += t2; t3 -= t1; t4 = (uint32_t) ((int32_t) (t0 - t3) >> 1); t1 = t4 - t1; t2 = t4 - t2; t0 -= t1; t3 += t2;
-    io[0] = (int32_t) t0; io[1] = (int32_t) t1; io[2] = (int32_t) t2; io[3] = (int32_t) t3;
-}
-
 // One 1-D inverse transform of compile-time length N (adst: 0 dct, 1 adst).
 template <int N, class M> DEV void tx1n(typename M::T *v, int adst)
 {
@@ -442,11 +403,23 @@ DEV int pred_px(int mode, int n, int x, int y, const uint16_t *e, int dc, int bd
 // ------------------------------------------------------------- k_resid
 // Inverse transform of every coded tx block of a batch (vp9dsp_template.c:1139-1750),
 // one launch per tx code, no dependencies: a wave holds 64/N jobs, N lanes per job
-// (one per column). The residual (out + (1 << (bits - 1))) >> bits is either added in
-// place onto the motion-compensated prediction (inter blocks) or stored column-major
-// as int16 for k_pred (intra blocks; 10/12-bit values saturate to int16, which leaves
-// clip(pred + r) unchanged since |pred| < 4096).
+// (one per column), or 64 4x4 jobs, one lane each (resid_wave4). The residual
+// (out + (1 << (bits - 1))) >> bits is either added in place onto the motion-compensated
+// prediction (inter blocks) or stored column-major as int16 for k_pred (intra blocks;
+// 10/12-bit values saturate to int16, which leaves clip(pred + r) unchanged since
+// |pred| < 4096).
 #define RWAVES 4
+
+// resid4_scan (vp9hip_resid4.h) restates the three 4x4 scans as constant expressions
+constexpr bool scan4_same(const int16_t (&t)[16], int tcode, int txtp)
+{
+    for (int k = 0; k < 16; k++)
+        if (t[k] != resid4_scan(tcode, txtp, k)) return false;
+    return true;
+}
+static_assert(scan4_same(vp9t_scan_default_4x4, 0, 0) && scan4_same(vp9t_scan_default_4x4, 0, 3) &&
+              scan4_same(vp9t_scan_default_4x4, 4, 0) && scan4_same(vp9t_scan_col_4x4, 0, 1) &&
+              scan4_same(vp9t_scan_row_4x4, 0, 2), "resid4_scan differs from vp9_tables.h");
 
 DEV const int16_t *scan_for(int tcode, int txtp)
 {
@@ -481,6 +454,8 @@ template <int N, typename COEF> struct RWave { static constexpr int E = (64 / N)
 // launches); the keyframe launches (k_resid_dev) write scratch and keep their registers:
 // they run beside the other slot's k_plf chains, whose co-resident waves the extra
 // registers cost (r04's PREQ everywhere: C3 10,245 -> 9,863 fps on one box, profiles/r05b).
+// N == 4 here (and store_col's N == 4 branch) serves k_plf's residual workgroups and the
+// high-bit-depth DCT/ADST k_resid_dev only (RLane4); every other 4x4 launch is resid_wave4.
 template <int N, int TCODE, typename PIX, class M, typename COEF, bool PREQ = true>
 DEV void resid_wave(const RJob *__restrict__ jobs, int njobs, int wj, int lane, const FrameDesc *__restrict__ frames,
                     const COEF *__restrict__ coefs, int16_t *__restrict__ resid, COEF *cbw)
@@ -604,20 +579,166 @@ DEV void resid_wave(const RJob *__restrict__ jobs, int njobs, int wj, int lane, 
     }
 }
 
+// Jobs per wave of the residual launches (k_resid, k_resid_dev, k_resid_multi): a 4x4 block
+// is one lane's (resid_wave4), larger ones take N lanes (resid_wave). k_plf's residual
+// workgroups keep resid_wave for every size.
+template <int N> struct RCap { static constexpr int V = N == 4 ? 64 : 64 / N; };
+// k_resid_dev takes the lane-per-block form where it needs no more registers than the
+// lane-per-column one (it runs beside the other slots' k_plf waves, profiles/r05b): the
+// 8-bit kernels and the WHT. A high-bit-depth DCT/ADST block in one lane (int32
+// coefficients, the transposed intermediate, a column of int64 products) takes 59 VGPRs
+// against 36, so that one instantiation stays lane-per-column.
+template <int N, int TCODE, typename COEF> struct RLane4 { static constexpr bool V = N == 4 && (sizeof(COEF) == 2 || TCODE == 4); };
+template <int N, int TCODE, typename COEF> struct RDevCap { static constexpr int V = RLane4<N, TCODE, COEF>::V ? 64 : 64 / N; };
+
+// four dwords at a dword-aligned address, one load
+struct __attribute__((packed, aligned(4))) RQuad { uint32_t x, y, z, w; };
+
+// The 16 scan-order coefficients at src (eob of them live) by wide loads. src is only
+// element-aligned, so int16 coefficients come as the dword window from the dword at or below
+// src, shifted down a half word when src is odd. The loads reach R4_READ_SPAN16 / 32 bytes
+// from the first coefficient whatever eob is; that coefficient lies inside the arena, which
+// ends in VP9HIP_COEF_PAD spare bytes (vp9hip_runtime.cpp), and the arena's start is dword-
+// aligned, so no load leaves it at either end.
+static_assert(R4_READ_SPAN16 - 2 <= VP9HIP_COEF_PAD && R4_READ_SPAN32 - 4 <= VP9HIP_COEF_PAD,
+              "4x4 coefficient loads past the last block stay inside the arena's pad");
+DEV void load_coef16(const int16_t *src, int eob, int16_t (&c)[16])
+{
+    const uintptr_t a = (uintptr_t) src;
+    const int odd = (int) (a >> 1) & 1;
+    const uint32_t sh = (uint32_t) odd << 4;             // funnel shift: 16 bits when src is odd
+    const uint32_t *w = (const uint32_t *) (a & ~(uintptr_t) 3);
+    uint32_t d[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    if (eob > 0) {
+        const RQuad q0 = *(const RQuad *) w;
+        d[0] = q0.x; d[1] = q0.y; d[2] = q0.z; d[3] = q0.w;
+    }
+    if (eob + odd > 8) {
+        const RQuad q1 = *(const RQuad *) (w + 4);
+        d[4] = q1.x; d[5] = q1.y; d[6] = q1.z; d[7] = q1.w; d[8] = w[8];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint32_t p = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);
+        c[2 * k] = (int16_t) (p & 0xffff);
+        c[2 * k + 1] = (int16_t) (p >> 16);
+    }
+}
+DEV void load_coef16(const int32_t *src, int eob, int32_t (&c)[16])
+{
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        RQuad q = { 0, 0, 0, 0 };
+        if (eob > 4 * g) q = *(const RQuad *) (src + 4 * g);
+        c[4 * g] = (int32_t) q.x; c[4 * g + 1] = (int32_t) q.y; c[4 * g + 2] = (int32_t) q.z; c[4 * g + 3] = (int32_t) q.w;
+    }
+}
+
+// four pixels of a row, one word (dst is 4-pixel aligned, planes are 64-padded)
+DEV void load_px4(const uint8_t *p, int (&v)[4])
+{
+    const uint32_t w = *(const uint32_t *) p;
+    v[0] = w & 0xff; v[1] = (w >> 8) & 0xff; v[2] = (w >> 16) & 0xff; v[3] = w >> 24;
+}
+DEV void load_px4(const uint16_t *p, int (&v)[4])
+{
+    const uint2 w = *(const uint2 *) p;
+    v[0] = w.x & 0xffff; v[1] = w.x >> 16; v[2] = w.y & 0xffff; v[3] = w.y >> 16;
+}
+DEV void store_px4(uint8_t *p, const int (&v)[4])
+{
+    *(uint32_t *) p = (uint32_t) v[0] | (uint32_t) v[1] << 8 | (uint32_t) v[2] << 16 | (uint32_t) v[3] << 24;
+}
+DEV void store_px4(uint16_t *p, const int (&v)[4])
+{
+    *(uint2 *) p = make_uint2((uint32_t) v[0] | (uint32_t) v[1] << 16, (uint32_t) v[2] | (uint32_t) v[3] << 16);
+}
+
+// One wave of 4x4 residual work (tx code 0 or 4): jobs [wj * 64, (wj + 1) * 64) of `jobs`,
+// one lane per job, the whole block in registers (resid4_tx, vp9hip_resid4.h): no LDS, no
+// barrier. Jobs are bucketed by tx code and txtp, so a wave is nearly always uniform in
+// txtp; a wave across a bucket boundary runs each txtp present under its lanes' mask.
+// PREQ as in resid_wave.
+template <int TCODE, typename PIX, class M, typename COEF, bool PREQ = true>
+DEV void resid_wave4(const RJob *__restrict__ jobs, int njobs, int wj, int lane, const FrameDesc *__restrict__ frames,
+                     const COEF *__restrict__ coefs, int16_t *__restrict__ resid)
+{
+    const int j = wj * 64 + lane;
+    if (j >= njobs) return;
+    const RJob r = jobs[j];
+    const int eob = r.eob, txtp = TCODE == 4 ? 0 : RJ_TXTP(r);
+    COEF c[16];
+    load_coef16(coefs + r.coef, eob, c);
+    int pq[PREQ ? 4 : 1][4];
+    PIX *q = nullptr;
+    size_t qp = 0;
+    if (RJ_INPLACE(r)) {
+        const FrameDesc &fd = frames[r.frame];
+        const int p = RJ_PLANE(r);
+        q = (PIX *) fd.plane[p] + r.dst;
+        qp = (size_t) fd.pitch[p ? 1 : 0];
+        if (PREQ) {
+#pragma unroll
+            for (int y = 0; y < (PREQ ? 4 : 1); y++) load_px4(q + y * qp, pq[y]);
+        }
+    }
+
+    int32_t res[16];
+    if (TCODE == 4) resid4_tx<4, 0, M, COEF>(c, eob, res);
+    else {
+        if (txtp == 0) resid4_tx<0, 0, M, COEF>(c, eob, res);
+        if (txtp == 1) resid4_tx<0, 1, M, COEF>(c, eob, res);
+        if (txtp == 2) resid4_tx<0, 2, M, COEF>(c, eob, res);
+        if (txtp == 3) resid4_tx<0, 3, M, COEF>(c, eob, res);
+    }
+
+    if (RJ_INPLACE(r)) {
+        const int bd = frames[r.frame].bd;
+#pragma unroll
+        for (int y = 0; y < 4; y++) {
+            int pv[4];
+            if (PREQ) {
+#pragma unroll
+                for (int x = 0; x < 4; x++) pv[x] = pq[PREQ ? y : 0][x];
+            } else load_px4(q + y * qp, pv);
+#pragma unroll
+            for (int x = 0; x < 4; x++) pv[x] = clipbd(pv[x] + res[x * 4 + y], bd);
+            store_px4(q + y * qp, pv);
+        }
+    } else {
+        // saturate to int16 and pack two to a dword (v_cvt_pk_i16_i32)
+        typedef short short2v __attribute__((ext_vector_type(2)));
+        uint32_t w[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const short2v pk = __builtin_amdgcn_cvt_pk_i16(res[2 * k], res[2 * k + 1]);
+            w[k] = __builtin_bit_cast(uint32_t, pk);
+        }
+        uint4 *o = (uint4 *) (resid + (size_t) r.dst * 16);
+        o[0] = make_uint4(w[0], w[1], w[2], w[3]);
+        o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    }
+}
+
 template <int N, int TCODE, typename PIX, class M, typename COEF>
 __global__ __launch_bounds__(64 * RWAVES) void k_resid(const RJob *__restrict__ jobs, int njobs,
                                                        const FrameDesc *__restrict__ frames,
                                                        const COEF *__restrict__ coefs, int16_t *__restrict__ resid)
 {
-    __shared__ COEF cbs[RWAVES][RWave<N, COEF>::E];
     const int wave = threadIdx.x >> 6;
-    resid_wave<N, TCODE, PIX, M, COEF>(jobs, njobs, blockIdx.x * RWAVES + wave, threadIdx.x & 63, frames, coefs, resid,
-                                       cbs[wave]);
+    if constexpr (N == 4)   // high bit depth: no preload, it costs 16 VGPRs and two waves per SIMD here
+        resid_wave4<TCODE, PIX, M, COEF, sizeof(COEF) == 2>(jobs, njobs, blockIdx.x * RWAVES + wave, threadIdx.x & 63,
+                                                            frames, coefs, resid);
+    else {
+        __shared__ COEF cbs[RWAVES][RWave<N, COEF>::E];
+        resid_wave<N, TCODE, PIX, M, COEF>(jobs, njobs, blockIdx.x * RWAVES + wave, threadIdx.x & 63, frames, coefs,
+                                           resid, cbs[wave]);
+    }
 }
 
 // k_resid of a launch list fixed at staging (runtime "static plan"): the job range comes
 // from the planner's summary in HBM (rng = {first, end}); the grid is sized from a staged
-// bound on the range (every tx block of the coded blocks), so one wave per 64 / N jobs as
+// bound on the range (every tx block of the coded blocks), so one wave per RDevCap jobs as
 // in k_resid, the waves past the range returning at once (a strided loop here costs 15-20
 // VGPRs and measurably slower launches beside the other frame group's).
 template <int N, int TCODE, typename PIX, class M, typename COEF>
@@ -625,13 +746,17 @@ __global__ __launch_bounds__(64 * RWAVES) void k_resid_dev(const RJob *__restric
                                                            const FrameDesc *__restrict__ frames,
                                                            const COEF *__restrict__ coefs, int16_t *__restrict__ resid)
 {
-    __shared__ COEF cbs[RWAVES][RWave<N, COEF>::E];
-    constexpr int CAP = 64 / N;
+    constexpr int CAP = RDevCap<N, TCODE, COEF>::V;
     const uint32_t j0 = __builtin_amdgcn_readfirstlane(rng[0]), j1 = __builtin_amdgcn_readfirstlane(rng[1]);
     const int njobs = j1 > j0 ? (int) (j1 - j0) : 0;
     const int wave = threadIdx.x >> 6, wj = (int) blockIdx.x * RWAVES + wave;
     if (wj * CAP >= njobs) return;
-    resid_wave<N, TCODE, PIX, M, COEF, false>(jobs + j0, njobs, wj, threadIdx.x & 63, frames, coefs, resid, cbs[wave]);
+    if constexpr (RLane4<N, TCODE, COEF>::V)
+        resid_wave4<TCODE, PIX, M, COEF, false>(jobs + j0, njobs, wj, threadIdx.x & 63, frames, coefs, resid);
+    else {
+        __shared__ COEF cbs[RWAVES][RWave<N, COEF>::E];
+        resid_wave<N, TCODE, PIX, M, COEF, false>(jobs + j0, njobs, wj, threadIdx.x & 63, frames, coefs, resid, cbs[wave]);
+    }
 }
 
 // Every transform size of a phase in ONE launch (narrow, level-scheduled phases: the chain
@@ -645,7 +770,7 @@ __global__ __launch_bounds__(64 * RWAVES) void k_resid_multi(ResidMulti a, const
                                                              const COEF *__restrict__ coefs, int16_t *__restrict__ resid)
 {
     constexpr int E = RWave<32, COEF>::E > RWave<16, COEF>::E ? RWave<32, COEF>::E : RWave<16, COEF>::E;
-    static_assert(E >= RWave<8, COEF>::E && E >= RWave<4, COEF>::E, "LDS block of the largest transform");
+    static_assert(E >= RWave<8, COEF>::E, "LDS block of the largest transform (the 4x4 codes use none)");
     __shared__ COEF cbs[RWAVES][E];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t gw = blockIdx.x * RWAVES + wave;
@@ -657,11 +782,11 @@ __global__ __launch_bounds__(64 * RWAVES) void k_resid_multi(ResidMulti a, const
     const RJob *j = jobs + a.off[t];
     const int n = (int) a.n[t];
     switch (t) {
-    case 0: resid_wave<4, 0, PIX, M, COEF>(j, n, wj, lane, frames, coefs, resid, cbs[wave]); break;
+    case 0: resid_wave4<0, PIX, M, COEF>(j, n, wj, lane, frames, coefs, resid); break;
     case 1: resid_wave<8, 1, PIX, M, COEF>(j, n, wj, lane, frames, coefs, resid, cbs[wave]); break;
     case 2: resid_wave<16, 2, PIX, M, COEF>(j, n, wj, lane, frames, coefs, resid, cbs[wave]); break;
     case 3: resid_wave<32, 3, PIX, M, COEF>(j, n, wj, lane, frames, coefs, resid, cbs[wave]); break;
-    default: resid_wave<4, 4, PIX, M, COEF>(j, n, wj, lane, frames, coefs, resid, cbs[wave]); break;
+    default: resid_wave4<4, PIX, M, COEF>(j, n, wj, lane, frames, coefs, resid); break;
     }
 }
 
@@ -3155,7 +3280,7 @@ template <int N, int TC>
 static void launch_resid_n(int hb, hipStream_t st, int n, const RJob *jobs, const FrameDesc *frames,
                            const void *coefs, int16_t *resid)
 {
-    const int per = RWAVES * (64 / N);
+    const int per = RWAVES * RCap<N>::V;
     const int nb = (n + per - 1) / per;
     if (hb)
         hipLaunchKernelGGL((k_resid<N, TC, uint16_t, M64, int32_t>), dim3(nb), dim3(64 * RWAVES), 0, st,
@@ -3168,7 +3293,7 @@ template <int N, int TC>
 static void launch_resid_dev_n(int hb, hipStream_t st, int ub, const RJob *jobs, const uint32_t *rng,
                                const FrameDesc *frames, const void *coefs, int16_t *resid)
 {
-    const int per = RWAVES * (64 / N);
+    const int per = RWAVES * (hb ? RDevCap<N, TC, int32_t>::V : RDevCap<N, TC, int16_t>::V);
     const int nb = (ub + per - 1) / per;
     if (hb)
         hipLaunchKernelGGL((k_resid_dev<N, TC, uint16_t, M64, int32_t>), dim3(nb), dim3(64 * RWAVES), 0, st,
@@ -3308,6 +3433,21 @@ int vp9hip_lfr_prof_read(unsigned long long *out)
     static const unsigned long long z[16] = {0};
     return hipMemcpyToSymbol(HIP_SYMBOL(lfr_prof), z, sizeof(z)) == hipSuccess ? 0 : -1;
 }
+// The lane routine of the 4x4 residual kernels (resid4_tx) on the host, for the CPU check
+// against the oracle: n blocks of tx code `tcode` (0 or 4) and `txtp`, block i with eobs[i]
+// (1..16) live coefficients of the 16 scan-order ones at coef + 16 * i (int16, or int32 with
+// hb); res + 16 * i gets its column-major residuals before the int16 saturation.
+int vp9hip_resid4_host(int hb, int tcode, int txtp, int n, const uint8_t *eobs, const void *coef, int32_t *res)
+{
+    if ((tcode != 0 && tcode != 4) || txtp < 0 || txtp > 3 || (tcode == 4 && txtp)) return -1;
+    for (int i = 0; i < n; i++) {
+        if (eobs[i] < 1 || eobs[i] > 16) return -1;
+        int32_t (&out)[16] = *(int32_t (*)[16]) (res + 16 * (size_t) i);
+        if (hb) resid4_block<M64, int32_t>(tcode, txtp, *(const int32_t (*)[16]) ((const int32_t *) coef + 16 * (size_t) i), eobs[i], out);
+        else resid4_block<M32, int16_t>(tcode, txtp, *(const int16_t (*)[16]) ((const int16_t *) coef + 16 * (size_t) i), eobs[i], out);
+    }
+    return 0;
+}
 int vp9hip_launch_resid(int hb, hipStream_t st, int tcode, int n, const RJob *jobs, const FrameDesc *frames,
                         const void *coefs, int16_t *resid)
 {
@@ -3344,7 +3484,7 @@ int vp9hip_launch_resid_multi(int hb, hipStream_t st, const uint32_t *off, const
     a.w0[0] = 0;
     for (int t = 0; t < 5; t++) {
         a.off[t] = off[t]; a.n[t] = n[t];
-        const uint32_t per = 64 / tn[t];
+        const uint32_t per = tn[t] == 4 ? RCap<4>::V : 64 / tn[t];   // jobs per wave
         a.w0[t + 1] = a.w0[t] + (n[t] + per - 1) / per;
     }
     if (!a.w0[5]) return 0;

@@ -1428,7 +1428,7 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
     s.o_ctr = o; o = al(o + (size_t) s.n_ctr * 4);
     s.o_blocks = o; o = al(o + nb * sizeof(vp9h_block));
     s.o_eobs = o; o = al(o + ne * 2);
-    s.o_coefs = o; o = al(o + nc * in.csz + 64);
+    s.o_coefs = o; o = al(o + nc * in.csz + VP9HIP_COEF_PAD);
     const size_t up = o;
     s.o_bneob = o; o = al(o + (nb + 1) * 4);
     s.o_beob0 = o; o = al(o + (nb + 1) * 4);
@@ -2329,7 +2329,7 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
     s.o_mcs = o; o = al(o + (size_t) tot.mc * sizeof(McUnit));
     s.o_lists = o; o = al(o + s.lists.size() * sizeof(uint32_t));
     s.o_ctr = o; o = al(o + (size_t) s.n_ctr * sizeof(uint32_t));
-    s.o_coefs = o; o = al(o + coef_off[n] + 64);
+    s.o_coefs = o; o = al(o + coef_off[n] + VP9HIP_COEF_PAD);
     s.n_sbs = tot.sb; s.n_pjobs = tot.job; s.n_passes = tot.pass; s.n_wgs = tot.wg; s.n_rjobs = tot_rj;
     s.n_lfs = tot.lf; s.n_mcs = tot.mc;
     if (o > s.arena_cap) {

@@ -46,6 +46,11 @@ typedef struct RJob {
     uint8_t  pad;
 } RJob;
 
+/* Spare bytes after the last coefficient of a batch's coefficient arena: k_resid's 4x4
+ * path loads a block's 16 coefficients by wide loads whatever its eob is (vp9hip_kernels.hip,
+ * load_coef16), so the last blocks' loads run past the data, into this pad. */
+#define VP9HIP_COEF_PAD 64
+
 #define RJ_PLANE(j) ((j).ptx & 3)
 #define RJ_INPLACE(j) (((j).ptx >> 5) & 1)
 #define RJ_TXTP(j) ((j).ptx >> 6)
