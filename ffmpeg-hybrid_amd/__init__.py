@@ -96,7 +96,8 @@ class SynthParams(ctypes.Structure):
                 ("lossless", ctypes.c_int32), ("filter_level", ctypes.c_int32),
                 ("sharpness", ctypes.c_int32), ("bilinear", ctypes.c_int32),
                 ("coef_stress", ctypes.c_int32), ("p_zero_eob", ctypes.c_float),
-                ("p_skip", ctypes.c_float), ("seed", ctypes.c_uint64), ("seg", SegParams)]
+                ("p_skip", ctypes.c_float), ("seed", ctypes.c_uint64), ("seg", SegParams),
+                ("eob_dense", ctypes.c_int32), ("ref_mix", ctypes.c_int32), ("mv_range", ctypes.c_int32)]
 
 
 class FrameInfo(ctypes.Structure):
@@ -129,7 +130,7 @@ _lib_handle = None
 # (frame_tensors) needs torch imported before this library is loaded.
 _torch_first = False
 
-ABI_VERSION = 3                # VP9HIP_ABI_VERSION of include/vp9hip.h these bindings mirror
+ABI_VERSION = 4                # VP9HIP_ABI_VERSION of include/vp9hip.h these bindings mirror
 PIPELINE_SLOTS = 3             # VP9HIP_PIPELINE_SLOTS: batch slots the decoder / adapter rotate
 # Exported symbols of include/vp9hip.h (checked by the CPU test suite).
 ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit_frame",
@@ -165,7 +166,8 @@ def lib():
     _torch_first = "torch" in sys.modules
     L = ctypes.CDLL(LIB_PATH)
     # the struct mirrors below are the header's of this ABI version (vp9h_synth_params and
-    # vp9h_enc_params grew in version 2, vp9h_frame_info and vp9hip_decoded_frame in 3): a
+    # vp9h_enc_params grew in version 2, vp9h_frame_info and vp9hip_decoded_frame in 3,
+    # vp9h_synth_params again in 4): a
     # library built from another header is refused
     if L.vp9hip_abi_version() != ABI_VERSION:
         raise Vp9HipUnavailable("libvp9hip.so ABI version %d, these bindings need %d: rebuild it (%s)"
@@ -278,6 +280,7 @@ def lib():
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_void_p]
     L.vp9hip_resid4_host.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
+    L.vp9hip_residn_host.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
     _lib_handle = L
     return L
 
@@ -342,6 +345,29 @@ def resid4_host(bpp, tcode, txtp, eobs, coefs):
     _check("vp9hip_resid4_host", lib().vp9hip_resid4_host(hb, tcode, txtp, n, eobs.ctypes.data, coefs.ctypes.data,
                                                           res.ctypes.data))
     return res
+
+
+def residn_host(bpp, tcode, txtp, eobs, coefs):
+    """The lane-per-column residual kernels' block routine run on the host (vp9hip_residn_host):
+    tcode 1..3 = 8x8, 16x16, 32x32 (N = 4 << tcode); coefs is (n, N * N) scan-order
+    coefficients (int16 at 8 bits, int32 above), eobs (n,) in 1..N * N; returns the (n, N * N)
+    int32 residuals, column-major (x * N + y), before the int16 saturation."""
+    hb = int(bpp > 8)
+    coefs = np.ascontiguousarray(coefs, np.int32 if hb else np.int16)
+    eobs = np.ascontiguousarray(eobs, np.uint16)
+    n = len(eobs)
+    nn = (4 << tcode) ** 2 if 1 <= tcode <= 3 else coefs.shape[1]
+    assert coefs.shape == (n, nn)
+    res = np.empty((n, nn), np.int32)
+    _check("vp9hip_residn_host", lib().vp9hip_residn_host(hb, tcode, txtp, n, eobs.ctypes.data, coefs.ctypes.data,
+                                                          res.ctypes.data))
+    return res
+
+
+def intra_txfm_type(mode):
+    """txtp (bit 0: ADST in the first pass, bit 1: in the second) the planners give a luma
+    intra block of `mode` below 32x32 (vp9hip_intra_txfm_type)."""
+    return _check("vp9hip_intra_txfm_type", lib().vp9hip_intra_txfm_type(int(mode)))
 
 
 def synth_params(width, height, bpp=8, **kw):

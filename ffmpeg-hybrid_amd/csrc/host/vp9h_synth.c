@@ -64,6 +64,23 @@ static int coef_mag(Gen *g)
     return m;
 }
 
+/* eob_dense, a 16x16 or 32x32 block (N = 4 << tx, n = N * N): the whole block and one short
+ * of it, the last coefficient of the residual kernels' first scatter round (8N per round) and
+ * the first of the second, the first past the default draw, anything, or the default draw */
+static int dense_eob(Gen *g, int tx)
+{
+    const int N = 4 << tx, n = N * N;
+    switch (rng_int(&g->rng, 8)) {
+    case 0: return n;
+    case 1: return n - 1;
+    case 2: return 8 * N;
+    case 3: return 8 * N + 1;
+    case 4: return 65;
+    case 5: case 6: return 1 + rng_int(&g->rng, n);
+    default: return 1 + rng_int(&g->rng, 64);
+    }
+}
+
 /* one tx block: eob + coefficients in scan order */
 static void gen_txb(Gen *g, int tx, int uv)
 {
@@ -71,6 +88,7 @@ static void gen_txb(Gen *g, int tx, int uv)
     int n = 16 << (2 * tx), i, eob;
     int hb = p->bpp > 8;
     if (rng_f(&g->rng) < p->p_zero_eob) eob = 0;
+    else if (p->eob_dense && n > 64) eob = dense_eob(g, tx);
     else eob = 1 + rng_int(&g->rng, MIN(n, 64));
     g->eobs = grow(g->eobs, &g->ce, g->ne + 1, 2, &g->err);
     if (g->err) return;
@@ -129,8 +147,11 @@ static void gen_block(Gen *g, int row, int col, int bl, int bp)
         b.uvmode = rng_int(&g->rng, 10);
     } else {
         int nref = 1 + (p->compound && rng_f(&g->rng) < 0.3);
+        const int mvr = p->mv_range > 0 ? p->mv_range : 512;
         b.comp = nref == 2;
-        b.ref[0] = 0;
+        /* ref_mix: any reference alone; compound LAST or GOLDEN with ALTREF, the pairs sign
+         * bias (0, 0, 1) codes (ALTREF the fixed reference, LAST / GOLDEN the variable one) */
+        b.ref[0] = p->ref_mix ? rng_int(&g->rng, nref == 2 ? 2 : 3) : 0;
         b.ref[1] = 2;
         b.filter = p->bilinear ? VP9H_FILTER_BILINEAR : rng_int(&g->rng, 3);
         for (i = 0; i < 4; i++) {
@@ -139,8 +160,8 @@ static void gen_block(Gen *g, int row, int col, int bl, int bp)
             for (k = 0; k < 2; k++) {
                 if (m == VP9H_ZEROMV) { b.mv[i][k][0] = b.mv[i][k][1] = 0; }
                 else {
-                    b.mv[i][k][0] = rng_int(&g->rng, 1025) - 512;
-                    b.mv[i][k][1] = rng_int(&g->rng, 1025) - 512;
+                    b.mv[i][k][0] = rng_int(&g->rng, 2 * mvr + 1) - mvr;
+                    b.mv[i][k][1] = rng_int(&g->rng, 2 * mvr + 1) - mvr;
                 }
             }
         }
@@ -242,7 +263,7 @@ int vp9hip_synth_frame(vp9h_frame *out, const vp9h_synth_params *p)
     int row, col, tc, i, s;
     int bidx = p->bpp == 8 ? 0 : p->bpp == 10 ? 1 : 2;
     if (!out || !p || p->width <= 0 || p->height <= 0 ||
-        (p->bpp != 8 && p->bpp != 10 && p->bpp != 12))
+        (p->bpp != 8 && p->bpp != 10 && p->bpp != 12) || p->mv_range < 0 || p->mv_range > 16383)
         return VP9HIP_EINVAL;
     memset(&g, 0, sizeof(g));
     memset(out, 0, sizeof(*out));

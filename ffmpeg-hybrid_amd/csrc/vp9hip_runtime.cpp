@@ -41,6 +41,7 @@
 #include "vp9hip_planlogic.h"
 #include "vp9hip_plan.h"
 #include "vp9hip_convert.h"
+#include "vp9hip_residn.h"
 
 extern "C" {
 int vp9hip_launch_resid_multi(int hb, hipStream_t st, const uint32_t *off, const uint32_t *n, const RJob *jobs,
@@ -3050,6 +3051,91 @@ extern "C" int vp9hip_set_graph(vp9hip_ctx *c, int on)
 }
 
 extern "C" int vp9hip_abi_version(void) { return VP9HIP_ABI_VERSION; }
+
+// resid_wave (vp9hip_kernels.hip) of one N x N block on the host, pass for pass, with the same
+// 1-D transforms (vp9hip_residn.h): zero the nzr rows of the bounding box, scatter eob scan-
+// order coefficients, column pass over the columns li < nzc reading the rows k < nzr, row pass
+// reading k < nzc, or the DC-only shortcut; then the rounding shift. What the kernel leaves
+// unwritten (LDS rows from nzr on, rows of the transposed block from nzc on) is poisoned here,
+// so a pass that read it would show. res[x * N + y], column-major, before the int16 saturation.
+namespace {
+template <int N, class M, typename COEF>
+void residn_block(int txtp, int eob, int nzc, int nzr, const int16_t *scan, const COEF *src, int32_t *res)
+{
+    typedef typename M::T T;
+    constexpr int BITS = N == 8 ? 5 : 6;
+    if (eob == 1 && txtp == 0) {
+        // DC-only shortcut (vp9dsp_template.c:1165-1178)
+        const T t1 = M::r14(M::in((int32_t) src[0]) * (T) 11585);
+        const int32_t tdc = (int32_t) M::r14(t1 * (T) 11585);
+        const int32_t add = (int32_t) ((uint32_t) tdc + (1u << (BITS - 1))) >> BITS;
+        for (int k = 0; k < N * N; k++) res[k] = add;
+        return;
+    }
+    COEF cb[N * N], tr[N * N];
+    for (int k = 0; k < N * N; k++) cb[k] = tr[k] = (COEF) 0x5a5a;
+    for (int k = 0; k < nzr; k++)
+        for (int li = 0; li < N; li++) cb[k * N + li] = 0;
+    for (int k0 = 0; k0 < eob; k0 += 8 * N)
+        for (int u = 0; u < 8; u++)
+            for (int li = 0; li < N; li++) {
+                const int k = k0 + li + u * N;
+                if (k < eob) cb[scan[k]] = src[k];
+            }
+    T v[N];
+    // column pass (type_a): column li < nzc into row li
+    for (int li = 0; li < nzc; li++) {
+        for (int k = 0; k < N; k++) v[k] = k < nzr ? M::in(cb[k * N + li]) : (T) 0;
+        tx1n<N, M>(v, txtp & 1);
+        for (int k = 0; k < N; k++) tr[li * N + k] = (COEF) (int64_t) v[k];
+    }
+    // row pass (type_b): column li of the transposed block
+    for (int li = 0; li < N; li++) {
+        for (int k = 0; k < N; k++) v[k] = k < nzc ? M::in(tr[k * N + li]) : (T) 0;
+        tx1n<N, M>(v, txtp >> 1);
+        for (int k = 0; k < N; k++) {
+            const int32_t ov = (COEF) (int64_t) v[k];
+            res[li * N + k] = (int32_t) ((uint32_t) ov + (1u << (BITS - 1))) >> BITS;
+        }
+    }
+}
+template <int N> int residn_blocks(int hb, int tcode, int txtp, int n, const uint16_t *eobs, const void *coef, int32_t *res)
+{
+    static const int16_t *const scans[3][4] = {
+        { vp9t_scan_default_8x8, vp9t_scan_col_8x8, vp9t_scan_row_8x8, vp9t_scan_default_8x8 },
+        { vp9t_scan_default_16x16, vp9t_scan_col_16x16, vp9t_scan_row_16x16, vp9t_scan_default_16x16 },
+        { vp9t_scan_default_32x32, vp9t_scan_default_32x32, vp9t_scan_default_32x32, vp9t_scan_default_32x32 },
+    };
+    const int16_t *scan = scans[tcode - 1][txtp];
+    for (int i = 0; i < n; i++) {
+        const int e = eobs[i];
+        if (e < 1 || e > N * N) return -1;
+        const int nzc = g_nz[tcode][txtp][e][0], nzr = g_nz[tcode][txtp][e][1];
+        const size_t o = (size_t) i * N * N;
+        if (hb) residn_block<N, M64, int32_t>(txtp, e, nzc, nzr, scan, (const int32_t *) coef + o, res + o);
+        else residn_block<N, M32, int16_t>(txtp, e, nzc, nzr, scan, (const int16_t *) coef + o, res + o);
+    }
+    return 0;
+}
+}
+
+// The planners' transform type of a luma intra block of `mode` (pl_intra_txfm_type), for tests
+// that sort a packet's tx blocks by it; -1 for no intra mode.
+extern "C" int vp9hip_intra_txfm_type(int mode) { return mode < 0 || mode > 9 ? -1 : pl_intra_txfm_type(mode); }
+
+// The lane-per-column residual kernels' block routine on the host, for the CPU check against
+// the oracle: n blocks of tx code `tcode` (1..3: 8x8, 16x16, 32x32) and `txtp` (0 for 32x32),
+// block i with eobs[i] (1..N * N) live coefficients of the N * N scan-order ones at
+// coef + N * N * i (int16, or int32 with hb); res + N * N * i gets its column-major residuals
+// before the int16 saturation. nzc / nzr come from init_nz's table, as the planners' do.
+extern "C" int vp9hip_residn_host(int hb, int tcode, int txtp, int n, const uint16_t *eobs, const void *coef, int32_t *res)
+{
+    if (tcode < 1 || tcode > 3 || txtp < 0 || txtp > 3 || (tcode == 3 && txtp) || n < 0) return -1;
+    init_nz();
+    return tcode == 1 ? residn_blocks<8>(hb, tcode, txtp, n, eobs, coef, res)
+         : tcode == 2 ? residn_blocks<16>(hb, tcode, txtp, n, eobs, coef, res)
+         : residn_blocks<32>(hb, tcode, txtp, n, eobs, coef, res);
+}
 
 extern "C" int vp9hip_device_info(int device, char *pci_bus_id, int len, char *name, int name_len)
 {

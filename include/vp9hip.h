@@ -37,7 +37,8 @@ extern "C" {
  * vp9h_stream_set_color and the output conversion (vp9hip_out_desc, vp9hip_convert_frames,
  * vp9hip_decoder_convert) added. vp9hip_convert_frames_scaled / vp9hip_decoder_convert_scaled
  * came later as new symbols only: no struct changed, so the version stayed. */
-#define VP9HIP_ABI_VERSION 3
+/* 4: vp9h_synth_params ends in eob_dense / ref_mix / mv_range. */
+#define VP9HIP_ABI_VERSION 4
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
 #define VP9HIP_EINVAL       (-22)          /* AVERROR(EINVAL)   */
@@ -375,10 +376,13 @@ int  vp9hip_device_info(int device, char *pci_bus_id, int len, char *name, int n
  * Generates a pseudo-random but structurally legal frame packet. Defaults follow the
  * stream settings of SURVEY.md §8(d): random partitions (P(split) 0.5 at 64/32, 0.3
  * at 16, 10 % sub-8x8), uniform intra modes, skip 0.2, TX_MODE_SELECT, per tx block
- * eob uniform in [1, min(n,64)] with geometric(0.6) magnitudes and random sign,
+ * eob uniform in [1, min(n,64)] (eob_dense: 16x16 and 32x32 blocks up to all n
+ * coefficients) with geometric(0.6) magnitudes and random sign,
  * base_q_idx 60 (no deltas), filter level 36, sharpness 0, LF deltas at the libvpx
- * defaults. inter != 0: LAST-ref inter frame (50 % NEWMV, MVs uniform in +-64 px,
- * 10 % intra blocks). The packet owns heap arrays; release with vp9hip_synth_free.
+ * defaults. inter != 0: an inter frame whose single-reference blocks read LAST and whose
+ * compound blocks read LAST + ALTREF (ref_mix: every reference, see below), 50 % NEWMV,
+ * MVs uniform in +-64 px (mv_range: another range), 10 % intra blocks. The packet owns
+ * heap arrays; release with vp9hip_synth_free.
  */
 /* Segmentation and loop-filter deltas of a frame (vp9.c:692-765, vp9block.c:101-141): what
  * vp9h_stream_encode writes into the frame header, and what vp9hip_synth_frame assumes for
@@ -404,7 +408,7 @@ typedef struct vp9h_synth_params {
     int32_t  bpp;              /* 8 / 10 / 12                                   */
     int32_t  ss_h, ss_v;       /* 1,1 = 4:2:0                                   */
     int32_t  log2_tile_cols;
-    int32_t  inter;            /* 0 = keyframe; 1 = inter frame on LAST         */
+    int32_t  inter;            /* 0 = keyframe; 1 = inter frame (see ref_mix)   */
     int32_t  compound;         /* inter: allow compound LAST+ALTREF blocks      */
     int32_t  q_idx;            /* base_q_idx (0 + lossless -> WHT)              */
     int32_t  lossless;
@@ -416,6 +420,15 @@ typedef struct vp9h_synth_params {
     float    p_skip;           /* default 0.2                                   */
     uint64_t seed;
     vp9h_seg_params seg;       /* segmentation / LF deltas (default: none)      */
+    /* ABI version 4; all zero = the draws above, packet for packet                 */
+    int32_t  eob_dense;        /* 1: a tx block of n = N * N > 64 coefficients draws its
+                                * eob from n, n - 1, 8N, 8N + 1, 65, uniform in [1, n]
+                                * (twice as likely) and the default draw            */
+    int32_t  ref_mix;          /* 1: single-reference blocks read LAST, GOLDEN or ALTREF,
+                                * compound ones LAST or GOLDEN with ALTREF (codable
+                                * under sign bias 0, 0, 1)                           */
+    int32_t  mv_range;         /* nonzero MVs uniform in +-mv_range 1/8 pel, at most
+                                * 16383 (0: 512)                                    */
 } vp9h_synth_params;
 
 /* Fill p with the §8(d) defaults for a w x h bpp stream. */

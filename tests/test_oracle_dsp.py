@@ -283,3 +283,46 @@ def test_mc_scaled_constant_and_step():
     d = np.zeros((64, 64), np.uint8)
     orc.mc_scaled(8, d, src, 8 * 160 + 8, 160, 16, 16, 0, 0, 32, 32, 1, 0)
     assert np.array_equal(d[:16, :16], src[8:40:2, 8:40:2])
+
+
+@pytest.mark.parametrize("tx,txtp", [(t, p) for t in range(4) for p in range(4) if t < 3 or p == 0])
+def test_itxfm_high_bit_depth_equals_8bit_where_nothing_wraps(orc, tx, txtp):
+    """The 10- and 12-bit transforms (int64 arithmetic, int32 storage) are the 8-bit ones
+    (wrapping 32-bit arithmetic, int16 storage) wherever the 8-bit path neither wraps nor
+    truncates: then both compute the same integers. That ties the 16-bit path to the 8-bit one,
+    which the checkasm float round trip above pins. Full-density blocks, |coefficient| <= A.
+
+    The bound A = min(2^14 / N^2, 256) (256, 256, 64, 16 for N = 4 .. 32); 2^14 / N^2 from the
+    transform gains, 256 so that the 8-bit result stays off the clip (asserted below: with
+    coefficients uniform in +-A a residual's deviation is A / sqrt 3 * (N / 2) >> bits, 18 at
+    N = 4 and 8, against the 127 there is room for):
+    every level of a 1-D flow graph is a set of plane rotations (cos^2 + sin^2 = 2^28 before
+    the 14-bit rounding shift, or (a +- b) * 11585 = a rotation by 45 degrees: norm kept) or
+    of butterflies a +- b (norm times sqrt 2), and idct32 / iadst16, the longest, have four
+    butterfly levels, log2 N or fewer each: a pass multiplies the Euclidean norm of a column
+    by at most sqrt N, and no value inside it exceeds that norm. Columns enter pass one with
+    norm <= sqrt(N) A, so its values stay <= N A; pass two sees columns of norm <= sqrt(N) N A
+    and its values and outputs stay <= N^2 A = 2^14. The widest 32-bit expression, the sum of
+    two rotations' raw products before the shift (the ADSTs), is <= sqrt 2 * 2^14 * norm
+    <= 1.42 * 2^28 < 2^31; what is stored between and after the passes is <= 2^14 < 2^15.
+    Each rounding shift is off by at most 1/2 per value, at most six per pass and amplified by
+    at most N per pass: < 3 N (1 + N) = 3168 in all, far inside both margins.
+
+    The oracle returns clip(pred + r) only: a result pixel strictly between 0 and the maximum
+    was not clipped, which is asserted, so r = pixel - pred at every depth."""
+    N = 4 << tx
+    A = min((1 << 14) // (N * N), 256)
+    rng = np.random.default_rng(0xb2 + tx * 4 + txtp)
+    blocks = [rng.integers(-A, A + 1, N * N) for _ in range(6)] + [rng.choice([-A, A], N * N) for _ in range(3)]
+    blocks.append(np.where(rng.random(N * N) < 0.5, 0, rng.integers(-A, A + 1, N * N)))
+    for c in blocks:
+        res = {}
+        for bpp in (8, 10, 12):
+            pred = 1 << (bpp - 1)
+            d = np.full((N, N), pred, _dt(bpp))
+            coef = c.astype(np.int16 if bpp == 8 else np.int32)
+            orc.itxfm_add(bpp, d, coef, N * N, tx, txtp)
+            assert d.min() > 0 and d.max() < (1 << bpp) - 1, "clipped: shrink the block, not the check"
+            res[bpp] = d.astype(np.int64) - pred
+        assert np.abs(res[8]).max() > 0
+        assert np.array_equal(res[10], res[8]) and np.array_equal(res[12], res[8]), (tx, txtp)

@@ -391,3 +391,50 @@ def test_header_peek_matches_the_parse(v9):
                     assert list(peek.ref_slot) == list(info.ref_slot)
                     assert list(peek.sign_bias) == list(info.sign_bias)
     assert types == {0, 1, 2, 3}
+
+
+@pytest.mark.parametrize("bpp", [8, 10])
+def test_dense_coefficients_every_reference_and_far_mvs_round_trip(v9, bpp):
+    """The generator's coverage switches through the bitstream writer and parser: a key + 2
+    inter stream at 136x72 with eob_dense (16x16 and 32x32 blocks up to all their coefficients:
+    the coefficient contexts and band offsets of scan positions >= 64), ref_mix (single-
+    reference blocks on LAST, GOLDEN and ALTREF, compound ones LAST or GOLDEN with ALTREF,
+    under sign bias (0, 0, 1) and three distinct slots) and MVs of +-500 px (differences up to
+    MV class 9). Parsed with 1 and with 2 tile-column threads; the parsed packets equal the
+    coded ones field for field, and the coded ones carry the generated blocks, eobs and
+    coefficients."""
+    w, h = 136, 72
+    # seed 0xd07: the first from 0xd00 on whose three frames hold the eobs asserted below
+    frames = [v9.SynthFrame(v9.synth_params(w, h, bpp, seed=0xd07, eob_dense=1))]
+    frames += [v9.SynthFrame(v9.synth_params(w, h, bpp, seed=0xd08 + i, inter=1, compound=1, eob_dense=1,
+                                             ref_mix=1, mv_range=4000)) for i in range(2)]
+    enc = v9.Stream()
+    per = [{}, dict(ref_slot=(0, 1, 2), sign_bias=(0, 0, 1), refresh_mask=1 << 1),
+           dict(ref_slot=(1, 0, 2), sign_bias=(0, 0, 1), refresh_mask=1 << 2)]
+    datas, coded = zip(*[enc.encode(f, **kw) for f, kw in zip(frames, per)])
+    stats = {"kept": 0, "to_new": 0}
+    import synth_walk
+    hist = synth_walk.eob_histogram([f.pkt for f in frames])
+    for k in ((2, 256), (2, 255), (2, 128), (2, 129), (3, 1024), (3, 1023), (3, 256), (3, 257)):
+        assert hist[k] > 0, k
+    for f, c in zip(frames, coded):
+        check_legalized(f.pkt, c.pkt, stats)
+        eo, co = _arrays(f.pkt)
+        ec, cc = _arrays(c.pkt)
+        assert np.array_equal(eo, ec) and co == cc            # every eob and coefficient as generated
+    assert stats["kept"] + stats["to_new"] > 0
+    single, comp, far = set(), set(), 0
+    for c in coded[1:]:
+        for b in _blocks(c.pkt):
+            if b.intra:
+                continue
+            (comp if b.comp else single).add((b.ref[0], b.ref[1]) if b.comp else b.ref[0])
+            far += max(abs(x) for x in b.mv) > 2048
+    assert single == {0, 1, 2} and comp == {(0, 2), (1, 2)} and far > 10
+    for threads in (1, 2):
+        dec = v9.Stream(threads=threads)
+        for d, c, kw in zip(datas, coded, per):
+            p, info = dec.decode(d)
+            same_packet(p.pkt, c.pkt)
+            if kw:
+                assert list(info.ref_slot) == list(kw["ref_slot"]) and list(info.sign_bias) == [0, 0, 1]
