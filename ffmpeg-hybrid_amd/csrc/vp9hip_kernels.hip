@@ -141,35 +141,98 @@ static_assert(scan4_same(vp9t_scan_default_4x4, 0, 0) && scan4_same(vp9t_scan_de
               scan4_same(vp9t_scan_default_4x4, 4, 0) && scan4_same(vp9t_scan_col_4x4, 0, 1) &&
               scan4_same(vp9t_scan_row_4x4, 0, 2), "resid4_scan differs from vp9_tables.h");
 
-DEV const int16_t *scan_for(int tcode, int txtp)
-{
-    const int ts = tcode & 3;
-    if (tcode == 4) return vp9t_scan_default_4x4;                 // lossless (vp9data.c:600-618)
-    return ts == 0 ? (txtp == 1 ? vp9t_scan_col_4x4 : txtp == 2 ? vp9t_scan_row_4x4 : vp9t_scan_default_4x4)
-         : ts == 1 ? (txtp == 1 ? vp9t_scan_col_8x8 : txtp == 2 ? vp9t_scan_row_8x8 : vp9t_scan_default_8x8)
-         : ts == 2 ? (txtp == 1 ? vp9t_scan_col_16x16 : txtp == 2 ? vp9t_scan_row_16x16 : vp9t_scan_default_16x16)
-         : vp9t_scan_default_32x32;
-}
-
+// one column of residuals to the scratch: saturated to int16 and packed two to a dword
+// (v_cvt_pk_i16_i32)
 template <int N> DEV void store_col(int16_t *dst, const int (&r)[N])
 {
+    typedef short short2v __attribute__((ext_vector_type(2)));
     uint32_t w[N / 2];
 #pragma unroll
-    for (int k = 0; k < N / 2; k++) w[k] = ((uint32_t) r[2 * k] & 0xffff) | ((uint32_t) r[2 * k + 1] << 16);
+    for (int k = 0; k < N / 2; k++) w[k] = __builtin_bit_cast(uint32_t, (short2v) __builtin_amdgcn_cvt_pk_i16(r[2 * k], r[2 * k + 1]));
     if (N == 4) *(uint2 *) dst = make_uint2(w[0], w[1]);
     else
 #pragma unroll
         for (int k = 0; k < N / 8; k++) ((uint4 *) dst)[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
 }
 
-// LDS row stride (coefficients) of an N x N block: padded so that the transposed store
-// (lane li writes row li) spreads over the banks: an odd number of dwords per row
-template <int N, typename COEF> struct RStride { static constexpr int S = N + (sizeof(COEF) == 2 ? 2 : 1); };
+// LDS row stride of an N x N block: RStride (vp9hip_residn.h)
 // LDS coefficients of one residual wave: 64 / N blocks of N rows
 template <int N, typename COEF> struct RWave { static constexpr int E = (64 / N) * N * RStride<N, COEF>::S; };
 
+// Where scan-order coefficient k of an N x N block goes in its LDS image: the byte offsets
+// rn_lds_off (vp9hip_residn.h) of the scans of vp9_tables.h, row padding folded in, one table
+// per scan (0 default, also txtp 3 and the WHT; 1 by columns; 2 by rows; 32x32 has the default
+// one only) and coefficient type. A lane of the gather reads its eight in one 16-byte load.
+template <int N, typename COEF> struct RScanTab { alignas(16) uint16_t v[N == 32 ? 1 : 3][N * N]; };
+template <int N> constexpr int rscan_pos(int t, int k)
+{
+    if constexpr (N == 4) return t == 1 ? vp9t_scan_col_4x4[k] : t == 2 ? vp9t_scan_row_4x4[k] : vp9t_scan_default_4x4[k];
+    else if constexpr (N == 8) return t == 1 ? vp9t_scan_col_8x8[k] : t == 2 ? vp9t_scan_row_8x8[k] : vp9t_scan_default_8x8[k];
+    else if constexpr (N == 16) return t == 1 ? vp9t_scan_col_16x16[k] : t == 2 ? vp9t_scan_row_16x16[k] : vp9t_scan_default_16x16[k];
+    else return vp9t_scan_default_32x32[k];
+}
+template <int N, typename COEF> constexpr RScanTab<N, COEF> rscan_make()
+{
+    RScanTab<N, COEF> t{};
+    for (int s = 0; s < (N == 32 ? 1 : 3); s++)
+        for (int k = 0; k < N * N; k++)
+            t.v[s][k] = (uint16_t) rn_lds_off<N, RStride<N, COEF>::S, (int) sizeof(COEF)>(rscan_pos<N>(s, k));
+    return t;
+}
+// every entry, taken apart again, is the scan position of vp9_tables.h
+template <int N, typename COEF> constexpr bool rscan_same(const RScanTab<N, COEF> &t)
+{
+    constexpr int S = RStride<N, COEF>::S, ESZ = (int) sizeof(COEF);
+    for (int s = 0; s < (N == 32 ? 1 : 3); s++)
+        for (int k = 0; k < N * N; k++) {
+            const int e = t.v[s][k] / ESZ;
+            if (t.v[s][k] % ESZ || e % S >= N || (e / S) * N + e % S != rscan_pos<N>(s, k)) return false;
+        }
+    return true;
+}
+template <int N, typename COEF> static __constant__ constexpr RScanTab<N, COEF> rscan_tab = rscan_make<N, COEF>();
+static_assert(rscan_same(rscan_tab<4, int16_t>) && rscan_same(rscan_tab<8, int16_t>) && rscan_same(rscan_tab<16, int16_t>) &&
+              rscan_same(rscan_tab<32, int16_t>) && rscan_same(rscan_tab<4, int32_t>) && rscan_same(rscan_tab<8, int32_t>) &&
+              rscan_same(rscan_tab<16, int32_t>) && rscan_same(rscan_tab<32, int32_t>),
+              "the gather tables differ from the scans of vp9_tables.h");
+
+// four dwords at a dword-aligned address, one load
+struct __attribute__((packed, aligned(4))) RQuad { uint32_t x, y, z, w; };
+
+// The eight scan-order coefficients at src by wide loads, whatever eob is: the caller zeroes
+// those from eob on. src is only element-aligned, so int16 coefficients come as the dword
+// window from the dword at or below src, shifted down a half word when src is odd (as
+// load_coef16 below). The loads reach RN_READ_SPAN16 / 32 bytes from src[0], which is a live
+// coefficient inside the arena; the arena ends in VP9HIP_COEF_PAD spare bytes
+// (vp9hip_runtime.cpp) and starts dword-aligned, so no load leaves it at either end.
+static_assert(RN_READ_SPAN16 - 2 <= VP9HIP_COEF_PAD && RN_READ_SPAN32 - 4 <= VP9HIP_COEF_PAD,
+              "the gather's loads past the last block stay inside the arena's pad");
+DEV void load_coef8(const int16_t *src, int16_t (&c)[8])
+{
+    const uintptr_t a = (uintptr_t) src;
+    const uint32_t sh = ((uint32_t) (a >> 1) & 1) << 4;  // funnel shift: 16 bits when src is odd
+    const uint32_t *w = (const uint32_t *) (a & ~(uintptr_t) 3);
+    const RQuad q = *(const RQuad *) w;
+    const uint32_t d[5] = { q.x, q.y, q.z, q.w, w[4] };
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t p = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);
+        c[2 * k] = (int16_t) (p & 0xffff);
+        c[2 * k + 1] = (int16_t) (p >> 16);
+    }
+}
+DEV void load_coef8(const int32_t *src, int32_t (&c)[8])
+{
+    const RQuad q0 = *(const RQuad *) src, q1 = *(const RQuad *) (src + 4);
+    c[0] = (int32_t) q0.x; c[1] = (int32_t) q0.y; c[2] = (int32_t) q0.z; c[3] = (int32_t) q0.w;
+    c[4] = (int32_t) q1.x; c[5] = (int32_t) q1.y; c[6] = (int32_t) q1.z; c[7] = (int32_t) q1.w;
+}
+
 // One wave of residual work: jobs [wj * 64/N, (wj + 1) * 64/N) of `jobs`, n lanes per
-// job; cbw = the wave's LDS block (RWave<N, COEF>::E coefficients, rows padded to S).
+// job; cbw = the wave's LDS block (RWave<N, COEF>::E coefficients, rows padded to S, dword-
+// aligned). The block is zeroed whole, the coefficients gathered into it eight scan positions
+// per lane and round, then the column pass, the transpose through the same block and the row
+// pass read every row of it: no load or store of these depends on a per-element branch.
 // PREQ: in-place jobs load their prediction pixels before the transform (the inter
 // launches); the keyframe launches (k_resid_dev) write scratch and keep their registers:
 // they run beside the other slot's k_plf chains, whose co-resident waves the extra
@@ -195,7 +258,7 @@ DEV void resid_wave(const RJob *__restrict__ jobs, int njobs, int wj, int lane, 
     if (act) r = jobs[j];
     else { r.coef = 0; r.dst = 0; r.eob = 0; r.frame = 0; r.ptx = 0; r.nzc = 1; r.nzr = 1; }
     const int eob = r.eob, txtp = TCODE == 3 || TCODE == 4 ? 0 : RJ_TXTP(r);
-    const int nzc = TCODE == 4 ? 4 : r.nzc, nzr = TCODE == 4 ? 4 : r.nzr;   // the WHT reads every row
+    const int nzc = TCODE == 4 ? 4 : r.nzc;   // columns with a coefficient (r.nzr, the rows: the passes read every row)
     const COEF *src = coefs + r.coef;
     const bool dconly = TCODE != 4 && act && eob == 1 && txtp == 0;
     const bool full = act && !dconly;
@@ -217,23 +280,36 @@ DEV void resid_wave(const RJob *__restrict__ jobs, int njobs, int wj, int lane, 
         }
     }
 
-    // zero the nonzero bounding box, then scatter scan-order coefficients
-    if (full)
-        for (int k = 0; k < nzr; k++) cb[k * S + li] = 0;
+    // zero the wave's whole LDS block, so that every cell a pass reads is defined and the passes
+    // read without a mask (dword stores: every caller's block is dword-aligned)
+    {
+        constexpr int ZW = RWave<N, COEF>::E * (int) sizeof(COEF) / 4;
+        static_assert(RWave<N, COEF>::E * sizeof(COEF) % 4 == 0, "the wave's LDS block is whole dwords");
+        uint32_t *z = (uint32_t *) cbw;
+#pragma unroll
+        for (int i = 0; i < (ZW + 63) / 64; i++)
+            if (i * 64 + 64 <= ZW || lane < ZW - i * 64) z[i * 64 + lane] = 0;
+    }
     wave_sync();
+    // gather: per round of 8 * N scan-order coefficients lane li takes the eight at kb by wide
+    // loads (load_coef8) and their LDS offsets in one load (rscan_tab); what lies at eob and
+    // beyond is the next block's and is scattered as zeros, harmless anywhere in the block
     if (full) {
-        const int16_t *scan = scan_for(TCODE, txtp);
-        for (int k0 = 0; k0 < eob; k0 += 8 * N) {
-            COEF c[8];
-            int pos[8];
+        const uint16_t *tab = rscan_tab<N, COEF>.v[N == 32 || TCODE == 4 || txtp == 3 ? 0 : txtp];
+        for (int k0 = 0; k0 < (N <= 8 ? 1 : eob); k0 += 8 * N) {
+            const int kb = k0 + 8 * li;
+            if (kb < eob) {
+                COEF c[8];
+                load_coef8(src + kb, c);
+                const uint4 pw = *(const uint4 *) (tab + kb);
+                const uint32_t po[4] = { pw.x, pw.y, pw.z, pw.w };
+                const int live = eob - kb;
 #pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int k = k0 + li + u * N;
-                if (k < eob) { c[u] = src[k]; pos[u] = scan[k]; pos[u] += (pos[u] >> LG) * (S - N); }
+                for (int u = 0; u < 8; u++) {
+                    const uint32_t off = u & 1 ? po[u >> 1] >> 16 : po[u >> 1] & 0xffff;
+                    *(COEF *) ((char *) cb + off) = u < live ? c[u] : (COEF) 0;
+                }
             }
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                if (k0 + li + u * N < eob) cb[pos[u]] = c[u];
         }
     }
     wave_sync();
@@ -251,13 +327,17 @@ DEV void resid_wave(const RJob *__restrict__ jobs, int njobs, int wj, int lane, 
         for (int k = 0; k < N; k++) res[k] = full ? (int) (COEF) v[k & 3] : 0;
     } else {
         T v[N];
-        // column pass (type_a): lane c < nzc transforms column c into row c
+        // column pass (type_a): lane c < nzc transforms column c into row c; the other lanes'
+        // columns hold no coefficient: they read zeros and write them, untransformed, as their
+        // rows, which the row pass reads like every other. Every lane loads, outside any branch
+        // (the block is valid, zeroed LDS for idle lanes too): under one the compiler loses the
+        // values' 16-bit range and the 24-bit multiplies of the transforms with it
         const bool colp = full && li < nzc;
 #pragma unroll
-        for (int k = 0; k < N; k++) v[k] = colp && k < nzr ? M::in(cb[k * S + li]) : (T) 0;
+        for (int k = 0; k < N; k++) v[k] = M::in(cb[k * S + li]);
         wave_sync();
-        if (colp) {
-            tx1n<N, M>(v, txtp & 1);
+        if (colp) tx1n<N, M>(v, txtp & 1);
+        if (full) {
 #pragma unroll
             for (int k = 0; k < N; k++) cb[li * S + k] = (COEF) (int64_t) v[k];
         }
@@ -265,7 +345,7 @@ DEV void resid_wave(const RJob *__restrict__ jobs, int njobs, int wj, int lane, 
         // row pass (type_b): lane i transforms column i of the transposed block
         if (full) {
 #pragma unroll
-            for (int k = 0; k < N; k++) v[k] = k < nzc ? M::in(cb[k * S + li]) : (T) 0;
+            for (int k = 0; k < N; k++) v[k] = M::in(cb[k * S + li]);
             tx1n<N, M>(v, txtp >> 1);
 #pragma unroll
             for (int k = 0; k < N; k++) {
@@ -292,11 +372,7 @@ DEV void resid_wave(const RJob *__restrict__ jobs, int njobs, int wj, int lane, 
             const int pv = PRE ? pq[PRE ? k : 0] : (int) q[k * qp];
             q[k * qp] = (PIX) clipbd(pv + res[k], bd);
         }
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; k++) res[k] = res[k] < -32768 ? -32768 : res[k] > 32767 ? 32767 : res[k];
-        store_col<N>(resid + (size_t) r.dst * 16 + li * N, res);
-    }
+    } else store_col<N>(resid + (size_t) r.dst * 16 + li * N, res);
 }
 
 // Jobs per wave of the residual launches (k_resid, k_resid_dev, k_resid_multi): a 4x4 block
@@ -310,9 +386,6 @@ template <int N> struct RCap { static constexpr int V = N == 4 ? 64 : 64 / N; };
 // against 36, so that one instantiation stays lane-per-column.
 template <int N, int TCODE, typename COEF> struct RLane4 { static constexpr bool V = N == 4 && (sizeof(COEF) == 2 || TCODE == 4); };
 template <int N, int TCODE, typename COEF> struct RDevCap { static constexpr int V = RLane4<N, TCODE, COEF>::V ? 64 : 64 / N; };
-
-// four dwords at a dword-aligned address, one load
-struct __attribute__((packed, aligned(4))) RQuad { uint32_t x, y, z, w; };
 
 // The 16 scan-order coefficients at src (eob of them live) by wide loads. src is only
 // element-aligned, so int16 coefficients come as the dword window from the dword at or below
@@ -450,7 +523,7 @@ __global__ __launch_bounds__(64 * RWAVES) void k_resid(const RJob *__restrict__ 
         resid_wave4<TCODE, PIX, M, COEF, sizeof(COEF) == 2>(jobs, njobs, blockIdx.x * RWAVES + wave, threadIdx.x & 63,
                                                             frames, coefs, resid);
     else {
-        __shared__ COEF cbs[RWAVES][RWave<N, COEF>::E];
+        __shared__ alignas(16) COEF cbs[RWAVES][RWave<N, COEF>::E];
         resid_wave<N, TCODE, PIX, M, COEF>(jobs, njobs, blockIdx.x * RWAVES + wave, threadIdx.x & 63, frames, coefs,
                                            resid, cbs[wave]);
     }
@@ -474,7 +547,7 @@ __global__ __launch_bounds__(64 * RWAVES) void k_resid_dev(const RJob *__restric
     if constexpr (RLane4<N, TCODE, COEF>::V)
         resid_wave4<TCODE, PIX, M, COEF, false>(jobs + j0, njobs, wj, threadIdx.x & 63, frames, coefs, resid);
     else {
-        __shared__ COEF cbs[RWAVES][RWave<N, COEF>::E];
+        __shared__ alignas(16) COEF cbs[RWAVES][RWave<N, COEF>::E];
         resid_wave<N, TCODE, PIX, M, COEF, false>(jobs + j0, njobs, wj, threadIdx.x & 63, frames, coefs, resid, cbs[wave]);
     }
 }
@@ -491,7 +564,7 @@ __global__ __launch_bounds__(64 * RWAVES) void k_resid_multi(ResidMulti a, const
 {
     constexpr int E = RWave<32, COEF>::E > RWave<16, COEF>::E ? RWave<32, COEF>::E : RWave<16, COEF>::E;
     static_assert(E >= RWave<8, COEF>::E, "LDS block of the largest transform (the 4x4 codes use none)");
-    __shared__ COEF cbs[RWAVES][E];
+    __shared__ alignas(16) COEF cbs[RWAVES][E];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t gw = blockIdx.x * RWAVES + wave;
     if (gw >= a.w0[5]) return;

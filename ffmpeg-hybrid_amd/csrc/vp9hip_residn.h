@@ -297,4 +297,22 @@ template <int N, class M> R4_HD void tx1n(typename M::T *v, int adst)
     else if (N == 16) { if (adst) iadst16<M>(v); else idct16<M>(v); }
     else idct32<M>(v);
 }
+
+/* LDS row stride (coefficients) of an N x N block: padded so that the transposed store
+ * (lane li writes row li) spreads over the banks: an odd number of dwords per row */
+template <int N, typename COEF> struct RStride { static constexpr int S = N + (sizeof(COEF) == 2 ? 2 : 1); };
+
+/* The coefficient block of resid_wave in LDS: N rows of S = RStride coefficients of ESZ bytes.
+ * Byte offset in that image of the raster position pos = row * N + col that a scan table of
+ * vp9_tables.h gives: what the kernels' gather tables hold, and what the host restatement
+ * scatters by. */
+template <int N, int S, int ESZ> R4_HD constexpr int rn_lds_off(int pos) { return ((pos / N) * S + pos % N) * ESZ; }
+
+/* The gather of resid_wave: per round of 8 * N scan-order coefficients, lane li of a block takes
+ * the eight at kb = k0 + 8 * li by wide loads, whatever eob is, as long as kb < eob. The loads
+ * reach at most this many bytes from coefficient kb (int16: five dwords from the dword at or
+ * below it; int32: two 16-byte loads), so past the last live coefficient of the arena they stay
+ * inside its VP9HIP_COEF_PAD spare bytes. */
+#define RN_READ_SPAN16 20
+#define RN_READ_SPAN32 32
 #endif

@@ -3053,17 +3053,24 @@ extern "C" int vp9hip_set_graph(vp9hip_ctx *c, int on)
 extern "C" int vp9hip_abi_version(void) { return VP9HIP_ABI_VERSION; }
 
 // resid_wave (vp9hip_kernels.hip) of one N x N block on the host, pass for pass, with the same
-// 1-D transforms (vp9hip_residn.h): zero the nzr rows of the bounding box, scatter eob scan-
-// order coefficients, column pass over the columns li < nzc reading the rows k < nzr, row pass
-// reading k < nzc, or the DC-only shortcut; then the rounding shift. What the kernel leaves
-// unwritten (LDS rows from nzr on, rows of the transposed block from nzc on) is poisoned here,
-// so a pass that read it would show. res[x * N + y], column-major, before the int16 saturation.
+// 1-D transforms and LDS image (vp9hip_residn.h: N rows of RStride coefficients, rn_lds_off):
+//   - the whole image zeroed, pad cells included: the kernel leaves no cell undefined any more,
+//     so there is none to poison here;
+//   - the gather: per round of 8 * N scan-order coefficients, lane li takes the eight at
+//     kb = k0 + 8 * li, skips the round at kb >= eob, and scatters those from eob on, which
+//     are the next block's, as zeros;
+//   - the column pass: every lane reads its column, the lanes li < nzc transform it, every
+//     lane writes its row of the transposed block;
+//   - the row pass over every row, or the DC-only shortcut; then the rounding shift.
+// src holds the N * N scan-order coefficients the caller handed in, so the gather's reads past
+// eob stay inside it. res[x * N + y], column-major, before the int16 saturation.
 namespace {
 template <int N, class M, typename COEF>
-void residn_block(int txtp, int eob, int nzc, int nzr, const int16_t *scan, const COEF *src, int32_t *res)
+void residn_block(int txtp, int eob, int nzc, const int16_t *scan, const COEF *src, int32_t *res)
 {
     typedef typename M::T T;
     constexpr int BITS = N == 8 ? 5 : 6;
+    constexpr int S = RStride<N, COEF>::S, ESZ = (int) sizeof(COEF);
     if (eob == 1 && txtp == 0) {
         // DC-only shortcut (vp9dsp_template.c:1165-1178)
         const T t1 = M::r14(M::in((int32_t) src[0]) * (T) 11585);
@@ -3072,29 +3079,30 @@ void residn_block(int txtp, int eob, int nzc, int nzr, const int16_t *scan, cons
         for (int k = 0; k < N * N; k++) res[k] = add;
         return;
     }
-    COEF cb[N * N], tr[N * N];
-    for (int k = 0; k < N * N; k++) cb[k] = tr[k] = (COEF) 0x5a5a;
-    for (int k = 0; k < nzr; k++)
-        for (int li = 0; li < N; li++) cb[k * N + li] = 0;
+    COEF cb[N * S];
+    for (int k = 0; k < N * S; k++) cb[k] = 0;
     for (int k0 = 0; k0 < eob; k0 += 8 * N)
-        for (int u = 0; u < 8; u++)
-            for (int li = 0; li < N; li++) {
-                const int k = k0 + li + u * N;
-                if (k < eob) cb[scan[k]] = src[k];
-            }
-    T v[N];
-    // column pass (type_a): column li < nzc into row li
-    for (int li = 0; li < nzc; li++) {
-        for (int k = 0; k < N; k++) v[k] = k < nzr ? M::in(cb[k * N + li]) : (T) 0;
-        tx1n<N, M>(v, txtp & 1);
-        for (int k = 0; k < N; k++) tr[li * N + k] = (COEF) (int64_t) v[k];
+        for (int li = 0; li < N; li++) {
+            const int kb = k0 + 8 * li;
+            if (kb >= eob) continue;
+            for (int u = 0; u < 8; u++)
+                cb[rn_lds_off<N, S, ESZ>(scan[kb + u]) / ESZ] = u < eob - kb ? src[kb + u] : (COEF) 0;
+        }
+    T v[N][N];
+    // column pass (type_a): column li into row li, transformed by the lanes li < nzc
+    for (int li = 0; li < N; li++) {
+        for (int k = 0; k < N; k++) v[li][k] = M::in(cb[k * S + li]);
+        if (li < nzc) tx1n<N, M>(v[li], txtp & 1);
     }
+    for (int li = 0; li < N; li++)
+        for (int k = 0; k < N; k++) cb[li * S + k] = (COEF) (int64_t) v[li][k];
     // row pass (type_b): column li of the transposed block
     for (int li = 0; li < N; li++) {
-        for (int k = 0; k < N; k++) v[k] = k < nzc ? M::in(tr[k * N + li]) : (T) 0;
-        tx1n<N, M>(v, txtp >> 1);
+        T w[N];
+        for (int k = 0; k < N; k++) w[k] = M::in(cb[k * S + li]);
+        tx1n<N, M>(w, txtp >> 1);
         for (int k = 0; k < N; k++) {
-            const int32_t ov = (COEF) (int64_t) v[k];
+            const int32_t ov = (COEF) (int64_t) w[k];
             res[li * N + k] = (int32_t) ((uint32_t) ov + (1u << (BITS - 1))) >> BITS;
         }
     }
@@ -3110,10 +3118,10 @@ template <int N> int residn_blocks(int hb, int tcode, int txtp, int n, const uin
     for (int i = 0; i < n; i++) {
         const int e = eobs[i];
         if (e < 1 || e > N * N) return -1;
-        const int nzc = g_nz[tcode][txtp][e][0], nzr = g_nz[tcode][txtp][e][1];
+        const int nzc = g_nz[tcode][txtp][e][0];
         const size_t o = (size_t) i * N * N;
-        if (hb) residn_block<N, M64, int32_t>(txtp, e, nzc, nzr, scan, (const int32_t *) coef + o, res + o);
-        else residn_block<N, M32, int16_t>(txtp, e, nzc, nzr, scan, (const int16_t *) coef + o, res + o);
+        if (hb) residn_block<N, M64, int32_t>(txtp, e, nzc, scan, (const int32_t *) coef + o, res + o);
+        else residn_block<N, M32, int16_t>(txtp, e, nzc, scan, (const int16_t *) coef + o, res + o);
     }
     return 0;
 }
