@@ -10,6 +10,7 @@ the VP9 decoder's frame loop vp9.c:1606-1863) at the pass-1 packet level.
 There is no CPU fallback: if the HIP library cannot be loaded, every entry point
 raises :class:`Vp9HipUnavailable`.
 """
+import collections
 import ctypes
 import os
 import sys
@@ -97,7 +98,8 @@ class SynthParams(ctypes.Structure):
                 ("sharpness", ctypes.c_int32), ("bilinear", ctypes.c_int32),
                 ("coef_stress", ctypes.c_int32), ("p_zero_eob", ctypes.c_float),
                 ("p_skip", ctypes.c_float), ("seed", ctypes.c_uint64), ("seg", SegParams),
-                ("eob_dense", ctypes.c_int32), ("ref_mix", ctypes.c_int32), ("mv_range", ctypes.c_int32)]
+                ("eob_dense", ctypes.c_int32), ("ref_mix", ctypes.c_int32), ("mv_range", ctypes.c_int32),
+                ("edge_large", ctypes.c_int32), ("p_intra", ctypes.c_float)]
 
 
 class FrameInfo(ctypes.Structure):
@@ -130,7 +132,7 @@ _lib_handle = None
 # (frame_tensors) needs torch imported before this library is loaded.
 _torch_first = False
 
-ABI_VERSION = 4                # VP9HIP_ABI_VERSION of include/vp9hip.h these bindings mirror
+ABI_VERSION = 5               # VP9HIP_ABI_VERSION of include/vp9hip.h these bindings mirror
 PIPELINE_SLOTS = 3             # VP9HIP_PIPELINE_SLOTS: batch slots the decoder / adapter rotate
 # Exported symbols of include/vp9hip.h (checked by the CPU test suite).
 ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit_frame",
@@ -167,7 +169,7 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     # the struct mirrors below are the header's of this ABI version (vp9h_synth_params and
     # vp9h_enc_params grew in version 2, vp9h_frame_info and vp9hip_decoded_frame in 3,
-    # vp9h_synth_params again in 4): a
+    # vp9h_synth_params again in 4 and 5): a
     # library built from another header is refused
     if L.vp9hip_abi_version() != ABI_VERSION:
         raise Vp9HipUnavailable("libvp9hip.so ABI version %d, these bindings need %d: rebuild it (%s)"
@@ -281,6 +283,8 @@ def lib():
                                                 ctypes.c_int64, ctypes.c_void_p]
     L.vp9hip_resid4_host.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
     L.vp9hip_residn_host.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
+    L.vp9hip_intra_job_host.argtypes = [ctypes.c_int] * 15 + [ctypes.POINTER(ctypes.c_int32)]
+    L.vp9hip_intra_job_dev.argtypes = [ctypes.c_int] * 13 + [ctypes.POINTER(ctypes.c_int32)]
     _lib_handle = L
     return L
 
@@ -368,6 +372,32 @@ def intra_txfm_type(mode):
     """txtp (bit 0: ADST in the first pass, bit 1: in the second) the planners give a luma
     intra block of `mode` below 32x32 (vp9hip_intra_txfm_type)."""
     return _check("vp9hip_intra_txfm_type", lib().vp9hip_intra_txfm_type(int(mode)))
+
+
+IntraJob = collections.namedtuple("IntraJob", "slot have_top have_left ct cl trreal nd trx")
+
+
+def intra_job_host(p, txs, mode, bx, by, x, y, pw4, tile_x0, cols, rows, ss_h, ss_v, ux0, uy0):
+    """The host planner's check_intra_mode of one tx block (vp9hip_intra_job_host =
+    pl_intra_job_blk) from what it holds: plane, tx size code, coded mode, the block's plane
+    pixel position, the tx block's (x, y) and the block's width in 4x4 units, the tile's first
+    8x8 column, the frame's 8x8 columns and rows, the subsampling and the tx block's 4x4 unit
+    in its SB. Returns IntraJob(slot of the final mode, have_top, have_left, ct, cl, trreal, nd,
+    trx)."""
+    out = (ctypes.c_int32 * 8)()
+    _check("vp9hip_intra_job_host", lib().vp9hip_intra_job_host(p, txs, mode, bx, by, x, y, pw4, tile_x0, cols, rows,
+                                                                ss_h, ss_v, ux0, uy0, out))
+    return IntraJob(*out)
+
+
+def intra_job_dev(p, txs, mode, sbx, sby, ux0, uy0, right, tile_sb0, cols, rows, ss_h, ss_v):
+    """The same from what the device planner's k_pjplan holds (vp9hip_intra_job_dev =
+    pl_intra_job_sb): the SB, the tx block's 4x4 unit in it, whether a tx block lies to its
+    right in the block, the tile's first SB column."""
+    out = (ctypes.c_int32 * 8)()
+    _check("vp9hip_intra_job_dev", lib().vp9hip_intra_job_dev(p, txs, mode, sbx, sby, ux0, uy0, int(right), tile_sb0, cols,
+                                                              rows, ss_h, ss_v, out))
+    return IntraJob(*out)
 
 
 def synth_params(width, height, bpp=8, **kw):

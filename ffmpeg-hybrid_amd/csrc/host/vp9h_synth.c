@@ -134,9 +134,14 @@ static void gen_block(Gen *g, int row, int col, int bl, int bp)
     b.row = row; b.col = col; b.bs = bs;
     if (p->seg.enabled && p->seg.nseg > 1) b.seg_id = (uint8_t) rng_int(&g->rng, MIN(8, p->seg.nseg));
     g->seg = b.seg_id;
-    b.intra = !p->inter || rng_f(&g->rng) < 0.1;
+    b.intra = !p->inter || rng_f(&g->rng) < (p->p_intra > 0 ? (double) p->p_intra : 0.1);
     b.skip = rng_f(&g->rng) < p->p_skip;
-    b.tx = p->lossless ? 0 : rng_int(&g->rng, max_tx_for_bs[bs] + 1);
+    /* edge_large, a block the frame's right or bottom edge cuts: three times in four one of its
+     * two largest legal transforms (the sizes the edge can fall inside) */
+    if (p->edge_large && !p->lossless && (col + w4 > g->cols || row + h4 > g->rows) && rng_f(&g->rng) < 0.75)
+        b.tx = max_tx_for_bs[bs] - rng_int(&g->rng, MIN(2, max_tx_for_bs[bs] + 1));
+    else
+        b.tx = p->lossless ? 0 : rng_int(&g->rng, max_tx_for_bs[bs] + 1);
     b.uvtx = b.tx - ((p->ss_h && w4 * 2 == (1 << b.tx)) || (p->ss_v && h4 * 2 == (1 << b.tx)));
     if (b.intra) {
         for (i = 0; i < 4; i++) b.mode[i] = rng_int(&g->rng, 10);
@@ -207,6 +212,9 @@ static void gen_block(Gen *g, int row, int col, int bl, int bp)
 static void gen_sb(Gen *g, int row, int col, int bl)
 {
     static const double p_split[3] = { 0.5, 0.5, 0.3 };
+    /* a square the frame edge cuts splits, or else takes the forced H / V partition; edge_large
+     * keeps it whole more often, so that large transforms cross the edge */
+    const double p_cut = g->p->edge_large ? 0.3 : 0.7;
     int hbs = 4 >> bl, bp;
     if (g->err) return;
     if (bl == 3) {
@@ -226,14 +234,14 @@ static void gen_sb(Gen *g, int row, int col, int bl)
                 gen_sb(g, row + hbs, col, bl + 1);
                 gen_sb(g, row + hbs, col + hbs, bl + 1);
             }
-        } else if (rng_f(&g->rng) < 0.7) {
+        } else if (rng_f(&g->rng) < p_cut) {
             gen_sb(g, row, col, bl + 1);
             gen_sb(g, row, col + hbs, bl + 1);
         } else {
             gen_block(g, row, col, bl, 1);
         }
     } else if (row + hbs < g->rows) {
-        if (rng_f(&g->rng) < 0.7) {
+        if (rng_f(&g->rng) < p_cut) {
             gen_sb(g, row, col, bl + 1);
             gen_sb(g, row + hbs, col, bl + 1);
         } else {
@@ -263,7 +271,8 @@ int vp9hip_synth_frame(vp9h_frame *out, const vp9h_synth_params *p)
     int row, col, tc, i, s;
     int bidx = p->bpp == 8 ? 0 : p->bpp == 10 ? 1 : 2;
     if (!out || !p || p->width <= 0 || p->height <= 0 ||
-        (p->bpp != 8 && p->bpp != 10 && p->bpp != 12) || p->mv_range < 0 || p->mv_range > 16383)
+        (p->bpp != 8 && p->bpp != 10 && p->bpp != 12) || p->mv_range < 0 || p->mv_range > 16383 ||
+        !(p->p_intra >= 0 && p->p_intra <= 1))
         return VP9HIP_EINVAL;
     memset(&g, 0, sizeof(g));
     memset(out, 0, sizeof(*out));

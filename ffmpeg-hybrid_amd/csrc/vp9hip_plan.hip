@@ -524,11 +524,8 @@ DEV int pjob_sb(const PlanDev &D, const PlanFrame &F, uint32_t *ja)
         if (w & TXR_JOB) {
             // check_intra_mode resolved (vp9recon.c:37-221) from the record's inputs
             const int p = w & 3, txs = (w >> 2) & 3, ux0 = (w >> 12) & 15, uy0 = (w >> 16) & 15;
-            const int sh = p ? SSH : 0, sv = p ? SSV : 0;
-            const int pw8 = p ? cols * 8 >> SSH : cols * 8, ph8 = p ? rows * 8 >> SSV : rows * 8;
-            const PlIntra pi = pl_intra_job(p, txs, (int) ((w >> 8) & 15), (int) e0, G.sbx * (64 >> sh) + ux0 * 4,
-                                            G.sby * (64 >> sv) + uy0 * 4, 0, (w & TXR_RIGHT) ? 2 : 1, p ? tx0l >> SSH : tx0l,
-                                            pw8, ph8, ux0, uy0);
+            const PlIntra pi = pl_intra_job_sb(p, txs, (int) ((w >> 8) & 15), (int) e0, G.sbx, G.sby, ux0, uy0,
+                                               (w & TXR_RIGHT) != 0, tx0l, cols, rows, SSH, SSV);
             ja[nj + (int) mbcnt(mj)] = pi.a | (pi.trx ? JA_TRX : 0u);      // at most T <= JCAP
         }
         nj += __popcll(mj);

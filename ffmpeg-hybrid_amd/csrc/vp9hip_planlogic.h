@@ -126,6 +126,28 @@ PL_HD PlIntra pl_intra_job(int p, int txs, int mode, int e, int gx, int gy, int 
     return r;
 }
 
+/* pl_intra_job from what each planner holds of a tx block, so that the CPU check
+ * (vp9hip_intra_job_host / _dev, tests/test_intra_edges_host.py) runs the planners' own argument
+ * rules. The host planner walks the block: its plane pixel position (bx, by), the tx block's
+ * (x, y) and the block's width pw4 in 4x4 units, the tile's first 8x8 column. */
+PL_HD PlIntra pl_intra_job_blk(int p, int txs, int mode, int e, int bx, int by, int x, int y, int pw4, int tile_x0, int cols,
+                               int rows, int ss_h, int ss_v, int ux0, int uy0)
+{
+    return pl_intra_job(p, txs, mode, e, bx + x * 4, by + y * 4, x, pw4, p ? tile_x0 * 8 >> ss_h : tile_x0 * 8,
+                        p ? cols * 8 >> ss_h : cols * 8, p ? rows * 8 >> ss_v : rows * 8, ux0, uy0);
+}
+/* The device planner (k_pjplan) holds the record of k_psb: the SB, the tx block's 4x4 unit in
+ * it, whether a tx block lies to its right in the block (TXR_RIGHT), the tile's first luma
+ * pixel column tx0l. */
+PL_HD PlIntra pl_intra_job_sb(int p, int txs, int mode, int e, int sbx, int sby, int ux0, int uy0, int right, int tx0l,
+                              int cols, int rows, int ss_h, int ss_v)
+{
+    const int sh = p ? ss_h : 0, sv = p ? ss_v : 0;
+    const int pw8 = p ? cols * 8 >> ss_h : cols * 8, ph8 = p ? rows * 8 >> ss_v : rows * 8;
+    return pl_intra_job(p, txs, mode, e, sbx * (64 >> sh) + ux0 * 4, sby * (64 >> sv) + uy0 * 4, 0, right ? 2 : 1,
+                        p ? tx0l >> ss_h : tx0l, pw8, ph8, ux0, uy0);
+}
+
 /* The 4x4 units of the job's own SB plane (16 units per map row) its substituted mode
  * reads: fn(unit). A level / pass order may only place the job after their producers. */
 template <class F>

@@ -856,10 +856,8 @@ static int build_frame(vp9hip_ctx *c, Staged &s, FrameBuild &fb, std::vector<std
                         // intra: prediction job with check_intra_mode resolved (vp9recon.c:37-221),
                         // ordered after the jobs that produce the pixels its mode reads
                         PendingJob q;
-                        const PlIntra pi = pl_intra_job(p, txs, mode, e, bx + x * 4, by + y * 4, x, g.pw4,
-                                                        p ? tile_x0 * 8 >> ss_h : tile_x0 * 8,
-                                                        p ? cols * 8 >> ss_h : cols * 8, p ? rows * 8 >> ss_v : rows * 8,
-                                                        ux0, uy0);
+                        const PlIntra pi = pl_intra_job_blk(p, txs, mode, e, bx, by, x, y, g.pw4, tile_x0, cols, rows, ss_h, ss_v,
+                                                            ux0, uy0);
                         q.j.a = pi.a;
                         q.j.roff = roff;
                         q.ts = txs;
@@ -3130,6 +3128,44 @@ template <int N> int residn_blocks(int hb, int tcode, int txtp, int n, const uin
 // The planners' transform type of a luma intra block of `mode` (pl_intra_txfm_type), for tests
 // that sort a packet's tx blocks by it; -1 for no intra mode.
 extern "C" int vp9hip_intra_txfm_type(int mode) { return mode < 0 || mode > 9 ? -1 : pl_intra_txfm_type(mode); }
+
+// The planners' check_intra_mode of one tx block, for the CPU check against a restatement from
+// the packet (tests/synth_walk.py): plane p, tx size code, coded mode and what each planner holds
+// of the block (pl_intra_job_blk: the host planner, pl_intra_job_sb: the device planner's
+// k_pjplan; vp9hip_planlogic.h). out[8] = the fields of the PJob word: the final mode's slot,
+// have_top, have_left, ct, cl, trreal; then nd and trx. -1 for a tx block outside the frame or
+// arguments no packet has.
+static int intra_job_out(const PlIntra &pi, int32_t *out)
+{
+    PJob j;
+    j.a = pi.a;
+    j.roff = 0;
+    out[0] = PJ_MSLOT(j); out[1] = PJ_HTOP(j); out[2] = PJ_HLEFT(j); out[3] = PJ_CT(j); out[4] = PJ_CL(j);
+    out[5] = PJ_TRREAL(j); out[6] = pi.nd; out[7] = pi.trx;
+    return 0;
+}
+static bool intra_job_args_ok(int p, int txs, int mode, int cols, int rows, int ss_h, int ss_v, int ux0, int uy0, const int32_t *out)
+{
+    return p >= 0 && p <= 2 && txs >= 0 && txs <= 3 && mode >= 0 && mode <= 9 && cols > 0 && rows > 0 && cols <= 2048 &&
+           rows <= 2048 && (ss_h | ss_v | 1) == 1 && ux0 >= 0 && ux0 <= 15 && uy0 >= 0 && uy0 <= 15 && out;
+}
+extern "C" int vp9hip_intra_job_host(int p, int txs, int mode, int bx, int by, int x, int y, int pw4, int tile_x0, int cols,
+                                     int rows, int ss_h, int ss_v, int ux0, int uy0, int32_t *out)
+{
+    if (!intra_job_args_ok(p, txs, mode, cols, rows, ss_h, ss_v, ux0, uy0, out) || bx < 0 || by < 0 || x < 0 || y < 0 ||
+        bx + x * 4 >= (cols * 8 >> (p ? ss_h : 0)) || by + y * 4 >= (rows * 8 >> (p ? ss_v : 0)) || tile_x0 < 0 || tile_x0 >= cols)
+        return -1;
+    return intra_job_out(pl_intra_job_blk(p, txs, mode, 0, bx, by, x, y, pw4, tile_x0, cols, rows, ss_h, ss_v, ux0, uy0), out);
+}
+extern "C" int vp9hip_intra_job_dev(int p, int txs, int mode, int sbx, int sby, int ux0, int uy0, int right, int tile_sb0,
+                                    int cols, int rows, int ss_h, int ss_v, int32_t *out)
+{
+    if (!intra_job_args_ok(p, txs, mode, cols, rows, ss_h, ss_v, ux0, uy0, out) || sbx < 0 || sby < 0 ||
+        sbx * 8 + (ux0 << (p ? ss_h : 0)) / 2 >= cols || sby * 8 + (uy0 << (p ? ss_v : 0)) / 2 >= rows || tile_sb0 < 0 ||
+        tile_sb0 > sbx)
+        return -1;
+    return intra_job_out(pl_intra_job_sb(p, txs, mode, 0, sbx, sby, ux0, uy0, right, tile_sb0 * 64, cols, rows, ss_h, ss_v), out);
+}
 
 // The lane-per-column residual kernels' block routine on the host, for the CPU check against
 // the oracle: n blocks of tx code `tcode` (1..3: 8x8, 16x16, 32x32) and `txtp` (0 for 32x32),

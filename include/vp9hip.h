@@ -38,7 +38,8 @@ extern "C" {
  * vp9hip_decoder_convert) added. vp9hip_convert_frames_scaled / vp9hip_decoder_convert_scaled
  * came later as new symbols only: no struct changed, so the version stayed. */
 /* 4: vp9h_synth_params ends in eob_dense / ref_mix / mv_range. */
-#define VP9HIP_ABI_VERSION 4
+/* 5: vp9h_synth_params ends in edge_large / p_intra. */
+#define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
 #define VP9HIP_EINVAL       (-22)          /* AVERROR(EINVAL)   */
@@ -381,8 +382,9 @@ int  vp9hip_device_info(int device, char *pci_bus_id, int len, char *name, int n
  * base_q_idx 60 (no deltas), filter level 36, sharpness 0, LF deltas at the libvpx
  * defaults. inter != 0: an inter frame whose single-reference blocks read LAST and whose
  * compound blocks read LAST + ALTREF (ref_mix: every reference, see below), 50 % NEWMV,
- * MVs uniform in +-64 px (mv_range: another range), 10 % intra blocks. The packet owns
- * heap arrays; release with vp9hip_synth_free.
+ * MVs uniform in +-64 px (mv_range: another range), 10 % intra blocks (p_intra: another
+ * share). A square the frame edge cuts splits with chance 0.7 (edge_large: 0.3). The packet
+ * owns heap arrays; release with vp9hip_synth_free.
  */
 /* Segmentation and loop-filter deltas of a frame (vp9.c:692-765, vp9block.c:101-141): what
  * vp9h_stream_encode writes into the frame header, and what vp9hip_synth_frame assumes for
@@ -429,6 +431,12 @@ typedef struct vp9h_synth_params {
                                 * under sign bias 0, 0, 1)                           */
     int32_t  mv_range;         /* nonzero MVs uniform in +-mv_range 1/8 pel, at most
                                 * 16383 (0: 512)                                    */
+    /* ABI version 5; all zero = the draws above, packet for packet                 */
+    int32_t  edge_large;       /* 1: a square the frame's right or bottom edge cuts splits
+                                * with chance 0.3, not 0.7 (else the forced H / V
+                                * partition), and a block that edge cuts takes one of its
+                                * two largest legal tx sizes three times in four    */
+    float    p_intra;          /* inter frames: share of intra blocks (0: 0.1)      */
 } vp9h_synth_params;
 
 /* Fill p with the §8(d) defaults for a w x h bpp stream. */

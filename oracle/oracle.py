@@ -47,6 +47,9 @@ def lib():
         _L.vp9o_mc_scaled.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_ssize_t, ctypes.c_void_p,
                                       ctypes.c_ssize_t] + [ctypes.c_int] * 8
         _L.vp9o_mc_scaled.restype = None
+        _L.vp9o_set_intra_trace.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+        _L.vp9o_set_intra_trace.restype = None
+        _L.vp9o_intra_trace_count.restype = ctypes.c_size_t
         _L.vp9o_scan.argtypes = [ctypes.c_int, ctypes.c_int]
         _L.vp9o_scan.restype = ctypes.POINTER(ctypes.c_int16)
     return _L
@@ -81,6 +84,22 @@ def decode_frame(pkt, out_planes, ref_planes=None, ref_sizes=None, tile_threads=
     if r < 0:
         raise RuntimeError("vp9o_decode_frame failed: %d" % r)
     return out_planes
+
+
+def intra_trace(pkt, out_planes, ref_planes=None, cap=1 << 16):
+    """decode_frame with check_intra_mode traced (vp9o_set_intra_trace): the (n, 6) int32 array of
+    (plane, tx size code, final mode, top n_px_have or 0, left n_px_have or 0, 4x4 top-right
+    0 not read / 1 real / 2 replicated), one row per call in call order."""
+    buf = np.zeros((cap, 6), np.int32)
+    lib().vp9o_set_intra_trace(buf.ctypes.data, cap)
+    try:
+        decode_frame(pkt, out_planes, ref_planes)
+        n = lib().vp9o_intra_trace_count()
+    finally:
+        lib().vp9o_set_intra_trace(None, 0)
+    if n > cap:
+        raise RuntimeError("intra trace: %d calls, room for %d" % (n, cap))
+    return buf[:n]
 
 
 def scan(tx, txtp):

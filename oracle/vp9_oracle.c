@@ -147,6 +147,12 @@ static void load_coefs(OCtx *c, int p, void *blk, int eob, int tx, int txtp)
     }
 }
 
+/* vp9o_set_intra_trace: what check_intra_mode resolved, call for call (vp9_oracle.h) */
+static int32_t *intra_trace;
+static size_t intra_trace_cap, intra_trace_n;
+void vp9o_set_intra_trace(int32_t *buf, size_t cap) { intra_trace = buf; intra_trace_cap = buf ? cap : 0; intra_trace_n = 0; }
+size_t vp9o_intra_trace_count(void) { return intra_trace_n; }
+
 /* check_intra_mode, vp9recon.c:37-221. Byte-addressed like the reference. */
 static int check_intra_mode(OCtx *c, int mode, uint8_t **a, uint8_t *dst_edge, ptrdiff_t stride_edge,
                             uint8_t *dst_inner, ptrdiff_t stride_inner, uint8_t *l, int col, int x,
@@ -180,6 +186,16 @@ static int check_intra_mode(OCtx *c, int mode, uint8_t **a, uint8_t *dst_edge, p
     int i;
 
     mode = mode_conv[mode][have_left][have_top];
+    if (intra_trace) {
+        const int ht = (((c->cols - col) << !ss_h) - x) * 4, hl = (((c->rows - row) << !ss_v) - y) * 4;
+        if (intra_trace_n < intra_trace_cap) {
+            int32_t *t = intra_trace + 6 * intra_trace_n;
+            t[0] = p; t[1] = tx; t[2] = mode;
+            t[3] = have_top ? ht : 0; t[4] = have_left ? hl : 0;
+            t[5] = !(tx == 0 && edges[mode][3]) ? 0 : have_top && have_right && 8 <= ht ? 1 : 2;
+        }
+        intra_trace_n++;
+    }
     if (edges[mode][1]) {
         uint8_t *top = NULL, *topleft = NULL;
         int n_px_need = 4 << tx, n_px_have = (((c->cols - col) << !ss_h) - x) * 4;

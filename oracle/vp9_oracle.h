@@ -36,6 +36,15 @@ int vp9o_decode_frame(const vp9h_frame *f, vp9o_planes *cur, const vp9o_planes *
  * vp9.c:1442-1551): the slice-threaded CPU baseline. Output identical. */
 int vp9o_decode_frame_tiles(const vp9h_frame *f, vp9o_planes *cur, const vp9o_planes *refs, int nthreads);
 
+/* Optional trace of check_intra_mode (vp9recon.c:37-221) for tests that restate it from the
+ * packet: while buf is set, every call of vp9o_decode_frame's intra reconstruction appends six
+ * int32 (plane, tx size code, final mode after mode_conv 0..14, n_px_have of the top edge or 0
+ * without have_top, n_px_have of the left edge or 0 without have_left, the 4x4 top-right:
+ * 0 not read, 1 real, 2 replicated) while fewer than cap records are held. The count goes on
+ * past cap. NULL ends the trace. Not for vp9o_decode_frame_tiles (one buffer, no lock). */
+void vp9o_set_intra_trace(int32_t *buf, size_t cap);
+size_t vp9o_intra_trace_count(void);
+
 /* DSP entry points for unit tests (stride in pixels). */
 void vp9o_itxfm_add(int bpp, void *dst, ptrdiff_t stride, void *coef, int eob, int tx, int txtp);
 void vp9o_intra_pred(int bpp, void *dst, ptrdiff_t stride, const void *left, const void *top,

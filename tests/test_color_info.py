@@ -184,8 +184,9 @@ def test_out_layout(v9):
 
 def test_abi_version_and_struct_tails(v9):
     import ctypes
-    assert v9.ABI_VERSION == 4 and v9.lib().vp9hip_abi_version() == 4
-    assert [f[0] for f in v9.SynthParams._fields_[-4:]] == ["seg", "eob_dense", "ref_mix", "mv_range"]
+    assert v9.ABI_VERSION == 5 and v9.lib().vp9hip_abi_version() == 5
+    assert [f[0] for f in v9.SynthParams._fields_[-6:]] == ["seg", "eob_dense", "ref_mix", "mv_range", "edge_large",
+                                                            "p_intra"]
     assert v9.FrameInfo._fields_[-2:] == [("colorspace", ctypes.c_int32), ("full_range", ctypes.c_int32)]
     assert v9.DecodedFrameInfo._fields_[-2:] == [("colorspace", ctypes.c_int32), ("full_range", ctypes.c_int32)]
     assert ctypes.sizeof(v9.FrameInfo) == 88 and ctypes.sizeof(v9.DecodedFrameInfo) == 40

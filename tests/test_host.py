@@ -29,8 +29,9 @@ def test_struct_layouts_match_header(v9):
     # vp9h_block is 52 bytes (include/vp9hip.h); the Python mirror must agree
     assert ctypes.sizeof(v9.Block) == 52
     assert ctypes.sizeof(v9.SegParams) == 124             # 31 int32
-    assert ctypes.sizeof(v9.SynthParams) == 208           # 72 + vp9h_seg_params + 3 int32 (a multiple of the uint64 alignment)
+    assert ctypes.sizeof(v9.SynthParams) == 216           # 72 + vp9h_seg_params + 4 int32 + float (a multiple of the uint64 alignment)
     assert v9.SynthParams.eob_dense.offset == 196 and v9.SynthParams.mv_range.offset == 204
+    assert v9.SynthParams.edge_large.offset == 208 and v9.SynthParams.p_intra.offset == 212
     assert ctypes.sizeof(v9.EncParams) == 88 + 124          # 22 int32 + vp9h_seg_params
     assert v9.SynthParams.seg.offset == 72 and v9.EncParams.seg.offset == 88
 

@@ -438,3 +438,37 @@ def test_dense_coefficients_every_reference_and_far_mvs_round_trip(v9, bpp):
             same_packet(p.pkt, c.pkt)
             if kw:
                 assert list(info.ref_slot) == list(kw["ref_slot"]) and list(info.sign_bias) == [0, 0, 1]
+
+
+@pytest.mark.parametrize("w,h", [(88, 72), (24, 72), (72, 8)])
+def test_large_transforms_across_the_frame_edge_and_intra_heavy_inter_frames_round_trip(v9, w, h):
+    """edge_large and p_intra through the bitstream writer and parser: a key + 2 inter stream of
+    frames whose right and bottom edges cut whole 32x64 / 64x32 / 16x32 ... blocks with 16x16
+    and 32x32 transforms (the above / left contexts of tx blocks that end outside the frame) and
+    whose inter frames are mostly intra (intra modes coded without neighbour context). The
+    parsed packets equal the coded ones field for field, and the coded ones carry the generated
+    blocks, eobs and coefficients."""
+    import synth_walk
+    frames = [v9.SynthFrame(v9.synth_params(w, h, 8, seed=0xd40, edge_large=1))]
+    frames += [v9.SynthFrame(v9.synth_params(w, h, 8, seed=0xd41 + i, inter=1, compound=1, edge_large=1, p_intra=0.7))
+               for i in range(2)]
+    cols, rows = (w + 7) >> 3, (h + 7) >> 3
+    cut = [b for f in frames for b in _blocks(f.pkt)
+           if (b.col + synth_walk.BWH8[b.bs][0] > cols or b.row + synth_walk.BWH8[b.bs][1] > rows) and b.tx >= 2]
+    assert cut and any(b.intra for b in cut)
+    share = [sum(b.intra for b in _blocks(f.pkt)) / f.pkt.nblocks for f in frames[1:]]
+    assert min(share) > 0.4, share
+    enc = v9.Stream()
+    per = [{}, dict(ref_slot=(0, 1, 2), sign_bias=(0, 0, 1), refresh_mask=1 << 1),
+           dict(ref_slot=(1, 0, 2), sign_bias=(0, 0, 1), refresh_mask=1 << 2)]
+    datas, coded = zip(*[enc.encode(f, **kw) for f, kw in zip(frames, per)])
+    stats = {"kept": 0, "to_new": 0}
+    for f, c in zip(frames, coded):
+        check_legalized(f.pkt, c.pkt, stats)
+        eo, co = _arrays(f.pkt)
+        ec, cc = _arrays(c.pkt)
+        assert np.array_equal(eo, ec) and co == cc
+    dec = v9.Stream()
+    for d, c in zip(datas, coded):
+        p, info = dec.decode(d)
+        same_packet(p.pkt, c.pkt)

@@ -1,4 +1,4 @@
-"""The synthetic generator's coverage switches (eob_dense, ref_mix, mv_range) and the packet
+"""The synthetic generator's coverage switches (eob_dense, ref_mix, mv_range, edge_large, p_intra) and the packet
 walker the GPU tests build their coverage conditions on (tests/synth_walk.py).
 
 With the switches at 0 the generator draws what it always drew: the digests below were taken
@@ -37,7 +37,7 @@ def test_default_packets_are_pinned(v9, w, h, bpp, kw, digest):
     f = v9.SynthFrame(v9.synth_params(w, h, bpp, **kw))
     assert synth_walk.packet_digest(f.pkt) == digest
     # explicit zeros are the defaults
-    z = v9.SynthFrame(v9.synth_params(w, h, bpp, eob_dense=0, ref_mix=0, mv_range=0, **kw))
+    z = v9.SynthFrame(v9.synth_params(w, h, bpp, eob_dense=0, ref_mix=0, mv_range=0, edge_large=0, p_intra=0, **kw))
     assert synth_walk.packet_digest(z.pkt) == digest
     # ±512 spelled out is the default range, draw for draw
     m = v9.SynthFrame(v9.synth_params(w, h, bpp, mv_range=512, **kw))
@@ -113,6 +113,50 @@ def test_mv_range(v9):
     for r in (-1, 16384):
         with pytest.raises(v9.Vp9HipError):
             v9.SynthFrame(v9.synth_params(200, 130, 8, inter=1, mv_range=r))
+
+
+def _cut_blocks(f):
+    """(blocks the frame's right or bottom edge cuts, those of them with one of the two largest
+    tx sizes the block size allows)"""
+    cols, rows = (f.pkt.width + 7) >> 3, (f.pkt.height + 7) >> 3
+    max_tx = [3, 3, 3, 3, 2, 2, 2, 1, 1, 1, 0, 0, 0]
+    cut = [b for b in f.blocks() if b.col + synth_walk.BWH8[b.bs][0] > cols or b.row + synth_walk.BWH8[b.bs][1] > rows]
+    return cut, [b for b in cut if b.tx >= max_tx[b.bs] - 1]
+
+
+def test_edge_large_keeps_cut_blocks_whole_and_their_transforms_large(v9):
+    """88x88: the second superblock column and row show 24 pixels. With edge_large the blocks
+    the frame edge cuts are fewer and larger (fewer splits of cut squares) and seven in eight of them take
+    one of their two largest tx sizes (three in four by the switch, half of the rest by the
+    uniform draw; blocks of 8x8 and below have two sizes at most)."""
+    big, n_cut = {}, {}
+    for sw in (0, 1):
+        fr = [v9.SynthFrame(v9.synth_params(88, 88, 8, seed=71 + i, edge_large=sw)) for i in range(64)]
+        cut = [c for f in fr for c in _cut_blocks(f)[0]]
+        large = [c for f in fr for c in _cut_blocks(f)[1]]
+        n_cut[sw] = len(cut)
+        big[sw] = sum(b.bs < 3 for b in cut)                     # the forced 64x32 / 32x64 of a cut superblock
+        assert sw == 0 or len(large) > 0.8 * len(cut), (len(large), len(cut))
+        # inside the frame nothing changes in kind: every tx size of the uncut 32x32 and larger blocks
+        assert {b.tx for f in fr for b in f.blocks() if b.bs < 6} == {0, 1, 2, 3}
+    # 128 cut superblocks stay whole with chance 0.7, not 0.3: 90 against 38, sigma 5 each
+    assert n_cut[1] < n_cut[0] and big[1] > 1.5 * big[0], (n_cut, big)
+    # lossless stays 4x4
+    f = v9.SynthFrame(v9.synth_params(88, 88, 8, seed=71, lossless=1, q_idx=0, edge_large=1))
+    assert {b.tx for b in f.blocks()} == {0}
+
+
+def test_p_intra_sets_the_intra_share_of_inter_frames(v9):
+    for share in (0.1, 0.5, 0.85, 1.0):
+        f = v9.SynthFrame(v9.synth_params(352, 288, 8, seed=81, inter=1, p_intra=share))
+        bl = f.blocks()
+        got = sum(b.intra for b in bl) / len(bl)
+        assert abs(got - share) < 0.05, (share, got, len(bl))         # > 1000 blocks: sigma < 0.016
+    k = v9.SynthFrame(v9.synth_params(352, 288, 8, seed=81, p_intra=0.5))
+    assert all(b.intra for b in k.blocks())                           # keyframes stay all intra
+    for bad in (-0.5, 1.5, float("nan")):
+        with pytest.raises(v9.Vp9HipError):
+            v9.SynthFrame(v9.synth_params(352, 288, 8, inter=1, p_intra=bad))
 
 
 def test_intra_txfm_type_is_the_reference_table(v9):
