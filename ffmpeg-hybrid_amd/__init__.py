@@ -285,6 +285,8 @@ def lib():
     L.vp9hip_residn_host.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
     L.vp9hip_intra_job_host.argtypes = [ctypes.c_int] * 15 + [ctypes.POINTER(ctypes.c_int32)]
     L.vp9hip_intra_job_dev.argtypes = [ctypes.c_int] * 13 + [ctypes.POINTER(ctypes.c_int32)]
+    L.vp9hip_plan_sched_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4
+    L.vp9hip_test_plan_records.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)] + [ctypes.c_void_p] * 4
     _lib_handle = L
     return L
 
@@ -366,6 +368,20 @@ def residn_host(bpp, tcode, txtp, eobs, coefs):
     _check("vp9hip_residn_host", lib().vp9hip_residn_host(hb, tcode, txtp, n, eobs.ctypes.data, coefs.ctypes.data,
                                                           res.ctypes.data))
     return res
+
+
+def plan_sched_host(ss_h, ss_v, ja):
+    """The device planner's intra schedule of one SB in scalar host code
+    (vp9hip_plan_sched_host): ja = the SB's job words in decode order (plane | tx size << 2 |
+    mode slot << 8 | x4 << 12 | y4 << 16 | trx << 30). Returns (order, passes, masks): the decode
+    index of the job at each position of the SB's job array, the pass words, and per job the units
+    it waits for (bit u of its top row, bit 16 + v of its left column)."""
+    ja = np.ascontiguousarray(ja, np.uint32)
+    n = len(ja)
+    order, passes, masks = np.empty(n, np.uint16), np.empty(max(n, 1), np.uint32), np.empty(n, np.uint32)
+    npass = _check("vp9hip_plan_sched_host", lib().vp9hip_plan_sched_host(ss_h, ss_v, n, ja.ctypes.data, order.ctypes.data,
+                                                                         passes.ctypes.data, masks.ctypes.data))
+    return order, passes[:npass].copy(), masks
 
 
 def intra_txfm_type(mode):
@@ -719,6 +735,19 @@ class Device:
 
     def run_batch(self):
         _check("vp9hip_run_batch", lib().vp9hip_run_batch(self._c))
+
+    def plan_records(self):
+        """Test only (vp9hip_test_plan_records): the device planner's intra schedule of the current
+        slot's batch, read back once the device is idle. Returns (sbs, wgs, passes, jobs_a):
+        uint32 arrays of shape (slots, 3), (slots, 4), (slots, jcap) and (slots, jcap)."""
+        jcap = ctypes.c_int()
+        ns = _check("vp9hip_test_plan_records", lib().vp9hip_test_plan_records(self._c, 0, ctypes.byref(jcap), None, None,
+                                                                               None, None))
+        sbs, wgs = np.empty((ns, 3), np.uint32), np.empty((ns, 4), np.uint32)
+        passes, jobs = np.empty((ns, jcap.value), np.uint32), np.empty((ns, jcap.value), np.uint32)
+        _check("vp9hip_test_plan_records", lib().vp9hip_test_plan_records(self._c, ns, ctypes.byref(jcap), sbs.ctypes.data,
+                                                                          wgs.ctypes.data, passes.ctypes.data, jobs.ctypes.data))
+        return sbs, wgs, passes, jobs
 
     def sync(self):
         _check("vp9hip_sync", lib().vp9hip_sync(self._c))

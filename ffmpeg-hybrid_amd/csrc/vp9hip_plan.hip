@@ -419,38 +419,42 @@ __global__ __launch_bounds__(64) void k_psb(PlanDev D)
 }
 
 // ------------------------------------------------------------------ k_pjplan
-// plan_sb's LDS: the unit map, then the heights, then the priority order with the pass of
-// each job share one region, each dead before the next is written (7.2 KB at 4:2:0; with ord
-// and sch after the heights 8.75 KB: 17 instead of 21 workgroups per CU)
+// plan_sb's LDS: the unit map, then the heights, then the priority order share one region,
+// each dead before the next is written; the producer lists die with the heights, and the
+// readiness masks and done bits of the pass loop take their place (7.2 KB at 4:2:0)
 template <int JCAP> struct alignas(16) PlanLds {   // 16: jmap rows are stored 16 bytes at a time
     uint32_t ja[JCAP];            // PJob word per intra job (decode order), bit 30: the 4x4
                                   // top-right lies inside the block (trx)
     union {
-        uint16_t jmap[3][256];    // producing job of each 4x4 unit
+        uint16_t jmap[3][256];    // producing job of each 4x4 unit (PL_JM_ENT)
         struct {
             union {
                 uint32_t hgt[JCAP];           // longest path to a sink (list-scheduling priority)
-                struct {
-                    uint16_t ord[JCAP];       // jobs by (height desc, index asc)
-                    uint16_t sch[JCAP];       // pass of each job (0xffff: not yet)
-                } os;
+                uint16_t ord[JCAP];           // jobs by (height desc, index asc)
             } h;
             uint16_t doff[JCAP + 1];      // producers of job j: dep[2 (doff & 2047) ..] (count doff >> 11)
-            uint16_t dep[4 * JCAP];
+            union {
+                uint16_t dep[4 * JCAP];
+                struct {
+                    uint32_t mk[JCAP];        // pl_deps' masks of job j: the units it waits for
+                    // units whose job an earlier pass took: bit u of drow[p * 16 + v] and bit v
+                    // of dcol[p * 16 + u] for unit (u, v) of plane p (a fourth plane's worth, and
+                    // indices masked to 63, so that no job word can address past them)
+                    uint32_t drow[64], dcol[64];
+                } rd;
+            } d;
             uint32_t hs[64];              // height histogram -> list starts
             uint16_t tk[16];              // jobs taken by the pass being built
         } b;
     } u;
 };
 static_assert(sizeof(uint16_t[3][256]) <= sizeof(uint32_t[256 + 2 * 64]), "the unit map fits the heights' region");
-// unit-map entry: job | units to its right edge << 10 | units to its bottom edge << 13 (0..7
-// each: a job is at most 8 units wide); 0xffff (job 1023 > JCAP) marks a unit no job covers
-#define JM_ENT(j, r, b) ((uint32_t) (j) | (uint32_t) (r) << 10 | (uint32_t) (b) << 13)
+#define JM_ENT PL_JM_ENT
 
 // edges the job's (substituted) mode reads: 1 left, 2 top, 4 top-left, 8 top-right (pl_intra_job)
 DEV uint32_t needs_of(uint32_t a)
 {
-    return (uint32_t) pl_field(0x21371a777a12ull, (int) ((a >> 8) & 15), 4);     /* pl_intra_job's needs by slot */
+    return (uint32_t) pl_slot_needs((int) ((a >> 8) & 15));
 }
 DEV uint32_t wor(uint32_t v) { return rdl(wscan_dpp<OP_OR>(v), 63); }
 
@@ -577,7 +581,8 @@ static_assert(sizeof(RJob) == 16 && offsetof(RJob, eob) == 8 && offsetof(RJob, f
 // dependencies and intra step. The job words are in S.ja already (pjob_sb), nj of them.
 // (Two SBs per wave with the second's job words loaded under the first's scheduling cut the
 // first load's share of a wave's cycles from 31 to 20 %, but not the kernel: 2,880 -> 2,926 us
-// per C3 batch. The waves' time goes to dependent LDS chains at 6 waves per SIMD, LDS-bound.)
+// per C3 batch. By its counters the kernel is bound by scalar issue: about 4,300 SALU per wave at
+// 22 waves per CU)
 template <int SSH, int SSV>
 DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> &S, int nj)
 {
@@ -622,46 +627,16 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> 
     wsync();
     PPT(7);
 
-    // ---- producers of every intra job (the pixels its substituted mode reads)
-    // The units job j reads are pl_local_reads' runs: the top row (uy0 - 1, from ux0 - 1 with
-    // the top-left unit to ux0 + n + trx) and the left column (ux0 - 1, rows uy0 .. uy0 + n - 1).
-    // Jobs are aligned squares, so a run's units of one producer are consecutive: the walk
-    // jumps from a producer's unit past that producer's extent (one step per distinct
-    // producer instead of one per unit). Only the top-left unit's producer can recur in the
-    // left run. Units no intra job covers (0xffff) are stepped over one by one.
+    // ---- producers of every intra job (the pixels its substituted mode reads): pl_deps walks
+    // the two runs of units job j reads in the unit map
     auto deps_of = [&](int j, auto fn) {
         const uint32_t a = S.ja[j];
         const int p = a & 3, ts = (a >> 2) & 3, ux0 = (a >> 12) & 15, uy0 = (a >> 16) & 15;
-        const int units = p ? CW : 16, unitsv = p ? CH : 16, n4 = 1 << ts;
-        const int nd = (int) needs_of(a), trx = (a & JA_TRX) ? 1 : 0;
-        int tl = -1;                                       // producer of the top-left unit
-        if (uy0 > 0) {
-            const int u1 = pl_min((nd & 2) ? ux0 + n4 + trx : ux0, units);
-            int u = (nd & 4) ? ux0 - 1 : ux0;
-            if (u < 0) u = 0;
-            const uint16_t *row = S.u.jmap[p] + (uy0 - 1) * 16;
-            while (u < u1) {
-                const uint32_t e = row[u];
-                if (e == 0xffff) { u++; continue; }
-                const int d = (int) (e & 1023);
-                if (u == ux0 - 1) tl = d;
-                if (d < j) fn(d);
-                u += (int) ((e >> 10) & 7) + 1;               // past the producer's right edge
-            }
-        }
-        if (ux0 > 0 && (nd & 1)) {
-            const int v1 = pl_min(uy0 + n4, unitsv);
-            int v = uy0;
-            const uint16_t *col = S.u.jmap[p] + ux0 - 1;
-            while (v < v1) {
-                const uint32_t e = col[v * 16];
-                if (e == 0xffff) { v++; continue; }
-                const int d = (int) (e & 1023);
-                if (d < j && d != tl) fn(d);
-                v += (int) (e >> 13) + 1;                     // past the producer's bottom edge
-            }
-        }
+        return pl_deps(S.u.jmap[p], j, ux0, uy0, 1 << ts, (int) needs_of(a), (a & JA_TRX) ? 1 : 0, p ? CW : 16, p ? CH : 16, fn);
     };
+    uint32_t mreg[NCH];                       // pl_deps' masks of jobs c * 64 + lane
+#pragma unroll
+    for (int c = 0; c < NCH; c++) mreg[c] = 0;
     {
         // one enumeration: job j's list starts at the prefix sum of the per-size bounds (an
         // n-unit job reads at most 2n + 2 units: its left column, and the top row with the
@@ -673,12 +648,18 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> 
             const uint32_t cap = j < NJ ? 2u * (1u << ((S.ja[j] >> 2) & 3)) + 2u : 0u;
             const uint32_t incl = wscan_incl(cap, lane);
             const uint32_t off = carry + incl - cap;
+            uint32_t mk = 0;
             if (j < NJ) {
                 uint32_t k = off;
-                if (off + cap <= 4u * JCAP) deps_of(j, [&](int d) { if (k < off + cap) S.u.b.dep[k++] = (uint16_t) d; });
+                if (off + cap <= 4u * JCAP) mk = deps_of(j, [&](int d) { if (k < off + cap) S.u.b.d.dep[k++] = (uint16_t) d; });
                 else st |= PLS_SCHED;
                 S.u.b.doff[j] = (uint16_t) (off >> 1 | (k - off) << 11);
             }
+            // the masks wait in registers until the lists are dead (selects on the uniform
+            // chunk index: the array stays in registers)
+#pragma unroll
+            for (int cc = 0; cc < NCH; cc++)
+                if (c == cc * 64) mreg[cc] = mk;
             carry += rdl(incl, 63);
         }
         wsync();                              // jmap is dead: hgt overlays it
@@ -699,7 +680,7 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> 
             if (j < NJ) {
                 const uint32_t h1 = S.u.b.h.hgt[j] + 1;
                 for (int k = k0; k < k1; k++) {
-                    const int d = S.u.b.dep[k];
+                    const int d = S.u.b.d.dep[k];
                     if (S.u.b.h.hgt[d] < h1) { atomicMax(&S.u.b.h.hgt[d], h1); ch |= d >= c; }
                 }
             }
@@ -709,13 +690,16 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> 
     }
     PPT(9);
     // ---- priority order: height descending, then decode order. The heights go to registers
-    // first: the order and the pass words overlay them (NCH = JCAP / 64 chunks)
+    // first: the order overlays them (NCH = JCAP / 64 chunks). The producer lists are dead:
+    // the masks and the (empty) done bits take their place
     int hreg[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
         const int j = c * 64 + lane;
         hreg[c] = j < NJ ? pl_min((int) S.u.b.h.hgt[j], 63) : -1;
+        if (j < NJ) S.u.b.d.rd.mk[j] = mreg[c];
     }
+    S.u.b.d.rd.drow[lane] = S.u.b.d.rd.dcol[lane] = 0;
     S.u.b.hs[lane] = 0;
     wsync();
 #pragma unroll
@@ -733,21 +717,22 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> 
             if (c * 64 >= NJ) break;
             const int j = c * 64 + lane;
             const int h = hreg[c];
-            uint64_t pend = __ballot(h >= 0);
-            while (pend) {
-                const int hh = rdl(h, __builtin_ctzll(pend));
-                const uint64_t m = __ballot(h == hh);
-                const uint32_t base = S.u.b.hs[hh];
-                if (h == hh) S.u.b.h.os.ord[base + mbcnt(m)] = (uint16_t) j;
-                wsync();
-                if (lane == 0) S.u.b.hs[hh] = base + (uint32_t) __popcll(m);
-                wsync();
-                pend &= ~m;
+            // the chunk's lanes of this lane's height, from one ballot per bit of the height (no
+            // loop over the chunk's distinct heights); the first of them takes the height's
+            // next positions for all, each lane its rank among them
+            uint64_t m = __ballot(h >= 0);
+#pragma unroll
+            for (int b = 0; b < 6; b++) {
+                const uint64_t bal = __ballot((h >> b) & 1);
+                m &= ((h >> b) & 1) ? bal : ~bal;
             }
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
+            uint32_t base = 0;
+            if (h >= 0 && rank == 0) base = atomicAdd(&S.u.b.hs[h], (uint32_t) __popcll(m));
+            base = (uint32_t) __shfl((int) base, __ffsll((unsigned long long) m) - 1);
+            if (h >= 0) S.u.b.h.ord[base + rank] = (uint16_t) j;
         }
     }
-    wsync();
-    for (int j = lane; j < NJ; j += 64) S.u.b.h.os.sch[j] = 0xffff;
     wsync();
     PPT(10);
     // ---- list scheduling (merge_mixed): each pass takes, in priority order, every ready job
@@ -755,24 +740,22 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> 
     uint32_t *gpass = D.passes + (size_t) slot * JCAP;
     PJob *gjob = D.pjobs + (size_t) slot * JCAP;
     int done = 0, npass = 0;
-    // Each lane holds, per chunk c of the priority order, position c * 64 + lane: its job, size,
-    // and the range of its producer list still to see (k: the first producer not known to be
-    // scheduled in an earlier pass; producers scheduled in earlier passes stay so), and bit c
-    // of `pend` while it is unscheduled. A pass then reads LDS only for the sch[] word of each
-    // waiting job's current producer.
-    uint32_t jreg[NCH], kreg[NCH], k1reg[NCH], szreg[NCH];
+    // Each lane holds, per chunk c of the priority order, position c * 64 + lane: its job with
+    // its size code and the done words of its two runs (job | ts << 10 | top run's drow index
+    // << 12 | left run's dcol index << 18; index 0 of the plane where the job has no such run:
+    // its mask is empty there), its masks, and bit c of `pend` while it is unscheduled. A job is
+    // ready when the done words hold every unit of its masks: two independent LDS reads.
+    uint32_t jwreg[NCH], mkreg[NCH];
     uint32_t pend = 0;
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
         const int pos = c * 64 + lane;
-        jreg[c] = kreg[c] = k1reg[c] = 0;
-        szreg[c] = 0;
+        jwreg[c] = mkreg[c] = 0;
         if (pos < NJ) {
-            const uint32_t j = S.u.b.h.os.ord[pos], dw = S.u.b.doff[j];
-            jreg[c] = j;
-            kreg[c] = (dw & 2047) << 1;
-            k1reg[c] = kreg[c] + (dw >> 11);
-            szreg[c] = 4u << ((S.ja[j] >> 2) & 3);
+            const uint32_t j = S.u.b.h.ord[pos], a = S.ja[j];
+            const uint32_t p = a & 3, ux0 = (a >> 12) & 15, uy0 = (a >> 16) & 15;
+            jwreg[c] = j | ((a >> 2) & 3) << 10 | (p * 16 + (uy0 ? uy0 - 1 : 0)) << 12 | (p * 16 + (ux0 ? ux0 - 1 : 0)) << 18;
+            mkreg[c] = S.u.b.d.rd.mk[j];
             pend |= 1u << c;
         }
     }
@@ -784,34 +767,26 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> 
             if (budget < 4) break;
             bool cand = (pend >> c) & 1u;
             if (!__any(cand)) continue;           // every job of this chunk is scheduled
-            if (cand) {
-                uint32_t k = kreg[c];
-                const uint32_t k1 = k1reg[c];
-                while (k < k1 && S.u.b.h.os.sch[S.u.b.dep[k]] < (uint16_t) npass) k++;
-                kreg[c] = k;
-                cand = k == k1;
-            }
+            const uint32_t jw = jwreg[c], mk = mkreg[c];
+            // every lane reads (scheduled and empty positions too: their indices are valid)
+            const uint32_t have = S.u.b.d.rd.drow[(jw >> 12) & 63] | S.u.b.d.rd.dcol[(jw >> 18) & 63] << 16;
+            cand = cand && (have & mk) == mk;
             if (!__any(cand)) continue;           // nothing ready in this chunk
-            const uint32_t j = jreg[c], sz = szreg[c];
-            // takes in priority order by lane-size prefix sums: round 1 takes the longest
-            // prefix of the chunk's ready jobs that fits, later rounds refill the remaining
-            // lanes from the jobs skipped (any packing that respects the producers is exact;
-            // only the pass count depends on it)
-            for (int round = 0; round < 3 && budget >= 4; round++) {
-                if (round && !__any(cand)) break;     // round 1 took every ready job
-                const uint32_t incl = wscan_incl(cand ? sz : 0u, lane);
-                const bool take = cand && incl <= (uint32_t) budget;
-                const uint64_t m = __ballot(take);
-                if (!m) break;
-                if (take) {
-                    cand = false;
-                    pend &= ~(1u << c);
-                    S.u.b.h.os.sch[j] = (uint16_t) npass;
-                    S.u.b.tk[ntake + (int) mbcnt(m)] = (uint16_t) j;
-                }
-                ntake += __popcll(m);
-                budget -= (int) rdl(incl, 63 - __builtin_clzll(m));
+            // takes in priority order by lane-size prefix sums: the longest prefix of the chunk's
+            // ready jobs that fits. (A second round over the jobs skipped can take nothing: the
+            // first one skipped is larger than the lanes left, and so is every prefix sum after
+            // it. Any packing that respects the producers is exact; only the pass count
+            // depends on it.)
+            const uint32_t incl = wscan_incl(cand ? 4u << ((jw >> 10) & 3) : 0u, lane);
+            const bool take = cand && incl <= (uint32_t) budget;
+            const uint64_t m = __ballot(take);
+            if (!m) continue;
+            if (take) {
+                pend &= ~(1u << c);
+                S.u.b.tk[ntake + (int) mbcnt(m)] = (uint16_t) (jw & 1023);
             }
+            ntake += __popcll(m);
+            budget -= (int) rdl(incl, 63 - __builtin_clzll(m));
         }
         wsync();
         if (ntake == 0) { st |= PLS_SCHED; break; }
@@ -832,6 +807,13 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> 
             pj.a = a & ~JA_TRX;
             pj.roff = ((a >> 4) & 1) ? rbase + pl_resid_unit(a & 3, (a >> 12) & 15, (a >> 16) & 15, SSH, SSV) : 0u;
             if (inb(D, (uint32_t) (done + mypos), JCAP, 128u)) gjob[done + mypos] = pj;
+            // the job's units are done for the passes that follow (after the take: the jobs of
+            // one pass do not see each other)
+            const uint32_t n4 = 1u << ((a >> 2) & 3), ux0 = (a >> 12) & 15, uy0 = (a >> 16) & 15, bits = (1u << n4) - 1u;
+            for (uint32_t i = 0; i < n4; i++) {
+                atomicOr(&S.u.b.d.rd.drow[((a & 3) * 16 + uy0 + i) & 63], bits << ux0);
+                atomicOr(&S.u.b.d.rd.dcol[((a & 3) * 16 + ux0 + i) & 63], bits << uy0);
+            }
         }
         if (lane == 0 && inb(D, (uint32_t) npass, JCAP, 256u)) gpass[npass] = (uint32_t) done << 14 | cnt[0] << 9 | cnt[1] << 5 | cnt[2] << 2 | cnt[3];
         done += ntake;

@@ -163,6 +163,60 @@ PL_HD void pl_local_reads(int ux0, int uy0, int n4, int nd, int trx, int units, 
             if (v < unitsv) fn(v * 16 + ux0 - 1);
 }
 
+/* The edges the mode of PJob slot `slot` reads (pl_intra_job's needs by slot) */
+PL_HD int pl_slot_needs(int slot) { return pl_field(0x21371a777a12ull, slot, 4); }
+
+/* Entry of an SB plane's unit map (16 x 16 4x4 units): the intra job covering the unit | units
+ * to the job's right edge << 10 | units to its bottom edge << 13 (0..7 each: a job is at most 8
+ * units wide); PL_JM_NONE (job 1023, above every JCAP) marks a unit no intra job covers. */
+#define PL_JM_ENT(j, r, b) ((uint32_t) (j) | (uint32_t) (r) << 10 | (uint32_t) (b) << 13)
+#define PL_JM_NONE 0xffffu
+
+/* The producers of intra job j inside its SB plane, from the plane's unit map jm[256]: the
+ * units of pl_local_reads' two runs (the top row uy0 - 1 from the top-left unit to ux0 + n4 +
+ * trx, the left column ux0 - 1) that an earlier job d < j covers. Jobs are aligned squares, so
+ * a run's units of one producer are consecutive: the walk jumps from a producer's unit past
+ * that producer's extent and calls fn(d) once per distinct producer (only the top-left unit's
+ * producer can recur in the left run). Uncovered units are stepped over one by one.
+ * Returns the same units as masks: bit u for unit u of the top row, bit 16 + v for unit v of
+ * the left column. Job j may run once the jobs covering every masked unit have run. */
+template <class F>
+PL_HD uint32_t pl_deps(const uint16_t *jm, int j, int ux0, int uy0, int n4, int nd, int trx, int units, int unitsv, F fn)
+{
+    uint32_t mk = 0;
+    int tl = -1;                                       /* producer of the top-left unit */
+    if (uy0 > 0) {
+        const int u1 = pl_min((nd & 2) ? ux0 + n4 + trx : ux0, units);
+        int u = (nd & 4) ? ux0 - 1 : ux0;
+        if (u < 0) u = 0;
+        const uint16_t *row = jm + (uy0 - 1) * 16;
+        while (u < u1) {
+            const uint32_t e = row[u];
+            if (e == PL_JM_NONE) { u++; continue; }
+            const int d = (int) (e & 1023), r = pl_min((int) ((e >> 10) & 7), u1 - 1 - u);
+            if (u == ux0 - 1) tl = d;
+            if (d < j) { fn(d); mk |= ((2u << r) - 1u) << u; }
+            u += (int) ((e >> 10) & 7) + 1;               /* past the producer's right edge */
+        }
+    }
+    if (ux0 > 0 && (nd & 1)) {
+        const int v1 = pl_min(uy0 + n4, unitsv);
+        int v = uy0;
+        const uint16_t *col = jm + ux0 - 1;
+        while (v < v1) {
+            const uint32_t e = col[v * 16];
+            if (e == PL_JM_NONE) { v++; continue; }
+            const int d = (int) (e & 1023), b = pl_min((int) (e >> 13), v1 - 1 - v);
+            if (d < j) {
+                if (d != tl) fn(d);
+                mk |= ((2u << b) - 1u) << (16 + v);
+            }
+            v += (int) (e >> 13) + 1;                     /* past the producer's bottom edge */
+        }
+    }
+    return mk;
+}
+
 /* The units of OTHER SBs the job reads, in frame unit coordinates (fx, fy = the job's
  * first unit): left, top and top-left SBs (above-right reads stay inside the block's
  * columns, vp9recon.c:71-121). fn(ux, uy) with ux >= -1 / uy >= -1 unchecked. */

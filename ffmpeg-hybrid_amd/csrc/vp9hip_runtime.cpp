@@ -3181,6 +3181,107 @@ extern "C" int vp9hip_residn_host(int hb, int tcode, int txtp, int n, const uint
          : residn_blocks<32>(hb, tcode, txtp, n, eobs, coef, res);
 }
 
+// The device planner's intra schedule of one SB (plan_sb of vp9hip_plan.hip) in scalar code, for
+// the tests that compare the device's records with it (include/vp9hip.h states the rules). It
+// shares pl_deps with the kernel and nothing else: readiness here is "every producer in an
+// earlier pass", with the producers read back from the masks' units.
+extern "C" int vp9hip_plan_sched_host(int ss_h, int ss_v, int nj, const uint32_t *ja, uint16_t *order, uint32_t *passes,
+                                      uint32_t *masks)
+{
+    if ((ss_h | ss_v | 1) != 1 || nj < 0 || nj > pl_rcap(ss_h, ss_v) || (nj && !ja) || !order || !passes) return -1;
+    const int CW = 16 >> ss_h, CH = 16 >> ss_v;
+    std::vector<uint16_t> jm(3 * 256, (uint16_t) PL_JM_NONE);
+    struct J { int p, n4, ux0, uy0; };
+    std::vector<J> job((size_t) nj);
+    for (int j = 0; j < nj; j++) {
+        const uint32_t a = ja[j];
+        J &q = job[(size_t) j];
+        q.p = a & 3; q.n4 = 1 << ((a >> 2) & 3); q.ux0 = (a >> 12) & 15; q.uy0 = (a >> 16) & 15;
+        if (q.p > 2 || (q.ux0 & (q.n4 - 1)) || (q.uy0 & (q.n4 - 1))) return -1;
+        const int units = q.p ? CW : 16, unitsv = q.p ? CH : 16;
+        if (q.ux0 >= units || q.uy0 >= unitsv) return -1;
+        for (int v = q.uy0; v < q.uy0 + q.n4 && v < unitsv; v++)
+            for (int u = q.ux0; u < q.ux0 + q.n4 && u < units; u++)
+                jm[(size_t) (q.p * 256 + v * 16 + u)] = (uint16_t) PL_JM_ENT(j, q.ux0 + q.n4 - 1 - u, q.uy0 + q.n4 - 1 - v);
+    }
+    // producers: the jobs at the units of the masks
+    std::vector<std::vector<int>> prod((size_t) nj);
+    for (int j = 0; j < nj; j++) {
+        const J &q = job[(size_t) j];
+        const uint32_t a = ja[j];
+        const uint32_t mk = pl_deps(&jm[(size_t) q.p * 256], j, q.ux0, q.uy0, q.n4, pl_slot_needs((int) ((a >> 8) & 15)),
+                                    (int) ((a >> 30) & 1), q.p ? CW : 16, q.p ? CH : 16, [](int) {});
+        if (masks) masks[j] = mk;
+        for (int b = 0; b < 32; b++) {
+            if (!((mk >> b) & 1)) continue;
+            const int unit = b < 16 ? (q.uy0 - 1) * 16 + b : (b - 16) * 16 + q.ux0 - 1;
+            const int d = jm[(size_t) (q.p * 256 + unit)] & 1023;
+            if (d >= j) return -2;              // a masked unit that no earlier job covers
+            if (std::find(prod[(size_t) j].begin(), prod[(size_t) j].end(), d) == prod[(size_t) j].end()) prod[(size_t) j].push_back(d);
+        }
+    }
+    // heights: producers precede their consumers, so one sweep from the last job is final
+    std::vector<int> h((size_t) nj, 1), pos((size_t) nj), pass_of((size_t) nj, -1);
+    for (int j = nj - 1; j >= 0; j--)
+        for (int d : prod[(size_t) j]) h[(size_t) d] = std::max(h[(size_t) d], h[(size_t) j] + 1);
+    for (int j = 0; j < nj; j++) pos[(size_t) j] = j;
+    std::stable_sort(pos.begin(), pos.end(), [&](int x, int y) { return std::min(h[(size_t) x], 63) > std::min(h[(size_t) y], 63); });
+    int done = 0, npass = 0;
+    while (done < nj) {
+        int budget = 64;
+        std::vector<int> tk;
+        for (int c = 0; c < nj && budget >= 4; c += 64) {
+            int sum = 0;
+            for (int i = c; i < std::min(c + 64, nj); i++) {
+                const int j = pos[(size_t) i];
+                if (pass_of[(size_t) j] >= 0) continue;
+                bool ready = true;
+                for (int d : prod[(size_t) j]) ready = ready && pass_of[(size_t) d] >= 0 && pass_of[(size_t) d] < npass;
+                if (!ready) continue;
+                if (sum + 4 * job[(size_t) j].n4 > budget) break;      // the prefix ends at the first that does not fit
+                sum += 4 * job[(size_t) j].n4;
+                tk.push_back(j);
+            }
+            budget -= sum;
+        }
+        if (tk.empty()) return -2;
+        for (int j : tk) pass_of[(size_t) j] = npass;
+        uint32_t cnt[4] = { 0, 0, 0, 0 };
+        int at = done;
+        for (int n4 = 8; n4; n4 >>= 1)
+            for (int j : tk)
+                if (job[(size_t) j].n4 == n4) { order[at++] = (uint16_t) j; cnt[n4 == 8 ? 3 : n4 == 4 ? 2 : n4 == 2 ? 1 : 0]++; }
+        passes[npass++] = (uint32_t) done << 14 | cnt[0] << 9 | cnt[1] << 5 | cnt[2] << 2 | cnt[3];
+        done = at;
+    }
+    return npass;
+}
+
+// The current slot's device-planned intra schedule, copied to the host (include/vp9hip.h).
+extern "C" int vp9hip_test_plan_records(vp9hip_ctx *c, int cap_slots, int *jcap, uint32_t *sbs, uint32_t *wgs,
+                                        uint32_t *passes, uint32_t *jobs_a)
+{
+    if (!c) return VP9HIP_EINVAL;
+    Staged &s = c->stg;
+    if (!s.dev || !s.planned || !s.arena || !s.nslots || s.jcap <= 0) return VP9HIP_EINVAL;
+    static_assert(sizeof(SBRec) == 12 && sizeof(WGRec) == 16 && sizeof(PJob) == 8, "the layouts vp9hip.h describes");
+    const size_t ns = s.nslots, jc = (size_t) s.jcap;
+    if (jcap) *jcap = s.jcap;
+    if (!sbs && !wgs && !passes && !jobs_a) return (int) ns;
+    if (cap_slots < 0 || (size_t) cap_slots < ns) return VP9HIP_EINVAL;
+    hipSetDevice(c->dev);
+    HIPCHK(hipDeviceSynchronize());
+    if (sbs) HIPCHK(hipMemcpy(sbs, s.arena + s.o_sbs, ns * sizeof(SBRec), hipMemcpyDeviceToHost));
+    if (wgs) HIPCHK(hipMemcpy(wgs, s.arena + s.o_wgs, ns * sizeof(WGRec), hipMemcpyDeviceToHost));
+    if (passes) HIPCHK(hipMemcpy(passes, s.arena + s.o_passes, ns * jc * 4, hipMemcpyDeviceToHost));
+    if (jobs_a) {
+        std::vector<PJob> pj(ns * jc);
+        HIPCHK(hipMemcpy(pj.data(), s.arena + s.o_pjobs, ns * jc * sizeof(PJob), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < ns * jc; k++) jobs_a[k] = pj[k].a;
+    }
+    return (int) ns;
+}
+
 extern "C" int vp9hip_device_info(int device, char *pci_bus_id, int len, char *name, int name_len)
 {
     int n = 0;

@@ -123,6 +123,27 @@ void vp9hip_close(vp9hip_ctx *ctx);
  * lfr_spin = n bounds the row loop filter's hand-off waits to n polls (forcing its timeout
  * path). No reference counterpart; never called in production. */
 void vp9hip_test_hooks(int reject_batch, uint32_t lfr_spin);
+/* Test only: the device planner's intra schedule of the current slot's batch, copied to the
+ * host after the device went idle. Per SB slot s (cap_slots of them at least): sbs + 3 s =
+ * frame, sbx | sby << 16, tile_x0 | flags << 16; wgs + 4 s = first job, first pass word,
+ * njobs | npass << 16, SB slot; the SB's pass words (first job << 14 | 4x4 jobs << 9 | 8x8 << 5 |
+ * 16x16 << 2 | 32x32) at passes + job capacity * s and its job words (PJob.a) in pass order at
+ * jobs_a + job capacity * s. Any pointer may be NULL. Returns the number of SB slots (*jcap:
+ * the job capacity per SB) or a negative error; VP9HIP_EINVAL for a batch the host planned. */
+int  vp9hip_test_plan_records(vp9hip_ctx *ctx, int cap_slots, int *jcap, uint32_t *sbs, uint32_t *wgs,
+                              uint32_t *passes, uint32_t *jobs_a);
+/* Test only, no device: the device planner's schedule of one SB restated in scalar code. ja[nj]:
+ * the SB's intra jobs in decode order, each plane | tx size << 2 | mode slot << 8 | x4 << 12 |
+ * y4 << 16 | trx << 30 (the PJob word's fields; trx: the 4x4 top-right lies inside the block).
+ * Producers of a job: the earlier jobs covering the units of its top and left runs (masks[j]:
+ * those units, bit u of the top row, bit 16 + v of the left column); heights: longest path to a
+ * sink, at most 63; order: height descending, then index; per pass, chunk by chunk of 64 in that
+ * order, the longest prefix of the ready jobs that fits the lanes left of 64; a pass's jobs
+ * by size 32, 16, 8, 4, take order within a size. order[nj]: the decode index of the job at each
+ * position of the SB's job array; passes: the pass words. Returns the number of passes, -1 for
+ * bad arguments, -2 if a mask names a unit no earlier job covers or a pass can take no job. */
+int  vp9hip_plan_sched_host(int ss_h, int ss_v, int nj, const uint32_t *ja, uint16_t *order, uint32_t *passes,
+                            uint32_t *masks);
 
 /* Allocate `nbufs` device frame buffers of w x h (padded to 64 internally). */
 int  vp9hip_configure(vp9hip_ctx *ctx, int width, int height, int bpp, int ss_h, int ss_v,
