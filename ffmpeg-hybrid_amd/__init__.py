@@ -286,6 +286,7 @@ def lib():
     L.vp9hip_intra_job_host.argtypes = [ctypes.c_int] * 15 + [ctypes.POINTER(ctypes.c_int32)]
     L.vp9hip_intra_job_dev.argtypes = [ctypes.c_int] * 13 + [ctypes.POINTER(ctypes.c_int32)]
     L.vp9hip_plan_sched_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4
+    L.vp9hip_plan_heights_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2
     L.vp9hip_test_plan_records.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)] + [ctypes.c_void_p] * 4
     _lib_handle = L
     return L
@@ -382,6 +383,16 @@ def plan_sched_host(ss_h, ss_v, ja):
     npass = _check("vp9hip_plan_sched_host", lib().vp9hip_plan_sched_host(ss_h, ss_v, n, ja.ctypes.data, order.ctypes.data,
                                                                          passes.ctypes.data, masks.ctypes.data))
     return order, passes[:npass].copy(), masks
+
+
+def plan_heights_host(ss_h, ss_v, ja):
+    """The heights (longest path to a sink, unclamped) the device planner's relaxation gives the
+    jobs of one SB, from the kernel's routine run on the host (vp9hip_plan_heights_host); ja as
+    for plan_sched_host."""
+    ja = np.ascontiguousarray(ja, np.uint32)
+    heights = np.empty(len(ja), np.uint32)
+    _check("vp9hip_plan_heights_host", lib().vp9hip_plan_heights_host(ss_h, ss_v, len(ja), ja.ctypes.data, heights.ctypes.data))
+    return heights
 
 
 def intra_txfm_type(mode):

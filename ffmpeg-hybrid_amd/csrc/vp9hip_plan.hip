@@ -443,7 +443,7 @@ template <int JCAP> struct alignas(16) PlanLds {   // 16: jmap rows are stored 1
                     uint32_t drow[64], dcol[64];
                 } rd;
             } d;
-            uint32_t hs[64];              // height histogram -> list starts
+            uint32_t hs[64];              // height histogram -> list starts (before: the heights' spare words)
             uint16_t tk[16];              // jobs taken by the pass being built
         } b;
     } u;
@@ -471,12 +471,11 @@ DEV uint32_t wor(uint32_t v) { return rdl(wscan_dpp<OP_OR>(v), 63); }
 // (an atomic in between would turn the later uniform loads into dependent vector loads).
 // ja: k_pjplan's LDS job words; returns the SB's intra job count
 template <int SSH, int SSV>
-DEV int pjob_sb(const PlanDev &D, const PlanFrame &F, uint32_t *ja)
+DEV int pjob_sb(const PlanDev &D, const PlanFrame &F, const SbGeo &G, uint32_t *ja)
 {
     constexpr int CW = 16 >> SSH, CH = 16 >> SSV, JCAP = 256 + 2 * CW * CH, NCH = 6;
-    const int s = blockIdx.x, lane = threadIdx.x;
+    const int lane = threadIdx.x;
     unsigned long long pt0 = D.prof ? clock64() : 0;
-    const SbGeo G = sb_geo(F, s);
     const uint32_t slot = G.slot;
     uint32_t st = 0, bf = 0;                  // PLS_* bits, status[1] bits of failed bounds
     if (slot >= D.nslots) bf |= 4u;
@@ -584,12 +583,11 @@ static_assert(sizeof(RJob) == 16 && offsetof(RJob, eob) == 8 && offsetof(RJob, f
 // per C3 batch. By its counters the kernel is bound by scalar issue: about 4,300 SALU per wave at
 // 22 waves per CU)
 template <int SSH, int SSV>
-DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> &S, int nj)
+DEV void plan_sb(const PlanDev &D, const PlanFrame &F, const SbGeo &G, PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> &S, int nj)
 {
     constexpr int CW = 16 >> SSH, CH = 16 >> SSV, JCAP = 256 + 2 * CW * CH, NCH = JCAP / 64;
-    const int s = blockIdx.x, lane = threadIdx.x;
+    const int lane = threadIdx.x;
     unsigned long long pt0 = D.prof ? clock64() : 0;
-    const SbGeo G = sb_geo(F, s);
     const uint32_t slot = G.slot;
     const uint32_t rbase = slot * D.rcap;
     uint32_t st = 0;
@@ -653,7 +651,8 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> 
                 uint32_t k = off;
                 if (off + cap <= 4u * JCAP) mk = deps_of(j, [&](int d) { if (k < off + cap) S.u.b.d.dep[k++] = (uint16_t) d; });
                 else st |= PLS_SCHED;
-                S.u.b.doff[j] = (uint16_t) (off >> 1 | (k - off) << 11);
+                // (an empty list starts at 0: the heights read a list's first four entries unasked)
+                S.u.b.doff[j] = (uint16_t) (k > off ? off >> 1 | (k - off) << 11 : 0u);
             }
             // the masks wait in registers until the lists are dead (selects on the uniform
             // chunk index: the array stays in registers)
@@ -670,23 +669,17 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, PlanLds<256 + 2 * (16 >> 
     // ---- heights (longest path to a sink). Producers precede their consumers (d < j), so
     // the chunks of 64 jobs are finished last to first: a chunk's consumers in later chunks
     // are final, and the chunk relaxes until none of its own jobs rises (at most one round
-    // per job of a chain inside it); its last round pushes final heights to every producer
-    for (int c = ((NJ - 1) & ~63); c >= 0; c -= 64) {
-        const int j = c + lane;
-        const uint32_t dw = j < NJ ? S.u.b.doff[j] : 0u;
-        const int k0 = (int) (dw & 2047) << 1, k1 = k0 + (int) (dw >> 11);
-        for (int it = 0; it < 65; it++) {
-            bool ch = false;                  // a job of this chunk rose
-            if (j < NJ) {
-                const uint32_t h1 = S.u.b.h.hgt[j] + 1;
-                for (int k = k0; k < k1; k++) {
-                    const int d = S.u.b.d.dep[k];
-                    if (S.u.b.h.hgt[d] < h1) { atomicMax(&S.u.b.h.hgt[d], h1); ch |= d >= c; }
-                }
-            }
-            wsync();
-            if (!__any(ch)) break;
-        }
+    // per job of a chain inside it); its last round pushes final heights to every producer.
+    // pl_heights_chunk's round reads the lane's height and issues four returning maxima from
+    // registers, one wait; a producer that does not exist is a word of hs, which is not live yet
+    // (VP9HIP_PLAN_DBG bit 4, timing only: no relaxation, every height stays 1)
+    {
+        uint32_t *hgt = S.u.b.h.hgt;
+        const uint32_t spare = (uint32_t) (S.u.b.hs - hgt);
+        auto each = [&](auto fn) { const bool r = fn(lane, 0); wsync(); return __any(r) != 0; };
+        auto amax = [&](uint32_t i, uint32_t v) { return atomicMax(&hgt[i], v); };
+        for (int c = (D.dbg & 16) ? -1 : ((NJ - 1) & ~63); c >= 0; c -= 64)
+            pl_heights_chunk<1>(hgt, S.u.b.d.dep, S.u.b.doff, c, NJ, spare, each, amax);
     }
     PPT(9);
     // ---- priority order: height descending, then decode order. The heights go to registers
@@ -880,9 +873,10 @@ __global__ __launch_bounds__(64) void k_pjplan(PlanDev D)
     __shared__ PlanLds<256 + 2 * (16 >> SSH) * (16 >> SSV)> S;
     const PlanFrame F = D.frames[blockIdx.y];     // by value, before any store: one batch of scalar loads
     if ((int) blockIdx.x >= F.sb_cols * F.sb_rows) return;
-    const int nj = pjob_sb<SSH, SSV>(D, F, S.ja);
+    const SbGeo G = sb_geo(F, blockIdx.x);        // once for both halves (tile column loop, divisions)
+    const int nj = pjob_sb<SSH, SSV>(D, F, G, S.ja);
     wsync();
-    plan_sb<SSH, SSV>(D, F, S, nj);
+    plan_sb<SSH, SSV>(D, F, G, S, nj);
 }
 
 // ------------------------------------------------------------------ k_plmc

@@ -217,6 +217,63 @@ PL_HD uint32_t pl_deps(const uint16_t *jm, int j, int ux0, int uy0, int n4, int 
     return mk;
 }
 
+/* Heights (longest path to a sink, the list-scheduling priority) of one chunk of 64 jobs,
+ * c .. c + 63 of nj: the chunk relaxes until none of its own jobs rises, and its last round
+ * pushes final heights to every producer. Producers precede their consumers, so the caller
+ * finishes the chunks last to first, with every hgt[j] = 1 before the first.
+ * The lists are the planners': job j's producers are dep[2 (doff[j] & 2047) ..], doff[j] >> 11
+ * of them, and a list's first four entries are readable whatever its length (every list has
+ * room for four). A lane keeps them in two registers for all rounds; one that does not exist
+ * is word spare + lane of hgt, outside the heights and above every job index, so a round is
+ * four returning maxima back to back with no read before them and no branch: a job of the chunk
+ * rose where the old value is below the new one and c <= d < j, which no spare word meets.
+ * Entries past the fourth (a 16x16 or 32x32 job beside small ones) take the loop, in chunks
+ * that hold such a job only.
+ * One routine, two executors: each(fn) runs fn(lane, r) for the chunk's 64 lanes and returns
+ * the OR of the results, with r the lane's slot of the NL-lane state (a wave: its own lane and
+ * slot 0, then the wave's any; the host: a loop over 64 slots); amax(i, v) is
+ * hgt[i] = max(hgt[i], v) and returns the old value. */
+template <int NL, class EACH, class AMAX>
+PL_HD void pl_heights_chunk(uint32_t *hgt, const uint16_t *dep, const uint16_t *doff, int c, int nj, uint32_t spare, EACH each,
+                            AMAX amax)
+{
+    uint32_t e01[NL], e23[NL];
+    const bool longl = each([&](int lane, int r) {
+        const int j = c + lane;
+        const uint32_t dw = j < nj ? doff[j] : 0u, sp = spare + (uint32_t) lane;
+        const int k0 = (int) (dw & 2047) << 1, n = (int) (dw >> 11);
+        const uint32_t d0 = dep[k0], d1 = dep[k0 + 1], d2 = dep[k0 + 2], d3 = dep[k0 + 3];
+        e01[r] = (n > 0 ? d0 : sp) | (n > 1 ? d1 : sp) << 16;
+        e23[r] = (n > 2 ? d2 : sp) | (n > 3 ? d3 : sp) << 16;
+        return n > 4;
+    });
+    for (int it = 0; it < 65; it++) {
+        const bool rose = each([&](int lane, int r) {
+            const uint32_t j = (uint32_t) (c + lane), lo = (uint32_t) c;
+            const uint32_t h1 = hgt[(int) j < nj ? j : spare + (uint32_t) lane] + 1;
+            const uint32_t d0 = e01[r] & 0xffff, d1 = e01[r] >> 16, d2 = e23[r] & 0xffff, d3 = e23[r] >> 16;
+            const uint32_t o0 = amax(d0, h1), o1 = amax(d1, h1), o2 = amax(d2, h1), o3 = amax(d3, h1);
+            /* the least old value among the producers inside the chunk (the tests on d do not
+             * change from round to round: selects and minima, one compare per round) */
+            const uint32_t jl = j - lo;                    /* lo <= d < j as one unsigned compare */
+            const uint32_t x0 = d0 - lo < jl ? o0 : ~0u, x1 = d1 - lo < jl ? o1 : ~0u;
+            const uint32_t x2 = d2 - lo < jl ? o2 : ~0u, x3 = d3 - lo < jl ? o3 : ~0u;
+            const uint32_t xa = x0 < x1 ? x0 : x1, xb = x2 < x3 ? x2 : x3;
+            bool ch = (xa < xb ? xa : xb) < h1;
+            if (longl && (int) j < nj) {
+                const uint32_t dw = doff[j];
+                const int k0 = (int) (dw & 2047) << 1, k1 = k0 + (int) (dw >> 11);
+                for (int k = k0 + 4; k < k1; k++) {
+                    const uint32_t d = dep[k];
+                    if (hgt[d] < h1) { amax(d, h1); ch |= d >= lo; }
+                }
+            }
+            return ch;
+        });
+        if (!rose) break;
+    }
+}
+
 /* The units of OTHER SBs the job reads, in frame unit coordinates (fx, fy = the job's
  * first unit): left, top and top-left SBs (above-right reads stay inside the block's
  * columns, vp9recon.c:71-121). fn(ux, uy) with ux >= -1 / uy >= -1 unchecked. */

@@ -3257,6 +3257,44 @@ extern "C" int vp9hip_plan_sched_host(int ss_h, int ss_v, int nj, const uint32_t
     return npass;
 }
 
+// The heights k_pjplan gives an SB's intra jobs, from the kernel's own routine
+// (pl_heights_chunk, a loop over 64 slots for the wave's lanes) over lists laid out as plan_sb
+// lays them out: job j's at the prefix sum of the per-size bounds 2n + 2. heights[j] is not
+// clamped (the kernel clamps at 63 when it sorts).
+extern "C" int vp9hip_plan_heights_host(int ss_h, int ss_v, int nj, const uint32_t *ja, uint32_t *heights)
+{
+    if ((ss_h | ss_v | 1) != 1 || nj < 0 || nj > pl_rcap(ss_h, ss_v) || (nj && (!ja || !heights))) return -1;
+    const int CW = 16 >> ss_h, CH = 16 >> ss_v, JCAP = pl_rcap(ss_h, ss_v);
+    std::vector<uint16_t> jm(3 * 256, (uint16_t) PL_JM_NONE), dep((size_t) 4 * JCAP, 0), doff((size_t) JCAP + 1, 0);
+    for (int j = 0; j < nj; j++) {
+        const uint32_t a = ja[j];
+        const int p = a & 3, n4 = 1 << ((a >> 2) & 3), ux0 = (a >> 12) & 15, uy0 = (a >> 16) & 15;
+        if (p > 2 || (ux0 & (n4 - 1)) || (uy0 & (n4 - 1)) || ux0 >= (p ? CW : 16) || uy0 >= (p ? CH : 16)) return -1;
+        for (int v = uy0; v < uy0 + n4 && v < (p ? CH : 16); v++)
+            for (int u = ux0; u < ux0 + n4 && u < (p ? CW : 16); u++)
+                jm[(size_t) (p * 256 + v * 16 + u)] = (uint16_t) PL_JM_ENT(j, ux0 + n4 - 1 - u, uy0 + n4 - 1 - v);
+    }
+    uint32_t off = 0;
+    for (int j = 0; j < nj; j++) {
+        const uint32_t a = ja[j], cap = 2u * (1u << ((a >> 2) & 3)) + 2u;
+        const int p = a & 3;
+        if (off + cap > 4u * (uint32_t) JCAP) return -2;          // overlapping jobs
+        uint32_t k = off;
+        pl_deps(&jm[(size_t) p * 256], j, (a >> 12) & 15, (a >> 16) & 15, 1 << ((a >> 2) & 3), pl_slot_needs((int) ((a >> 8) & 15)),
+                (int) ((a >> 30) & 1), p ? CW : 16, p ? CH : 16, [&](int d) { if (k < off + cap) dep[k++] = (uint16_t) d; });
+        doff[(size_t) j] = (uint16_t) (k > off ? off >> 1 | (k - off) << 11 : 0u);
+        off += cap;
+    }
+    std::vector<uint32_t> hgt((size_t) JCAP + 128, 0);           // the heights, then the lanes' spare words
+    for (int j = 0; j < nj; j++) hgt[(size_t) j] = 1;
+    auto each = [&](auto fn) { bool any = false; for (int l = 0; l < 64; l++) any |= fn(l, l); return any; };
+    auto amax = [&](uint32_t i, uint32_t v) { const uint32_t old = hgt[i]; hgt[i] = std::max(old, v); return old; };
+    for (int c = (nj - 1) & ~63; c >= 0; c -= 64)
+        pl_heights_chunk<64>(hgt.data(), dep.data(), doff.data(), c, nj, (uint32_t) JCAP + 64, each, amax);
+    for (int j = 0; j < nj; j++) heights[j] = hgt[(size_t) j];
+    return 0;
+}
+
 // The current slot's device-planned intra schedule, copied to the host (include/vp9hip.h).
 extern "C" int vp9hip_test_plan_records(vp9hip_ctx *c, int cap_slots, int *jcap, uint32_t *sbs, uint32_t *wgs,
                                         uint32_t *passes, uint32_t *jobs_a)

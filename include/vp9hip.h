@@ -144,6 +144,10 @@ int  vp9hip_test_plan_records(vp9hip_ctx *ctx, int cap_slots, int *jcap, uint32_
  * bad arguments, -2 if a mask names a unit no earlier job covers or a pass can take no job. */
 int  vp9hip_plan_sched_host(int ss_h, int ss_v, int nj, const uint32_t *ja, uint16_t *order, uint32_t *passes,
                             uint32_t *masks);
+/* Test only, no device: the heights of the same jobs from the device planner's own relaxation
+ * (the routine k_pjplan runs, a loop over 64 slots in place of the wave's lanes): heights[nj],
+ * longest path to a sink, not clamped. Returns 0, -1 for bad arguments, -2 for overlapping jobs. */
+int  vp9hip_plan_heights_host(int ss_h, int ss_v, int nj, const uint32_t *ja, uint32_t *heights);
 
 /* Allocate `nbufs` device frame buffers of w x h (padded to 64 internally). */
 int  vp9hip_configure(vp9hip_ctx *ctx, int width, int height, int bpp, int ss_h, int ss_v,
