@@ -154,7 +154,8 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9hip_decoder_send_packet", "vp9hip_decoder_receive_frame", "vp9hip_decoder_release",
                "vp9hip_decoder_flush",
                "vp9h_stream_set_color", "vp9hip_out_layout", "vp9hip_out_coefs", "vp9hip_convert_frames",
-               "vp9hip_decoder_convert", "vp9hip_convert_frames_scaled", "vp9hip_decoder_convert_scaled"]
+               "vp9hip_decoder_convert", "vp9hip_convert_frames_scaled", "vp9hip_decoder_convert_scaled",
+               "vp9hip_convert_frames_resampled", "vp9hip_decoder_convert_resampled", "vp9hip_resample_weights"]
 
 
 def lib():
@@ -281,6 +282,13 @@ def lib():
     L.vp9hip_decoder_convert_scaled.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_void_p]
+    L.vp9hip_convert_frames_resampled.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(OutDesc),
+                                                  ctypes.POINTER(Resample), ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_decoder_convert_resampled.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int, ctypes.c_int,
+                                                   ctypes.POINTER(Resample), ctypes.c_void_p, ctypes.c_int64,
+                                                   ctypes.c_int64, ctypes.c_void_p]
+    L.vp9hip_resample_weights.argtypes = [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int32),
+                                                                ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
     L.vp9hip_resid4_host.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
     L.vp9hip_residn_host.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
     L.vp9hip_intra_job_host.argtypes = [ctypes.c_int] * 15 + [ctypes.POINTER(ctypes.c_int32)]
@@ -329,8 +337,21 @@ class OutDesc(ctypes.Structure):
                 ("frame_stride", ctypes.c_int64)]
 
 
+class Rect(ctypes.Structure):
+    """vp9hip_rect: (x, y, w, h) in luma samples."""
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32)]
+
+
+class Resample(ctypes.Structure):
+    """vp9hip_resample: filter, output size, per-frame rectangles (or NULL) and the fill codes."""
+    _fields_ = [("filter", ctypes.c_int32), ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32),
+                ("src_rects", ctypes.POINTER(Rect)), ("dst_rects", ctypes.POINTER(Rect)), ("fill", ctypes.c_int32 * 3)]
+
+
 # VP9HIP_OUT_*: the names Device.convert / Decoder.convert take
 OUT_FORMATS = {"semiplanar": 0, "rgb24": 1, "rgbp_u8": 2, "rgbp_f16": 3}
+# VP9HIP_FILTER_*: the names of their filter argument
+FILTERS = {"box": 0, "triangle": 1}
 
 
 def _check(fn, r):
@@ -609,6 +630,70 @@ def out_layout(fmt, width, height, bpp=8, ss_h=1, ss_v=1, pitch=0, frame_stride=
     return n, p.value, tuple(off)
 
 
+def resample_weights(filter, n_src, n_out, o):
+    """(first source index, weights, their sum D) of output index o of an axis of n_src samples
+    resampled to n_out with `filter` ("box" / "triangle" or a VP9HIP_FILTER_* code): the
+    library's statement of the filters' definition (vp9hip_resample_weights, host only)."""
+    f = FILTERS.get(filter, filter)
+    n = _check("vp9hip_resample_weights", lib().vp9hip_resample_weights(int(f), int(n_src), int(n_out), int(o), None, None, 0, None))
+    first, d, w = ctypes.c_int(), ctypes.c_int64(), (ctypes.c_int32 * n)()
+    _check("vp9hip_resample_weights", lib().vp9hip_resample_weights(int(f), int(n_src), int(n_out), int(o), ctypes.byref(first),
+                                                                    w, n, ctypes.byref(d)))
+    return first.value, list(w), d.value
+
+
+def letterbox_rect(w, h, OW, OH, align=(1, 1)):
+    """The destination rectangle (dx, dy, dw, dh) that places a w x h picture inside OW x OH
+    at its aspect ratio, centred. In integers: if w OH >= h OW the picture takes the full
+    width, dw = OW and dh = max(1, (h OW + w // 2) // w) (the height rounded to nearest);
+    otherwise the full height, dh = OH and dw = max(1, (w OH + h // 2) // h). Then
+    dx = (OW - dw) // 2 and dy = (OH - dh) // 2, each rounded down to a multiple of align[0] /
+    align[1] (the subsampling, (2, 2) for a 4:2:0 semi-planar output)."""
+    w, h, OW, OH = int(w), int(h), int(OW), int(OH)
+    if min(w, h, OW, OH) < 1 or min(align) < 1:
+        raise ValueError("letterbox_rect: sizes and alignment must be positive")
+    if w * OH >= h * OW:
+        dw, dh = OW, max(1, (h * OW + w // 2) // w)       # <= OH: h OW <= w OH
+    else:
+        dw, dh = max(1, (w * OH + h // 2) // h), OH       # <= OW likewise
+    dx, dy = (OW - dw) // 2, (OH - dh) // 2
+    return dx // align[0] * align[0], dy // align[1] * align[1], dw, dh
+
+
+def _rect_array(name, rects, n):
+    """n vp9hip_rects of a rectangle argument: one 4-tuple for every frame, or n of them."""
+    rects = list(rects)
+    if len(rects) == 4 and not hasattr(rects[0], "__len__"):
+        rects = [rects] * n
+    if len(rects) != n or any(len(r) != 4 for r in rects):
+        raise ValueError("convert: %s takes one (x, y, w, h) or one per frame (%d)" % (name, n))
+    return (Rect * n)(*[Rect(*(int(v) for v in r)) for r in rects])
+
+
+def _resample_arg(n, resize, filter, src_rects, dst_rects, fill, bpp, colorspace, full_range):
+    """The vp9hip_resample of convert()'s filter / src_rects / dst_rects / fill arguments, or
+    None when none of them is given; they need resize. The arrays it points to are kept alive
+    as attributes of the struct."""
+    if filter == "box" and src_rects is None and dst_rects is None and fill is None:
+        return None
+    if resize is None:
+        raise ValueError("convert: filter, src_rects, dst_rects and fill need resize=(OW, OH)")
+    if filter not in FILTERS:
+        raise ValueError("convert: filter is 'box' or 'triangle'")
+    ow, oh = (int(x) for x in resize)
+    rs = Resample(FILTERS[filter], ow, oh)
+    if src_rects is not None:
+        rs._src = _rect_array("src_rects", src_rects, n)
+        rs.src_rects = ctypes.cast(rs._src, ctypes.POINTER(Rect))
+    if dst_rects is not None:
+        rs._dst = _rect_array("dst_rects", dst_rects, n)
+        rs.dst_rects = ctypes.cast(rs._dst, ctypes.POINTER(Rect))
+    if fill is None:      # black, by the range in effect
+        fill = (0, 0, 0) if colorspace == 7 else (0 if full_range else 16 << (bpp - 8), 1 << (bpp - 1), 1 << (bpp - 1))
+    rs.fill[:] = [int(v) for v in fill]
+    return rs
+
+
 def alloc_planes(width, height, bpp, ss_h=1, ss_v=1, pad=64):
     """Host planes padded to 64 luma pixels (the layout the oracle expects)."""
     dt = np.uint8 if bpp == 8 else np.uint16
@@ -884,7 +969,7 @@ class Device:
         return ow, oh
 
     def convert(self, bufs, fmt, colorspace=2, full_range=False, size=None, out=None, stream=None,
-                pitch=0, frame_stride=0, resize=None):
+                pitch=0, frame_stride=0, resize=None, filter="box", src_rects=None, dst_rects=None, fill=None):
         """Convert device buffers `bufs` (any order) to `fmt` on the GPU (vp9hip_convert_frames):
         "rgb24" -> (N,H,W,3) uint8, "rgbp_u8" -> (N,3,H,W) uint8, "rgbp_f16" -> (N,3,H,W)
         float16 in [0,1], "semiplanar" -> (y, uv) views of one allocation, (N,H,W) and
@@ -895,7 +980,13 @@ class Device:
         as in vp9hip_out_desc (0 = tight). resize=(OW, OH) resamples the visible picture to OW x OH
         with the exact box filter in the same launch (vp9hip_convert_frames_scaled; the shapes,
         `out`, pitch and frame_stride are then the output's, the UV view (N,OCH,OCW,2)); a given
-        resize always takes that kernel, None is the unscaled one. Runs in the order of torch's current stream (or on
+        resize always takes that kernel, None is the unscaled one. With resize, filter="triangle"
+        (antialiased bilinear; "box" is the default), src_rects (one (x, y, w, h) in luma samples,
+        or one per frame: the region resampled instead of the whole visible picture), dst_rects
+        (likewise: where in the OW x OH output the picture goes, see letterbox_rect) and fill (the
+        three sample codes written elsewhere; default black by the range in effect) take
+        vp9hip_convert_frames_resampled, the exact definitions of include/vp9hip.h; any of them
+        without resize is a ValueError. Runs in the order of torch's current stream (or on
         `stream`, a hipStream_t handle; see _enqueue_for_torch) and does not wait: order it after the frames' producer (sync(), or
         vp9hip_slot_stream_wait), as for frame_tensors. Needs torch imported before the library
         was loaded (see _torch_first)."""
@@ -906,19 +997,26 @@ class Device:
         bufs = [int(b) for b in bufs]
         w, h = size if size is not None else (self.w, self.h)
         d = OutDesc(OUT_FORMATS[fmt], int(colorspace), int(bool(full_range)), int(w), int(h), int(pitch), int(frame_stride))
-        fn = "vp9hip_convert_frames" if resize is None else "vp9hip_convert_frames_scaled"
+        rs = _resample_arg(len(bufs), resize, filter, src_rects, dst_rects, fill, self.bpp, int(colorspace), full_range)
+        fn = ("vp9hip_convert_frames" if resize is None else
+              "vp9hip_convert_frames_scaled" if rs is None else "vp9hip_convert_frames_resampled")
         if not bufs:
             raise Vp9HipError(fn, EINVAL)
         ow, oh = (w, h) if resize is None else self._resize_arg(fn, resize)
         flat, res, _, _ = self._convert_out(len(bufs), fmt, ow, oh, self.bpp, self.ss_h, self.ss_v, out, pitch, frame_stride)
         arr = (ctypes.c_int * len(bufs))(*bufs)
-        if resize is None:
+        if rs is not None:
+            call = lambda st: lib().vp9hip_convert_frames_resampled(self._c, arr, len(bufs), ctypes.byref(d), ctypes.byref(rs),
+                                                                    flat.data_ptr(), st)
+        elif resize is None:
             call = lambda st: lib().vp9hip_convert_frames(self._c, arr, len(bufs), ctypes.byref(d), flat.data_ptr(), st)
         else:
             call = lambda st: lib().vp9hip_convert_frames_scaled(self._c, arr, len(bufs), ctypes.byref(d), ow, oh,
                                                                  flat.data_ptr(), st)
         _check(fn, _enqueue_for_torch(self.frame_device(0)[3], stream, call))
         return res
+
+    letterbox_rect = staticmethod(letterbox_rect)
 
     def upload(self, buf, planes):
         planes = [np.ascontiguousarray(p) for p in planes]
@@ -1035,28 +1133,35 @@ class Decoder:
     def context(self):
         return ctypes.c_void_p(lib().vp9hip_decoder_context(self._d))
 
-    def convert(self, infos, fmt, out=None, resize=None):
+    def convert(self, infos, fmt, out=None, resize=None, filter="box", src_rects=None, dst_rects=None, fill=None):
         """Convert the frames of receive_frame(download=False) (their DecodedFrameInfos, all of
         one size, colour space and range) to `fmt` as Device.convert does, with the frames' own
         colour description (vp9hip_decoder_convert; with resize=(OW, OH)
-        vp9hip_decoder_convert_scaled), on torch's current stream; waits for it and releases
+        vp9hip_decoder_convert_scaled; with filter / src_rects / dst_rects / fill as well, which
+        mean what they mean there, vp9hip_decoder_convert_resampled), on torch's current stream; waits for it and releases
         the buffers. Returns the tensor(s)."""
         if not _torch_first:
             raise Vp9HipUnavailable("convert: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
                                     "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
         import torch
         infos = list(infos)
-        fn = "vp9hip_decoder_convert" if resize is None else "vp9hip_decoder_convert_scaled"
+        f = infos[0] if infos else DecodedFrameInfo()
+        cs = 2 if f.colorspace in (0, 6) else f.colorspace
+        rs = _resample_arg(len(infos), resize, filter, src_rects, dst_rects, fill, f.bpp or 8, cs, f.full_range)
+        fn = ("vp9hip_decoder_convert" if resize is None else
+              "vp9hip_decoder_convert_scaled" if rs is None else "vp9hip_decoder_convert_resampled")
         if not infos:
             raise Vp9HipError(fn, EINVAL)
         arr = (DecodedFrameInfo * len(infos))(*infos)
-        f = infos[0]
         ow, oh = (f.width, f.height) if resize is None else Device._resize_arg(fn, resize)
         flat, res, pitch, stride = Device._convert_out(len(infos), fmt, ow, oh, f.bpp, f.ss_h, f.ss_v, out, 0, 0)
         main = ctypes.c_void_p()
         _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
                                                                 (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
-        if resize is None:
+        if rs is not None:
+            call = lambda st: lib().vp9hip_decoder_convert_resampled(self._d, arr, len(infos), OUT_FORMATS[fmt], ctypes.byref(rs),
+                                                                     flat.data_ptr(), 0, 0, st)
+        elif resize is None:
             call = lambda st: lib().vp9hip_decoder_convert(self._d, arr, len(infos), OUT_FORMATS[fmt], flat.data_ptr(), 0, 0, st)
         else:
             call = lambda st: lib().vp9hip_decoder_convert_scaled(self._d, arr, len(infos), OUT_FORMATS[fmt], ow, oh,

@@ -41,6 +41,43 @@ int64_t vp9hip_out_layout(const vp9hip_out_desc *d, int bpp, int ss_h, int ss_v,
     return bytes;
 }
 
+/* The filters' definition (include/vp9hip.h), one output index of one axis. Plain 64-bit
+ * arithmetic from the formulas, no shortcut: this is what a result can be reproduced from. */
+int vp9hip_resample_weights(int filter, int n_src, int n_out, int o, int *first, int32_t *weights, int cap,
+                            int64_t *sum)
+{
+    if (filter != VP9HIP_FILTER_BOX && filter != VP9HIP_FILTER_TRIANGLE) return VP9HIP_EINVAL;
+    if (n_src < 1 || n_src > 16384 || n_out < 1 || n_out > 16384 || o < 0 || o >= n_out || cap < 0) return VP9HIP_EINVAL;
+    const int64_t w = n_src, ow = n_out;
+    int64_t s0, s1;
+    if (filter == VP9HIP_FILTER_BOX) {
+        s0 = o * w / ow;                               /* [o w, (o+1) w) meets [s ow, (s+1) ow) */
+        s1 = ((o + 1) * w + ow - 1) / ow;
+    } else {
+        const int64_t m2 = 2 * (w > ow ? w : ow), c = (2 * (int64_t) o + 1) * w;
+        const int64_t lo = c - m2 + ow;                /* (2 s + 1) ow > c - 2M */
+        s0 = lo < 0 ? 0 : lo / (2 * ow);
+        s1 = (c + m2 + ow - 1) / (2 * ow);             /* (2 s + 1) ow < c + 2M */
+        if (s1 > w) s1 = w;
+    }
+    int64_t d = 0;
+    for (int64_t s = s0; s < s1; s++) {
+        int64_t t;
+        if (filter == VP9HIP_FILTER_BOX) {
+            const int64_t a = o * w > s * ow ? o * w : s * ow, b = (o + 1) * w < (s + 1) * ow ? (o + 1) * w : (s + 1) * ow;
+            t = b - a;
+        } else {
+            const int64_t m2 = 2 * (w > ow ? w : ow), e = (2 * (int64_t) o + 1) * w - (2 * s + 1) * ow;
+            t = m2 - (e < 0 ? -e : e);
+        }
+        if (weights && s - s0 < cap) weights[s - s0] = (int32_t) t;
+        d += t;
+    }
+    if (first) *first = (int) s0;
+    if (sum) *sum = d;
+    return (int) (s1 - s0);
+}
+
 int vp9hip_out_coefs(int colorspace, int full_range, int bpp, int out_bits, int32_t c[5], int32_t *shift)
 {
     if (!c || !shift || (bpp != 8 && bpp != 10 && bpp != 12) || (out_bits != 8 && out_bits != bpp)) return VP9HIP_EINVAL;

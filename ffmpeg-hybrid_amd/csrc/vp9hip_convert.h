@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/vp9hip.h"
+
 #define CVT_MAX_FRAMES 32              // frames per launch (blockIdx.z): their buffers are kernel arguments
 
 struct CvtArgs {
@@ -40,5 +42,23 @@ struct CvtScaleArgs {
 
 // One launch of k_convert_scale over n <= CVT_MAX_FRAMES frames.
 hipError_t vp9hip_convert_scale_launch(const CvtScaleArgs &a, int format, int hbd, int n, hipStream_t st);
+
+// The fused resampling with source rectangles and letterbox (vp9hip_convert_resample.hip).
+// c.pitch / c.plane / c.frame_stride describe the ow x oh output; c.w / c.h / c.cw / c.ch are
+// not read: each frame of the launch has rectangles of its own, in luma samples, validated by
+// the runtime (inside the visible picture / the output, aligned to the subsampling).
+struct CvtResampleArgs {
+    CvtArgs c;
+    int32_t ow, oh;                    // output luma (and RGB) size
+    int32_t cow, coh;                  // the chroma planes' output grid (RGB: ow, oh; semi-planar: OCW, OCH)
+    int32_t ss_h, ss_v;                // the source's chroma subsampling: a source rectangle's chroma rectangle
+    int32_t ds_h, ds_v;                // the output's: a destination rectangle's (semi-planar: ss_h, ss_v; RGB: 0, 0)
+    int32_t fill[3];                   // sample codes outside the destination rectangle, at the source's depth
+    vp9hip_rect src_rect[CVT_MAX_FRAMES];
+    vp9hip_rect dst_rect[CVT_MAX_FRAMES];
+};
+
+// One launch of k_convert_resample over n <= CVT_MAX_FRAMES frames; filter: VP9HIP_FILTER_*.
+hipError_t vp9hip_convert_resample_launch(const CvtResampleArgs &a, int format, int hbd, int filter, int n, hipStream_t st);
 
 #endif

@@ -371,11 +371,12 @@ extern "C" int vp9hip_decoder_release(vp9hip_decoder *d, int buf)
     return 0;
 }
 
-// Received frames to an output format (vp9hip_convert_frames, or vp9hip_convert_frames_scaled
-// when `scaled`). They are complete (their batch was checked by receive_frame), so nothing is
+// Received frames to an output format (vp9hip_convert_frames, vp9hip_convert_frames_scaled
+// when `scaled`, or vp9hip_convert_frames_resampled when `rs`). They are complete (their batch was checked by receive_frame), so nothing is
 // ordered here.
 static int decoder_convert(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n, int format, bool scaled,
-                           int out_width, int out_height, void *dst_dev, int64_t pitch, int64_t frame_stride, void *stream)
+                           int out_width, int out_height, void *dst_dev, int64_t pitch, int64_t frame_stride, void *stream,
+                           const vp9hip_resample *rs = nullptr)
 {
     if (!d || !frames || n <= 0 || !d->configured) return VP9HIP_EINVAL;
     std::vector<int> bufs(n);
@@ -394,6 +395,7 @@ static int decoder_convert(vp9hip_decoder *d, const vp9hip_decoded_frame *frames
     o.full_range = frames[0].full_range;
     o.width = frames[0].width; o.height = frames[0].height;
     o.pitch = pitch; o.frame_stride = frame_stride;
+    if (rs) return vp9hip_convert_frames_resampled(d->ctx, bufs.data(), n, &o, rs, dst_dev, stream);
     if (scaled) return vp9hip_convert_frames_scaled(d->ctx, bufs.data(), n, &o, out_width, out_height, dst_dev, stream);
     return vp9hip_convert_frames(d->ctx, bufs.data(), n, &o, dst_dev, stream);
 }
@@ -409,6 +411,14 @@ extern "C" int vp9hip_decoder_convert_scaled(vp9hip_decoder *d, const vp9hip_dec
                                              int64_t frame_stride, void *stream)
 {
     return decoder_convert(d, frames, n, format, true, out_width, out_height, dst_dev, pitch, frame_stride, stream);
+}
+
+extern "C" int vp9hip_decoder_convert_resampled(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n, int format,
+                                                const vp9hip_resample *rs, void *dst_dev, int64_t pitch,
+                                                int64_t frame_stride, void *stream)
+{
+    if (!rs) return VP9HIP_EINVAL;
+    return decoder_convert(d, frames, n, format, false, 0, 0, dst_dev, pitch, frame_stride, stream, rs);
 }
 
 // avcodec_flush_buffers (vp9.c:1865-1883): drop the decoder delay and the reference

@@ -2890,7 +2890,7 @@ extern "C" int vp9hip_frame_device(vp9hip_ctx *c, int buf, void *planes[3], ptrd
     return 0;
 }
 
-// Output conversion (vp9hip_convert.hip, vp9hip_convert_scale.hip): frames bufs[0 .. n-1] into
+// Output conversion (vp9hip_convert.hip, vp9hip_convert_scale.hip, vp9hip_convert_resample.hip): frames bufs[0 .. n-1] into
 // dst_dev, enqueued on `stream` (NULL: the current slot's main stream). Everything is
 // validated before the first launch, so a refused call writes nothing. The buffers' pointers
 // travel as kernel arguments, CVT_MAX_FRAMES per launch: no device table, no copy, nothing to
@@ -2980,6 +2980,92 @@ extern "C" int vp9hip_convert_frames_scaled(vp9hip_ctx *c, const int *bufs, int 
         for (int i = 0; i < k; i++) a.src[i] = c->bufs[bufs[i0 + i]];
         a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
         HIPCHK(vp9hip_convert_scale_launch(s, d->format, c->hb, k, st));
+    }
+    return 0;
+}
+
+// max over o of D(o) for one axis (vp9hip_resample_weights is the definition): the bound's two
+// factors. About 2 max(n_src, n_out) taps in all.
+static int64_t resample_max_d(int filter, int n_src, int n_out)
+{
+    if (filter == VP9HIP_FILTER_BOX) return n_src;
+    int64_t m = 0, d;
+    for (int o = 0; o < n_out; o++) {
+        vp9hip_resample_weights(filter, n_src, n_out, o, nullptr, nullptr, 0, &d);
+        m = std::max(m, d);
+    }
+    return m;
+}
+
+// D(o) <= this for every o, in O(1): a triangle weight is at most 2M, and the taps of one output
+// are the s with (2s+1) n_out inside an open interval of length 4M, at most 2M / n_out + 1 of
+// them. It settles the bound for every geometry but extreme reductions; only those need the
+// exact maxima (a 4K source to 1080p would otherwise spend ~6,000 host calls per launch on them).
+static int64_t resample_d_upper(int filter, int n_src, int n_out)
+{
+    if (filter == VP9HIP_FILTER_BOX) return n_src;
+    const int64_t m2 = 2 * (int64_t) std::max(n_src, n_out);
+    return m2 * (m2 / n_out + 1);
+}
+
+// The same with a filter, a source and a destination rectangle per frame and the fill
+// (k_convert_resample). Every frame's rectangles are checked before the first launch.
+extern "C" int vp9hip_convert_frames_resampled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d,
+                                               const vp9hip_resample *rs, void *dst_dev, void *stream)
+{
+    if (!rs || (rs->filter != VP9HIP_FILTER_BOX && rs->filter != VP9HIP_FILTER_TRIANGLE)) return VP9HIP_EINVAL;
+    const int OW = rs->out_width, OH = rs->out_height;
+    if (OW < 1 || OW > 16384 || OH < 1 || OH > 16384) return VP9HIP_EINVAL;
+    CvtResampleArgs s;
+    int64_t stride;
+    memset(&s, 0, sizeof(s));
+    const int r = convert_args(c, bufs, n, d, OW, OH, dst_dev, s.c, &stride);
+    if (r < 0) return r;
+    CvtArgs &a = s.c;
+    const bool semi = d->format == VP9HIP_OUT_SEMIPLANAR;      // chroma keeps the subsampling; RGB resamples it to the output size
+    s.ow = OW; s.oh = OH;
+    s.ss_h = c->ss_h; s.ss_v = c->ss_v;
+    s.ds_h = semi ? c->ss_h : 0; s.ds_v = semi ? c->ss_v : 0;
+    s.cow = (OW + s.ds_h) >> s.ds_h; s.coh = (OH + s.ds_v) >> s.ds_v;
+    if (rs->dst_rects)
+        for (int p = 0; p < 3; p++) {
+            if (rs->fill[p] < 0 || rs->fill[p] >= 1 << c->bpp) return VP9HIP_EINVAL;
+            s.fill[p] = rs->fill[p];
+        }
+    // the rectangles in effect, and the bound on every (source -> destination) geometry
+    const vp9hip_rect whole_src = { 0, 0, d->width, d->height }, whole_dst = { 0, 0, OW, OH };
+    std::vector<vp9hip_rect> src(n, whole_src), dst(n, whole_dst);
+    const unsigned __int128 lim = (unsigned __int128) 1 << 63;
+    const int64_t maxv = (1 << c->bpp) - 1;
+    for (int i = 0; i < n; i++) {
+        if (rs->src_rects) src[i] = rs->src_rects[i];
+        if (rs->dst_rects) dst[i] = rs->dst_rects[i];
+        const vp9hip_rect &sr = src[i], &dr = dst[i];
+        if (sr.w < 1 || sr.h < 1 || sr.x < 0 || sr.y < 0 || sr.x > d->width - sr.w || sr.y > d->height - sr.h) return VP9HIP_EINVAL;
+        if ((sr.x & ((1 << c->ss_h) - 1)) || (sr.y & ((1 << c->ss_v) - 1))) return VP9HIP_EINVAL;
+        if (dr.w < 1 || dr.h < 1 || dr.x < 0 || dr.y < 0 || dr.x > OW - dr.w || dr.y > OH - dr.h) return VP9HIP_EINVAL;
+        if ((dr.x & ((1 << s.ds_h) - 1)) || (dr.y & ((1 << s.ds_v) - 1))) return VP9HIP_EINVAL;
+        if (i && !memcmp(&sr, &src[i - 1], sizeof(sr)) && !memcmp(&dr, &dst[i - 1], sizeof(dr))) continue;   // checked already
+        const int geo[2][4] = { { sr.w, sr.h, dr.w, dr.h },
+                                { (sr.w + s.ss_h) >> s.ss_h, (sr.h + s.ss_v) >> s.ss_v, (dr.w + s.ds_h) >> s.ds_h, (dr.h + s.ds_v) >> s.ds_v } };
+        auto over = [&](int64_t dx, int64_t dy) {
+            return (unsigned __int128) dx * (unsigned __int128) dy * (unsigned __int128) maxv >= lim;
+        };
+        for (const auto &g : geo)
+            if (over(resample_d_upper(rs->filter, g[0], g[2]), resample_d_upper(rs->filter, g[1], g[3])) &&
+                over(resample_max_d(rs->filter, g[0], g[2]), resample_max_d(rs->filter, g[1], g[3]))) return VP9HIP_EINVAL;
+    }
+    hipSetDevice(c->dev);
+    hipStream_t st = stream ? (hipStream_t) stream : c->st;
+    for (int i0 = 0; i0 < n; i0 += CVT_MAX_FRAMES) {
+        const int k = std::min(n - i0, CVT_MAX_FRAMES);
+        for (int i = 0; i < k; i++) {
+            a.src[i] = c->bufs[bufs[i0 + i]];
+            s.src_rect[i] = src[i0 + i];
+            s.dst_rect[i] = dst[i0 + i];
+        }
+        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
+        HIPCHK(vp9hip_convert_resample_launch(s, d->format, c->hb, rs->filter, k, st));
     }
     return 0;
 }

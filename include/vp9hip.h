@@ -38,7 +38,10 @@ extern "C" {
  * vp9hip_decoder_convert) added. vp9hip_convert_frames_scaled / vp9hip_decoder_convert_scaled
  * came later as new symbols only: no struct changed, so the version stayed. */
 /* 4: vp9h_synth_params ends in eob_dense / ref_mix / mv_range. */
-/* 5: vp9h_synth_params ends in edge_large / p_intra. */
+/* 5: vp9h_synth_params ends in edge_large / p_intra. vp9hip_convert_frames_resampled /
+ * vp9hip_decoder_convert_resampled / vp9hip_resample_weights (with vp9hip_rect and
+ * vp9hip_resample) came later, again as new symbols and new structs only: no existing struct
+ * changed, so the version stayed. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -326,8 +329,9 @@ int  vp9hip_convert_frames(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip
  * There is no intermediate rounding and no normalised weight, so every evaluation order
  * gives the same integers. The same formula serves every ratio: with ow == w and oh == h it
  * is the identity, and upscaling is nearest-neighbour with blended seams (an output sample
- * inside one source sample copies it, one across a boundary blends the two by area); bilinear
- * or bicubic upscaling is not offered.
+ * inside one source sample copies it, one across a boundary blends the two by area); the
+ * interpolating (bilinear) filter is VP9HIP_FILTER_TRIANGLE of
+ * vp9hip_convert_frames_resampled below; bicubic is not offered.
  *
  * For a visible source of w x h luma and cw x ch chroma (cw = (w + ss_h) >> ss_h) and an
  * output of OW x OH:
@@ -340,7 +344,8 @@ int  vp9hip_convert_frames(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip
  *       then go through the conversion's arithmetic unchanged, as a 4:4:4 source would:
  *       matrix, clip, code-7 pass-through, the half multiply.
  * Only the visible d->width x d->height (the top-left crop) contributes: samples of the
- * 64-padding, or of a configured size larger than the visible one, never enter a sum.
+ * 64-padding, or of a configured size larger than the visible one, never enter a sum. Other
+ * regions of the picture are the source rectangles of vp9hip_convert_frames_resampled.
  *
  * d->width / d->height stay the visible source size; the output is laid out as
  * vp9hip_out_layout says for a desc of out_width x out_height with d's pitch / frame_stride.
@@ -349,6 +354,73 @@ int  vp9hip_convert_frames(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip
  */
 int  vp9hip_convert_frames_scaled(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip_out_desc *d,
                                   int out_width, int out_height, void *dst_dev, void *stream);
+/*
+ * Resampling with a choice of filter, a source rectangle and a destination rectangle per
+ * output frame (letterbox), fused into the conversion like the box resize: one launch per 32
+ * frames. Integer and exact, one right answer (DESIGN.md "Resampling: triangle filter, source
+ * regions, letterbox").
+ *
+ * tri(P, ow, oh), the triangle filter of a w x h plane P of integer samples:
+ *   M = max(w, ow);  tx(ox, sx) = max(0, 2M - |(2 ox + 1) w - (2 sx + 1) ow|),  0 <= sx < w
+ *       the triangle 1 - |d| / s of support s = max(1, w / ow) source samples over the
+ *       distance d between the output sample's centre and the source sample's, scaled by
+ *       2 ow s to an integer. ty(oy, sy) is the same with h and oh.
+ *   Dx(ox) = sum_sx tx(ox, sx) > 0 (the nearest source sample weighs >= M); Dy(oy) alike
+ *   A(ox, oy) = sum_sy ty sum_sx tx P[sy][sx]                        exact integers
+ *   tri = (A + (Dx Dy >> 1)) / (Dx Dy)                               floor: round half up
+ * One rounding, no normalised weight tables, any evaluation order gives the same integers.
+ * Taps outside the plane are absent from A and D alike: the edge clamps. ow == w is the
+ * identity; a constant plane stays constant; upscaling has two taps per axis that sum to
+ * 2 ow, ordinary bilinear interpolation with half-pixel centres (align_corners = False);
+ * downscaling widens the triangle, so it is antialiased: the correctly rounded value of
+ * torch's interpolate(mode="bilinear", antialias=True).
+ * Bound: a call is accepted only if max_ox Dx * max_oy Dy * (2^bpp - 1) < 2^63 for every
+ * (source geometry -> destination geometry) pair it uses, luma and chroma (7680 x 4320 at 12
+ * bits -> 1 x 1 is just over it, -> 2 x 2 and the 8-bit -> 1 x 1 are under it).
+ *
+ * Source rectangle (x, y, w, h) in luma samples: inside d->width x d->height, w, h >= 1, x a
+ * multiple of 1 << ss_h and y of 1 << ss_v (for every format). Its chroma rectangle is
+ * (x >> ss_h, y >> ss_v, (w + ss_h) >> ss_h, (h + ss_v) >> ss_v). The filter is applied to the
+ * sub-plane as if it were the whole plane: nothing outside it enters a sum, edges clamp at
+ * it. NULL src_rects: the visible picture.
+ *
+ * Destination rectangle (dx, dy, dw, dh) inside the out_width x out_height output, dw, dh >=
+ * 1, and fill codes fill[0..2] at the source's depth (Y, U, V; G, B, R for colour space 7),
+ * 0 <= fill[p] < 2^bpp:
+ *   RGB formats: the three planes are resampled to dw x dh and placed at (dx, dy); every
+ *       other pixel is the conversion's arithmetic applied to (fill[0], fill[1], fill[2]).
+ *   SEMIPLANAR: dx a multiple of 1 << ss_h, dy of 1 << ss_v; luma resampled to dw x dh, chroma
+ *       to ((dw + ss_h) >> ss_h) x ((dh + ss_v) >> ss_v) at (dx >> ss_h, dy >> ss_v); everything
+ *       else is the fill codes (<< (16 - bpp) above 8 bits).
+ * NULL dst_rects: the whole output, fill unused. Every visible output byte is written,
+ * picture or fill; pitch padding and frame gaps are not.
+ *
+ * VP9HIP_FILTER_BOX applies box of vp9hip_convert_frames_scaled to the same geometry; with
+ * no rectangles the two calls give the same bytes.
+ *
+ * Checked as vp9hip_convert_frames, plus the above, before the first launch (a refused call
+ * writes nothing): any violation, a NULL vp9hip_resample or an unknown filter is
+ * VP9HIP_EINVAL. Not offered: bicubic / Lanczos (negative lobes need a clip and fixed-point
+ * tables), siting-aware chroma, mean / std normalisation, rotation.
+ */
+enum { VP9HIP_FILTER_BOX, VP9HIP_FILTER_TRIANGLE };
+typedef struct vp9hip_rect { int32_t x, y, w, h; } vp9hip_rect;
+typedef struct vp9hip_resample {
+    int32_t filter;                 /* VP9HIP_FILTER_* */
+    int32_t out_width, out_height;  /* 1..16384 */
+    const vp9hip_rect *src_rects;   /* n entries, or NULL: the visible picture */
+    const vp9hip_rect *dst_rects;   /* n entries, or NULL: the whole output */
+    int32_t fill[3];
+} vp9hip_resample;
+int  vp9hip_convert_frames_resampled(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip_out_desc *d,
+                                     const vp9hip_resample *rs, void *dst_dev, void *stream);
+/* Host only: the C statement of the filters' definition. The taps of output index o of an
+ * axis of n_src source samples resampled to n_out (both 1..16384): returns their count,
+ * *first = the first source index, weights[0 .. min(count, cap) - 1] and *sum = D(o) (box:
+ * n_src); first / weights / sum may be NULL. VP9HIP_EINVAL: an unknown filter, a size or o
+ * out of range, cap < 0. */
+int  vp9hip_resample_weights(int filter, int n_src, int n_out, int o,
+                             int *first, int32_t *weights, int cap, int64_t *sum);
 
 /* Upload host planes into device buffer `buf` (test hook for reference frames). */
 int  vp9hip_upload_frame(vp9hip_ctx *ctx, int buf, const uint8_t *const planes[3],
@@ -708,6 +780,10 @@ int  vp9hip_decoder_convert(vp9hip_decoder *d, const vp9hip_decoded_frame *frame
 int  vp9hip_decoder_convert_scaled(vp9hip_decoder *dec, const vp9hip_decoded_frame *frames, int n, int format,
                                    int out_width, int out_height, void *dst_dev,
                                    int64_t pitch, int64_t frame_stride, void *stream);
+/* The same through vp9hip_convert_frames_resampled; the rectangles are per entry of frames. */
+int  vp9hip_decoder_convert_resampled(vp9hip_decoder *dec, const vp9hip_decoded_frame *frames, int n, int format,
+                                      const vp9hip_resample *rs, void *dst_dev, int64_t pitch,
+                                      int64_t frame_stride, void *stream);
 /* avcodec_flush_buffers: drop queued frames and reference state (seek). */
 int  vp9hip_decoder_flush(vp9hip_decoder *d);
 
