@@ -296,6 +296,19 @@ def lib():
     L.vp9hip_plan_sched_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4
     L.vp9hip_plan_heights_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2
     L.vp9hip_test_plan_records.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)] + [ctypes.c_void_p] * 4
+    # motion export
+    L.vp9hip_set_export.argtypes = [vp, ctypes.c_int]
+    L.vp9hip_frame_motion.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                      ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_void_p)]
+    L.vp9hip_download_motion.argtypes = [vp, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_motion_host.argtypes = [ctypes.POINTER(FramePacket), ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_motion_launch_dev.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_void_p]
+    L.vp9hip_decoder_set_export.argtypes = [vp, ctypes.c_int]
+    L.vp9hip_decoder_frame_motion.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(ctypes.c_void_p),
+                                              ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int),
+                                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)]
     _lib_handle = L
     return L
 
@@ -694,6 +707,40 @@ def _resample_arg(n, resize, filter, src_rects, dst_rects, fill, bpp, colorspace
     return rs
 
 
+EXPORT_MOTION = 1              # VP9HIP_EXPORT_MOTION
+
+
+def motion_host(frame):
+    """The motion field of one packet (SynthFrame, a parsed packet or a FramePacket) on the host,
+    vp9hip_motion_host, the C statement of the definition in include/vp9hip.h: (mv, info), int16
+    (GH, GW, 2, 2) and uint8 (GH, GW, 4) with GW x GH = 2 ((width + 7) >> 3) x 2 ((height + 7) >> 3)
+    cells of 4x4 luma pixels. Cells no block covers are zero."""
+    pkt = frame.pkt if hasattr(frame, "pkt") else frame
+    gw, gh = 2 * ((pkt.width + 7) >> 3), 2 * ((pkt.height + 7) >> 3)
+    if gw <= 0 or gh <= 0:
+        raise Vp9HipError("vp9hip_motion_host", EINVAL)
+    mv, info = np.zeros((gh, gw, 2, 2), np.int16), np.zeros((gh, gw, 4), np.uint8)
+    _check("vp9hip_motion_host", lib().vp9hip_motion_host(ctypes.byref(pkt), mv.ctypes.data, info.ctypes.data))
+    return mv, info
+
+
+def _motion_views(mv, info, gw, gh, pitch, device):
+    """Zero-copy torch views of a field's two device planes, strided over the fixed pitch."""
+    if not _torch_first:
+        raise Vp9HipUnavailable("motion: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+    import torch
+
+    class _Mv:
+        __cuda_array_interface__ = {"shape": (gh, gw, 2, 2), "typestr": "<i2", "data": (mv, False),
+                                    "strides": (pitch * 8, 8, 4, 2), "version": 2}
+
+    class _Info:
+        __cuda_array_interface__ = {"shape": (gh, gw, 4), "typestr": "|u1", "data": (info, False),
+                                    "strides": (pitch * 4, 4, 1), "version": 2}
+    return torch.as_tensor(_Mv(), device=device or "cuda"), torch.as_tensor(_Info(), device=device or "cuda")
+
+
 def alloc_planes(width, height, bpp, ss_h=1, ss_v=1, pad=64):
     """Host planes padded to 64 luma pixels (the layout the oracle expects)."""
     dt = np.uint8 if bpp == 8 else np.uint16
@@ -769,6 +816,36 @@ class Device:
     def configure(self, width, height, bpp=8, nbufs=4, ss_h=1, ss_v=1):
         _check("vp9hip_configure", lib().vp9hip_configure(self._c, width, height, bpp, ss_h, ss_v, nbufs))
         self.w, self.h, self.bpp, self.ss_h, self.ss_v = width, height, bpp, ss_h, ss_v
+
+    def set_export(self, motion=True):
+        """Motion export on / off for the next configure (vp9hip_set_export): every batch then
+        leaves each frame's motion field beside its pixels (motion / download_motion)."""
+        _check("vp9hip_set_export", lib().vp9hip_set_export(self._c, EXPORT_MOTION if motion else 0))
+
+    def frame_motion(self, buf):
+        """The field of buffer `buf` in place (vp9hip_frame_motion): (mv pointer, info pointer,
+        (GW, GH), pitch in cells, hipStream_t handle)."""
+        mv, info, st = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        gw, gh, pitch = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        _check("vp9hip_frame_motion", lib().vp9hip_frame_motion(self._c, buf, ctypes.byref(mv), ctypes.byref(info),
+                                                                ctypes.byref(gw), ctypes.byref(gh), ctypes.byref(pitch),
+                                                                ctypes.byref(st)))
+        return mv.value, info.value, (gw.value, gh.value), pitch.value, st.value
+
+    def motion(self, buf, device=None):
+        """Zero-copy torch views (mv, info) of buffer `buf`'s motion field: int16 (GH, GW, 2, 2)
+        and uint8 (GH, GW, 4), strided over the planes' fixed pitch. Call sync() first (or order
+        consumers after the slot that wrote the frame), as for frame_tensors."""
+        mv, info, (gw, gh), pitch, _ = self.frame_motion(buf)
+        return _motion_views(mv, info, gw, gh, pitch, device)
+
+    def download_motion(self, buf):
+        """Buffer `buf`'s motion field as numpy arrays (mv, info) of motion()'s shapes
+        (vp9hip_download_motion; waits for the batches writing the buffer)."""
+        _, _, (gw, gh), _, _ = self.frame_motion(buf)
+        mv, info = np.empty((gh, gw, 2, 2), np.int16), np.empty((gh, gw, 4), np.uint8)
+        _check("vp9hip_download_motion", lib().vp9hip_download_motion(self._c, buf, mv.ctypes.data, info.ctypes.data))
+        return mv, info
 
     def submit(self, frame, out_buf, refs=(0, 0, 0)):
         r = (ctypes.c_int * 3)(*refs)
@@ -1076,7 +1153,8 @@ class Decoder:
     is needed (EAGAIN) or after the drain (EOF, which also sets .eof).
     """
 
-    def __init__(self, device=0, max_batch=16, extra_bufs=4, max_width=0, max_height=0, parse_threads=None):
+    def __init__(self, device=0, max_batch=16, extra_bufs=4, max_width=0, max_height=0, parse_threads=None,
+                 export_motion=False):
         self.params = DecoderParams()
         lib().vp9hip_decoder_defaults(ctypes.byref(self.params))
         self.params.device, self.params.max_batch, self.params.extra_bufs = device, max_batch, extra_bufs
@@ -1086,6 +1164,8 @@ class Decoder:
         self._d = ctypes.c_void_p()
         _check("vp9hip_decoder_open", lib().vp9hip_decoder_open(ctypes.byref(self.params), ctypes.byref(self._d)))
         self.eof = False
+        if export_motion:
+            _check("vp9hip_decoder_set_export", lib().vp9hip_decoder_set_export(self._d, EXPORT_MOTION))
 
     def close(self):
         if self._d:
@@ -1132,6 +1212,22 @@ class Decoder:
 
     def context(self):
         return ctypes.c_void_p(lib().vp9hip_decoder_context(self._d))
+
+    def motion(self, info, download=False, device=None):
+        """The motion field of a frame of receive_frame(download=False), valid until
+        release(info.buf) (vp9hip_decoder_frame_motion; needs export_motion=True): zero-copy
+        torch views (mv, info) as Device.motion returns them, or numpy copies with
+        download=True. A show_existing_frame output has the field of the frame it shows."""
+        mv, inf = ctypes.c_void_p(), ctypes.c_void_p()
+        gw, gh, pitch = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        _check("vp9hip_decoder_frame_motion",
+               lib().vp9hip_decoder_frame_motion(self._d, ctypes.byref(info), ctypes.byref(mv), ctypes.byref(inf),
+                                                 ctypes.byref(gw), ctypes.byref(gh), ctypes.byref(pitch)))
+        if not download:
+            return _motion_views(mv.value, inf.value, gw.value, gh.value, pitch.value, device)
+        m, i = np.empty((gh.value, gw.value, 2, 2), np.int16), np.empty((gh.value, gw.value, 4), np.uint8)
+        _check("vp9hip_download_motion", lib().vp9hip_download_motion(self.context(), info.buf, m.ctypes.data, i.ctypes.data))
+        return m, i
 
     def convert(self, infos, fmt, out=None, resize=None, filter="box", src_rects=None, dst_rects=None, fill=None):
         """Convert the frames of receive_frame(download=False) (their DecodedFrameInfos, all of

@@ -63,6 +63,8 @@ struct vp9hip_decoder {
     vp9hip_ctx *ctx = nullptr;
     bool configured = false, draining = false;
     bool stalled = false;                  // send_packet answered EAGAIN: receive must block
+    bool started = false;                  // a packet was sent: the export flags are fixed
+    int export_flags = 0;                  // vp9hip_decoder_set_export
     int cw = 0, ch = 0, cbpp = 0, css_h = 0, css_v = 0, nbufs = 0;
     int slot[8];
     std::vector<int> pins, busy, bw, bh;   // per device buffer
@@ -143,7 +145,9 @@ static int configure(vp9hip_decoder *d, const vp9h_frame &f)
     // 8 reference slots, the batch being filled, the launched batches' frames still to be
     // received (VP9HIP_PIPELINE_SLOTS in flight), and the frames the caller holds
     const int nb = 8 + (VP9HIP_PIPELINE_SLOTS + 1) * d->p.max_batch + (d->p.extra_bufs > 0 ? d->p.extra_bufs : 4);
-    int r = vp9hip_configure(d->ctx, w, h, f.bpp, f.ss_h, f.ss_v, nb);
+    int r = vp9hip_set_export(d->ctx, d->export_flags);   // the same flags again on a reconfigure
+    if (r < 0) return r;
+    r = vp9hip_configure(d->ctx, w, h, f.bpp, f.ss_h, f.ss_v, nb);
     if (r < 0) return r;
     d->configured = true;
     d->cw = w; d->ch = h; d->cbpp = f.bpp; d->css_h = f.ss_h; d->css_v = f.ss_v;
@@ -285,6 +289,7 @@ extern "C" int vp9hip_decoder_send_packet(vp9hip_decoder *d, const uint8_t *data
         return r < 0 ? r : 0;
     }
     if (d->draining) return VP9HIP_EOF;
+    d->started = true;
     size_t offs[8], sizes[8];
     const int nf = vp9h_superframe_split(data, size, offs, sizes, 8);
     if (nf < 0) return nf;
@@ -419,6 +424,26 @@ extern "C" int vp9hip_decoder_convert_resampled(vp9hip_decoder *d, const vp9hip_
 {
     if (!rs) return VP9HIP_EINVAL;
     return decoder_convert(d, frames, n, format, false, 0, 0, dst_dev, pitch, frame_stride, stream, rs);
+}
+
+// Motion export: the flags go to the context before it is configured (the first keyframe).
+extern "C" int vp9hip_decoder_set_export(vp9hip_decoder *d, int flags)
+{
+    if (!d || d->started) return VP9HIP_EINVAL;
+    const int r = vp9hip_set_export(d->ctx, flags);
+    if (!r) d->export_flags = flags;
+    return r;
+}
+
+// The field of a received frame: it is complete (receive_frame checked its batch) and stays
+// until the buffer is released, so this only looks up. A show_existing_frame output holds the
+// buffer of the frame it shows, and with it that frame's field.
+extern "C" int vp9hip_decoder_frame_motion(vp9hip_decoder *d, const vp9hip_decoded_frame *f, void **mv, void **info,
+                                           int *gw, int *gh, int64_t *pitch_cells)
+{
+    if (!d || !f || !d->configured || !(d->export_flags & VP9HIP_EXPORT_MOTION)) return VP9HIP_EINVAL;
+    if (f->buf < 0 || f->buf >= d->nbufs || d->pins[f->buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+    return vp9hip_frame_motion(d->ctx, f->buf, mv, info, gw, gh, pitch_cells, nullptr);
 }
 
 // avcodec_flush_buffers (vp9.c:1865-1883): drop the decoder delay and the reference

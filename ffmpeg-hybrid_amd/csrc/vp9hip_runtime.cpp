@@ -41,6 +41,7 @@
 #include "vp9hip_planlogic.h"
 #include "vp9hip_plan.h"
 #include "vp9hip_convert.h"
+#include "vp9hip_motion.h"
 #include "vp9hip_residn.h"
 
 extern "C" {
@@ -210,6 +211,12 @@ struct Staged {
     std::vector<int> wr, rd;            // frame buffers the batch writes / reads (sorted)
     uint32_t dep_mask = 0;              // bit k: it touches a buffer of slot k's batch
     double alg_stat[K_N] = {};          // algorithmic bytes after the launch-list moves
+    // motion export (vp9hip_set_export): every run launches k_motion over the batch's frames,
+    // from the MotionFrame records uploaded with the batch (o_mot)
+    bool motion = false;
+    size_t o_mot = 0;
+    std::vector<int> mot_buf;                        // per frame: its output buffer
+    std::vector<std::pair<int, int>> mot_grid;       // per frame: GW, GH
 };
 
 } // namespace
@@ -307,6 +314,14 @@ struct vp9hip_ctx {
     size_t plane_off[3] = { 0, 0, 0 }, buf_bytes = 0;
     std::vector<uint8_t *> bufs;
     std::vector<std::pair<int, int>> buf_wh;   // visible size of the frame each buffer holds
+    // motion export: the flags of the next configure (vp9hip_set_export); per frame buffer one
+    // allocation holding its mv plane (8 bytes per cell), then its info plane (4 bytes per cell),
+    // mot_pitch cells by mot_rows rows; mot_gwh: the grid of the field a buffer holds, { 0, 0 }
+    // when it holds none
+    int export_flags = 0;
+    std::vector<uint8_t *> mot;
+    std::vector<std::pair<int, int>> mot_gwh;
+    int mot_pitch = 0, mot_rows = 0;
     uint32_t *ptab = nullptr;           // intra predictor formula table (device)
     uint8_t *nz = nullptr;              // nonzero bounding boxes per (tcode, txtp, eob) (device, planner)
     bool host_plan = false;             // VP9HIP_HOST_PLAN=1: plan batches on host threads (A/B, tests)
@@ -492,6 +507,9 @@ static void free_bufs(vp9hip_ctx *c)
     for (auto *b : c->bufs) hipFree(b);
     c->bufs.clear();
     c->buf_wh.clear();
+    for (auto *b : c->mot) hipFree(b);
+    c->mot.clear();
+    c->mot_gwh.clear();
 }
 
 // Forget the staged batches of every slot (their FrameDescs, graphs and launch lists name
@@ -660,6 +678,15 @@ extern "C" int vp9hip_configure(vp9hip_ctx *c, int width, int height, int bpp, i
         hipMemsetAsync(b, 0, c->buf_bytes, c->st);
         c->bufs.push_back(b);
         c->buf_wh.push_back({ width, height });
+    }
+    if (c->export_flags & VP9HIP_EXPORT_MOTION) {
+        c->mot_pitch = 2 * c->cols; c->mot_rows = 2 * c->rows;
+        for (int i = 0; i < nbufs; i++) {
+            uint8_t *b = nullptr;
+            if (hipMalloc(&b, (size_t) c->mot_pitch * c->mot_rows * 12) != hipSuccess) { free_bufs(c); return VP9HIP_ENOMEM; }
+            c->mot.push_back(b);
+            c->mot_gwh.push_back({ 0, 0 });
+        }
     }
     int r = upload_ptab(c);
     if (!r) r = upload_nz(c);
@@ -1093,6 +1120,8 @@ struct DevIn {
     const std::vector<FrameBuild> *fbs;
     const std::vector<char> *res_fused, *lvl_ph;
     bool fuse, lfr_any;
+    const int *out_bufs;
+    bool motion;                 // the batch exports its frames' motion fields
 };
 
 // row-LF counter blocks of a staged batch, zeroed; word 3 of each block is the spin bound of
@@ -1425,6 +1454,8 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
     s.o_lists = o; o = al(o + (hl.size() + NS) * 4);      // host lists, then the device step lists
     s.o_expko = o; o = al(o + (s.stat ? s.exp_ko.size() : 0) * 4);   // static lists' offsets (k_psort)
     s.o_ctr = o; o = al(o + (size_t) s.n_ctr * 4);
+    s.motion = in.motion;
+    s.o_mot = o; o = al(o + (s.motion ? (size_t) n * sizeof(MotionFrame) : 0));
     s.o_blocks = o; o = al(o + nb * sizeof(vp9h_block));
     s.o_eobs = o; o = al(o + ne * 2);
     s.o_coefs = o; o = al(o + nc * in.csz + VP9HIP_COEF_PAD);
@@ -1508,6 +1539,22 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
         memcpy(img + s.o_expko, s.exp_ko.data(), s.exp_ko.size() * 4);
     }
     init_lfr_ctr(c, s, (uint32_t *) (img + s.o_ctr));
+    if (s.motion) {
+        MotionFrame *mf = (MotionFrame *) (img + s.o_mot);
+        for (int i = 0; i < n; i++) {
+            uint8_t *mp = c->mot[in.out_bufs[i]];
+            // a buffer the batch writes more than once keeps the field of its last writer: the
+            // launch runs all frames' workgroups at once, so an earlier writer exports nothing
+            bool last = true;
+            for (int j = i + 1; j < n && last; j++) last = in.out_bufs[j] != in.out_bufs[i];
+            mf[i].blk0 = pf[i].blk0; mf[i].nblk = last ? pf[i].nblk : 0;
+            mf[i].cols8 = (uint32_t) fbs[i].cols; mf[i].rows8 = (uint32_t) fbs[i].rows;
+            mf[i].mv = (uint64_t) mp;
+            mf[i].info = (uint64_t) (mp + (size_t) c->mot_pitch * c->mot_rows * 8);
+            mf[i].pitch = (uint32_t) c->mot_pitch;
+            mf[i].pad = 0;
+        }
+    }
     {   // packets: blocks, eobs, coefficients (frames copied in parallel)
         std::atomic<int> next(0);
         auto worker = [&]() {
@@ -2085,13 +2132,24 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
         }
     }
     s.dev = false;
+    s.motion = false;
     if (!c->host_plan) {
         DevIn in;
         in.pkts = pkts; in.n = n; in.G = G; in.maxpos = maxpos; in.NP = NP; in.csz = csz;
         in.fbs = &fbs; in.res_fused = &res_fused; in.lvl_ph = &lvl_ph;
         in.fuse = fuse; in.lfr_any = lfr_any;
+        in.out_bufs = out_bufs;
+        in.motion = (c->export_flags & VP9HIP_EXPORT_MOTION) && !tiled;
+        // the buffers' fields: the frames' grids once the batch ran; none for a sharded batch
+        for (int i = 0; i < n && !c->mot_gwh.empty(); i++) c->mot_gwh[out_bufs[i]] = { 0, 0 };
         const int r = stage_dev(c, in);
         if (r) return r;
+        s.mot_buf.clear(); s.mot_grid.clear();
+        for (int i = 0; i < n && in.motion; i++) {      // in frame order: a buffer's last writer wins
+            s.mot_buf.push_back(out_bufs[i]);
+            s.mot_grid.push_back({ 2 * fbs[i].cols, 2 * fbs[i].rows });
+            c->mot_gwh[out_bufs[i]] = s.mot_grid.back();
+        }
         STAGE_T(1);
         if (stage_trace) fprintf(stderr, "vp9hip stage (device plan): %d frames: setup %.1f upload %.1f ms\n", n, st_ms[0], st_ms[1]);
         return 0;
@@ -2461,7 +2519,10 @@ extern "C" int vp9hip_run_batch(vp9hip_ctx *c)
     Staged &s = c->stg;
     if (s.dev && !(c->plan_reuse && s.stat && s.planned)) {   // plan on the device from the resident packets
         const int r = plan_dev(c);
-        if (r) return r;
+        if (r) {                          // nothing was launched: no field of this batch is valid
+            for (size_t i = 0; s.motion && i < s.mot_buf.size(); i++) c->mot_gwh[s.mot_buf[i]] = { 0, 0 };
+            return r;
+        }
         if (c->plan_only) return 0;       // diagnostics: the planner alone
     }
     if (s.dev && s.stat && plan_stream(c) != c->st) {
@@ -2470,6 +2531,14 @@ extern "C" int vp9hip_run_batch(vp9hip_ctx *c)
     // a batch touching another slot's buffers follows that slot's last run
     for (int k = 0; c->slot_streams && k < MAX_SLOTS; k++)
         if (((s.dep_mask >> k) & 1) && c->sl[k].done_ev) HIPCHK(hipStreamWaitEvent(c->st, c->sl[k].done_ev, 0));
+    // motion export: one launch over the batch's blocks, ahead of the pixel work and outside its
+    // graph (its arguments are this staging's: the arena may move when the slot is restaged)
+    if (s.dev && s.motion) {
+        HIPCHK(vp9hip_motion_launch((const MotionFrame *) (s.arena + s.o_mot), s.nframes, s.max_blk,
+                                    (const vp9h_block *) (s.arena + s.o_blocks), 0, c->st));
+        // (again) the fields of this run: a refused earlier run or a fill in between cleared them
+        for (size_t i = 0; i < s.mot_buf.size(); i++) c->mot_gwh[s.mot_buf[i]] = s.mot_grid[i];
+    }
     // this slot's last work on the main stream: its next planning waits for it
     if (!s.done_ev) HIPCHK(hipEventCreateWithFlags(&s.done_ev, hipEventDisableTiming));
     if (c->timing || !c->use_graph) {
@@ -2860,6 +2929,7 @@ extern "C" int vp9hip_upload_frame(vp9hip_ctx *c, int buf, const uint8_t *const 
     if (!c || buf < 0 || buf >= (int) c->bufs.size() || !planes) return VP9HIP_EINVAL;
     hipSetDevice(c->dev);
     HIPCHK(sync_all(c));
+    if (!c->mot_gwh.empty()) c->mot_gwh[buf] = { 0, 0 };   // pixels from elsewhere: no field
     for (int p = 0; p < 3; p++) {
         const int bw = c->buf_wh[buf].first, bh = c->buf_wh[buf].second;
         int pw = p ? (bw + c->ss_h) >> c->ss_h : bw, ph = p ? (bh + c->ss_v) >> c->ss_v : bh;
@@ -2888,6 +2958,56 @@ extern "C" int vp9hip_frame_device(vp9hip_ctx *c, int buf, void *planes[3], ptrd
     if (height) *height = c->buf_wh[buf].second;
     if (stream) *stream = (void *) c->st;
     return 0;
+}
+
+// ---- motion export (include/vp9hip.h "motion export"; k_motion in vp9hip_motion.hip) ----
+extern "C" int vp9hip_set_export(vp9hip_ctx *c, int flags)
+{
+    if (!c || (flags & ~VP9HIP_EXPORT_MOTION)) return VP9HIP_EINVAL;
+    if (flags && c->host_plan) return VP9HIP_ENOSYS;      // host-planned batches do not upload the blocks
+    if (!c->bufs.empty() && flags != c->export_flags) return VP9HIP_EINVAL;
+    c->export_flags = flags;
+    return 0;
+}
+
+extern "C" int vp9hip_frame_motion(vp9hip_ctx *c, int buf, void **mv_dev, void **info_dev, int *gw, int *gh,
+                                   int64_t *pitch_cells, void **stream)
+{
+    if (!c || c->mot.empty() || buf < 0 || buf >= (int) c->mot.size()) return VP9HIP_EINVAL;
+    if (!c->mot_gwh[buf].first) return VP9HIP_EAGAIN;
+    if (mv_dev) *mv_dev = c->mot[buf];
+    if (info_dev) *info_dev = c->mot[buf] + (size_t) c->mot_pitch * c->mot_rows * 8;
+    if (gw) *gw = c->mot_gwh[buf].first;
+    if (gh) *gh = c->mot_gwh[buf].second;
+    if (pitch_cells) *pitch_cells = c->mot_pitch;
+    if (stream) *stream = (void *) c->st;
+    return 0;
+}
+
+extern "C" int vp9hip_download_motion(vp9hip_ctx *c, int buf, int16_t *mv, uint8_t *info)
+{
+    void *mvd = nullptr, *infod = nullptr;
+    int gw = 0, gh = 0;
+    int64_t pitch = 0;
+    if (const int r = vp9hip_frame_motion(c, buf, &mvd, &infod, &gw, &gh, &pitch, nullptr)) return r;
+    hipSetDevice(c->dev);
+    if (const int r = wait_writers(c, buf)) return r;
+    if (!c->dst_dl) HIPCHK(hipStreamCreateWithFlags(&c->dst_dl, hipStreamNonBlocking));
+    if (mv) HIPCHK(hipMemcpy2DAsync(mv, (size_t) gw * 8, mvd, (size_t) pitch * 8, (size_t) gw * 8, gh, hipMemcpyDeviceToHost, c->dst_dl));
+    if (info) HIPCHK(hipMemcpy2DAsync(info, (size_t) gw * 4, infod, (size_t) pitch * 4, (size_t) gw * 4, gh, hipMemcpyDeviceToHost, c->dst_dl));
+    HIPCHK(hipStreamSynchronize(c->dst_dl));
+    return 0;
+}
+
+// Diagnostics (tools/motion_bench.py): one k_motion launch over caller-built MotionFrame records
+// and blocks in device memory, on `stream`; shape 1 is the one-thread-per-block alternative.
+extern "C" int vp9hip_motion_launch_dev(const void *frames_dev, int nframes, int max_blk, const void *blocks_dev,
+                                        int shape, void *stream)
+{
+    if (!frames_dev || !blocks_dev || nframes <= 0 || nframes > 65535 || max_blk <= 0 || ((uintptr_t) blocks_dev & 3))
+        return VP9HIP_EINVAL;
+    return vp9hip_motion_launch((const MotionFrame *) frames_dev, nframes, max_blk, (const vp9h_block *) blocks_dev,
+                                shape, (hipStream_t) stream) == hipSuccess ? 0 : VP9HIP_EEXTERNAL;
 }
 
 // Output conversion (vp9hip_convert.hip, vp9hip_convert_scale.hip, vp9hip_convert_resample.hip): frames bufs[0 .. n-1] into
@@ -3085,6 +3205,7 @@ extern "C" int vp9hip_fill_buffers(vp9hip_ctx *c, int buf0, int count, int value
     hipSetDevice(c->dev);
     HIPCHK(sync_all(c));                 // neither slot's work may still read the buffers
     for (int i = buf0; i < buf0 + count; i++) HIPCHK(hipMemsetAsync(c->bufs[i], value & 255, c->buf_bytes, c->st));
+    for (int i = buf0; i < buf0 + count && !c->mot_gwh.empty(); i++) c->mot_gwh[i] = { 0, 0 };
     // every slot's later work (whichever stream it runs on) follows the fill
     if (!c->fill_ev) HIPCHK(hipEventCreateWithFlags(&c->fill_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(c->fill_ev, c->st));

@@ -41,7 +41,9 @@ extern "C" {
 /* 5: vp9h_synth_params ends in edge_large / p_intra. vp9hip_convert_frames_resampled /
  * vp9hip_decoder_convert_resampled / vp9hip_resample_weights (with vp9hip_rect and
  * vp9hip_resample) came later, again as new symbols and new structs only: no existing struct
- * changed, so the version stayed. */
+ * changed, so the version stayed. The motion export (vp9hip_set_export, vp9hip_frame_motion,
+ * vp9hip_download_motion, vp9hip_motion_host, vp9hip_decoder_set_export,
+ * vp9hip_decoder_frame_motion) likewise: new symbols only. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -422,6 +424,73 @@ int  vp9hip_convert_frames_resampled(vp9hip_ctx *ctx, const int *bufs, int n, co
 int  vp9hip_resample_weights(int filter, int n_src, int n_out, int o,
                              int *first, int32_t *weights, int cap, int64_t *sum);
 
+/* ---- motion export: the stream's own motion field and block modes as device tensors ----
+ * The second product of the decode besides the pixels (FFmpeg's AV_FRAME_DATA_MOTION_VECTORS /
+ * +export_mvs, which its VP9 decoder never filled): per 4x4 luma block the references, the
+ * prediction mode, the block size / skip / segment and the coded motion vectors, written from
+ * the batch's resident block array by one kernel (k_motion) per batch. Off by default; with it
+ * off nothing is allocated and nothing is launched.
+ *
+ * Definition, in integers. For a frame of visible size width x height let cols8 = (width + 7)
+ * >> 3 and rows8 = (height + 7) >> 3. The motion field is a grid of GW x GH = 2 cols8 x
+ * 2 rows8 cells, each one 4x4 luma block. The frame's blocks in decode order partition the 8x8
+ * grid (the planner rejects packets where they do not). A block at (row, col) in 8x8 units of
+ * size bs covers the cells [2 row, 2 row + h4) x [2 col, 2 col + w4) clipped to the grid, w4 /
+ * h4 its width / height in 4-pixel units; a block below 8x8 covers its whole 8x8 unit, 2 x 2
+ * cells. A block with row >= rows8, col >= cols8 or bs >= VP9H_N_BS covers nothing. For cell
+ * (r, c) inside block b, with i = (r & 1) * 2 + (c & 1):
+ *   info[r][c][0] = b.intra ? 255 : b.ref[0]
+ *   info[r][c][1] = (!b.intra && b.comp) ? b.ref[1] : 255
+ *   info[r][c][2] = b.mode[i]
+ *   info[r][c][3] = (uint8_t) (b.bs | b.skip << 4 | b.seg_id << 5)
+ *   mv[r][c][k][0..1] = b.mv[i][k][0..1], (x, y) in 1/8 luma pel, for each reference k whose
+ *       info byte is not 255, else 0: an intra block has all four values 0, a single-reference
+ *       block has mv[r][c][1] = 0 whatever the packet holds there.
+ * This relies on the packet filling all four mode[] / mv[] entries of every block as the
+ * reference does (ff_vp9_fill_mv: four equal copies at >= 8x8, row pairs at 8x4, column pairs
+ * at 4x8), as the planner's chroma vectors already do. A keyframe or intra-only frame gives
+ * bytes 0 and 1 equal to 255 and zero vectors everywhere. Reference names are LAST / GOLDEN /
+ * ALTREF as in the packet: mapping names to buffers stays the caller's business, through the
+ * refs it staged with. Vectors are the coded ones, in the current frame's coordinates, also
+ * under reference scaling. Not exported: transform sizes, the interpolation filter, chroma
+ * vectors. */
+#define VP9HIP_EXPORT_MOTION 1
+/* Export flags (0 or VP9HIP_EXPORT_MOTION) of the next vp9hip_configure, which then allocates
+ * two side planes per frame buffer, freed with the buffers: mv (8 bytes per cell) and info (4
+ * bytes per cell), of the fixed cell pitch 2 ((cfg_width + 7) >> 3) and 2 ((cfg_height + 7) >> 3)
+ * rows; a smaller frame in a larger context uses the top-left of its planes. VP9HIP_EINVAL:
+ * unknown flags, or a change of the flags of a configured context. VP9HIP_ENOSYS: export with
+ * VP9HIP_HOST_PLAN=1 (the host-planned path does not upload the blocks).
+ * With export on, vp9hip_stage_batch / _refs (and vp9hip_submit_frame, which goes through them)
+ * mark the batch's output buffers, and every vp9hip_run_batch writes their fields with one
+ * k_motion launch ahead of the pixel work, so vp9hip_sync_slot / vp9hip_slot_stream_wait /
+ * vp9hip_sync cover it. Every cell of the GW x GH grid is written, nothing else. A buffer that
+ * several frames of one batch write keeps the field of the last of them (cells outside that
+ * frame's grid are unspecified). The field of a frame the planner rejects is unspecified; a
+ * vp9hip_run_batch that fails before its launches (AVERROR_INVALIDDATA from a batch planned on
+ * the host's schedule) leaves none of the batch's buffers with a field until a later run. vp9hip_stage_batch_tiles does not export; it,
+ * vp9hip_upload_frame and vp9hip_fill_buffers leave the buffers they write without a field. */
+int  vp9hip_set_export(vp9hip_ctx *ctx, int flags);
+/* The field of device buffer `buf`, in place, in the style of vp9hip_frame_device: device
+ * pointers of the mv plane (int16, [gh][pitch_cells][2][2]) and the info plane (uint8,
+ * [gh][pitch_cells][4]), the grid of the frame last exported into the buffer, the pitch in
+ * cells, and the current slot's main hipStream_t; any output pointer may be NULL. Ordering is
+ * the caller's, as for the pixels. VP9HIP_EINVAL without export or for a bad buf;
+ * VP9HIP_EAGAIN if the buffer holds no exported field. */
+int  vp9hip_frame_motion(vp9hip_ctx *ctx, int buf, void **mv_dev, void **info_dev, int *gw, int *gh,
+                         int64_t *pitch_cells, void **stream);
+/* Copy the field of `buf` into tight host arrays mv[gh][gw][2][2] and info[gh][gw][4] (either may
+ * be NULL). Waits for the batches writing the buffer, like vp9hip_download_frame. Errors as
+ * vp9hip_frame_motion. */
+int  vp9hip_download_motion(vp9hip_ctx *ctx, int buf, int16_t *mv, uint8_t *info);
+/* Host only, no device: the C statement of the definition above over pkt's blocks in decode
+ * order, into tight mv[GH][GW][2][2] / info[GH][GW][4], with the clipping rules of the kernel
+ * (blocks outside the grid or of an unknown size cover nothing; nothing outside the arrays is
+ * written; cells no block covers keep their bytes). Returns the number of cells written
+ * (a cell two blocks cover counts twice), or VP9HIP_EINVAL for a NULL argument or a packet
+ * without a size. */
+int  vp9hip_motion_host(const vp9h_frame *pkt, int16_t *mv, uint8_t *info);
+
 /* Upload host planes into device buffer `buf` (test hook for reference frames). */
 int  vp9hip_upload_frame(vp9hip_ctx *ctx, int buf, const uint8_t *const planes[3],
                          const ptrdiff_t linesize[3]);
@@ -784,6 +853,18 @@ int  vp9hip_decoder_convert_scaled(vp9hip_decoder *dec, const vp9hip_decoded_fra
 int  vp9hip_decoder_convert_resampled(vp9hip_decoder *dec, const vp9hip_decoded_frame *frames, int n, int format,
                                       const vp9hip_resample *rs, void *dst_dev, int64_t pitch,
                                       int64_t frame_stride, void *stream);
+/* Motion export (see vp9hip_set_export): flags = VP9HIP_EXPORT_MOTION makes every decoded frame,
+ * hidden ones included, leave its motion field beside its pixels. Call before the first
+ * vp9hip_decoder_send_packet; VP9HIP_EINVAL afterwards. The flags reach the context before it is
+ * configured, and again when a new format reconfigures it. */
+int  vp9hip_decoder_set_export(vp9hip_decoder *d, int flags);
+/* The field of a received frame, in place (device pointers, grid, pitch in cells, as
+ * vp9hip_frame_motion): valid while the frame is un-released. Received frames are complete, so
+ * this only looks up. A show_existing_frame output returns the field of the frame it shows; a
+ * hidden frame's field exists but is handed out only that way. VP9HIP_EINVAL without export or
+ * for a frame the caller does not hold. */
+int  vp9hip_decoder_frame_motion(vp9hip_decoder *d, const vp9hip_decoded_frame *frame, void **mv, void **info,
+                                 int *gw, int *gh, int64_t *pitch_cells);
 /* avcodec_flush_buffers: drop queued frames and reference state (seek). */
 int  vp9hip_decoder_flush(vp9hip_decoder *d);
 

@@ -28,5 +28,8 @@ for v in asan tsan; do
     { echo "== hwaccel_cpu_$v san_g.ivf passes $1 lag $2 mode $3 depth $4 ${5:+extra $5}"; ./$B/hwaccel_cpu_$v /tmp/san_g.ivf - 8 1 1 $args; echo "exit $?"; } >> $O/hwaccel_cpu_$v.log 2>&1
   done
 done
+for v in plain asan; do
+  { echo "== motion_host_check_$v"; ./$B/motion_host_check_$v; echo "exit $?"; } > $O/motion_host_check_$v.log 2>&1
+done
 grep -l "ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|runtime error" $O/*.log && { echo "sanitizer findings"; exit 1; }
 grep -h "^exit" $O/*.log | sort | uniq -c
