@@ -155,7 +155,8 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9hip_decoder_flush",
                "vp9h_stream_set_color", "vp9hip_out_layout", "vp9hip_out_coefs", "vp9hip_convert_frames",
                "vp9hip_decoder_convert", "vp9hip_convert_frames_scaled", "vp9hip_decoder_convert_scaled",
-               "vp9hip_convert_frames_resampled", "vp9hip_decoder_convert_resampled", "vp9hip_resample_weights"]
+               "vp9hip_convert_frames_resampled", "vp9hip_decoder_convert_resampled", "vp9hip_resample_weights",
+               "vp9hip_convert_frames_bicubic", "vp9hip_decoder_convert_bicubic", "vp9hip_bicubic_weights"]
 
 
 def lib():
@@ -289,6 +290,11 @@ def lib():
                                                    ctypes.c_int64, ctypes.c_void_p]
     L.vp9hip_resample_weights.argtypes = [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int32),
                                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
+    L.vp9hip_convert_frames_bicubic.argtypes = L.vp9hip_convert_frames_resampled.argtypes
+    L.vp9hip_decoder_convert_bicubic.argtypes = L.vp9hip_decoder_convert_resampled.argtypes
+    L.vp9hip_bicubic_weights.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int32),
+                                                               ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
+                                                               ctypes.POINTER(ctypes.c_int64)]
     L.vp9hip_resid4_host.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
     L.vp9hip_residn_host.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
     L.vp9hip_intra_job_host.argtypes = [ctypes.c_int] * 15 + [ctypes.POINTER(ctypes.c_int32)]
@@ -365,6 +371,8 @@ class Resample(ctypes.Structure):
 OUT_FORMATS = {"semiplanar": 0, "rgb24": 1, "rgbp_u8": 2, "rgbp_f16": 3}
 # VP9HIP_FILTER_*: the names of their filter argument
 FILTERS = {"box": 0, "triangle": 1}
+# VP9HIP_FILTER_BICUBIC, filter="bicubic": entries of its own (vp9hip_convert_frames_bicubic)
+FILTER_BICUBIC = 2
 
 
 def _check(fn, r):
@@ -655,6 +663,17 @@ def resample_weights(filter, n_src, n_out, o):
     return first.value, list(w), d.value
 
 
+def bicubic_weights(n_src, n_out, o):
+    """(first source index, weights q, their sum D, the sum S of their magnitudes) of output
+    index o of an axis of n_src samples resampled to n_out with the bicubic filter: the library's
+    statement of its definition (vp9hip_bicubic_weights, host only)."""
+    fn = lib().vp9hip_bicubic_weights
+    n = _check("vp9hip_bicubic_weights", fn(int(n_src), int(n_out), int(o), None, None, 0, None, None))
+    first, d, a, w = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), (ctypes.c_int32 * n)()
+    _check("vp9hip_bicubic_weights", fn(int(n_src), int(n_out), int(o), ctypes.byref(first), w, n, ctypes.byref(d), ctypes.byref(a)))
+    return first.value, list(w), d.value, a.value
+
+
 def letterbox_rect(w, h, OW, OH, align=(1, 1)):
     """The destination rectangle (dx, dy, dw, dh) that places a w x h picture inside OW x OH
     at its aspect ratio, centred. In integers: if w OH >= h OW the picture takes the full
@@ -691,10 +710,10 @@ def _resample_arg(n, resize, filter, src_rects, dst_rects, fill, bpp, colorspace
         return None
     if resize is None:
         raise ValueError("convert: filter, src_rects, dst_rects and fill need resize=(OW, OH)")
-    if filter not in FILTERS:
-        raise ValueError("convert: filter is 'box' or 'triangle'")
+    if filter not in FILTERS and filter != "bicubic":
+        raise ValueError("convert: filter is 'box', 'triangle' or 'bicubic'")
     ow, oh = (int(x) for x in resize)
-    rs = Resample(FILTERS[filter], ow, oh)
+    rs = Resample(FILTER_BICUBIC if filter == "bicubic" else FILTERS[filter], ow, oh)
     if src_rects is not None:
         rs._src = _rect_array("src_rects", src_rects, n)
         rs.src_rects = ctypes.cast(rs._src, ctypes.POINTER(Rect))
@@ -1062,8 +1081,10 @@ class Device:
         or one per frame: the region resampled instead of the whole visible picture), dst_rects
         (likewise: where in the OW x OH output the picture goes, see letterbox_rect) and fill (the
         three sample codes written elsewhere; default black by the range in effect) take
-        vp9hip_convert_frames_resampled, the exact definitions of include/vp9hip.h; any of them
-        without resize is a ValueError. Runs in the order of torch's current stream (or on
+        vp9hip_convert_frames_resampled, the exact definitions of include/vp9hip.h;
+        filter="bicubic" (Keys a = -1/2, antialiased when downscaling, clipped: within one code of
+        torch's interpolate(mode="bicubic", antialias=True)) takes the same arguments through
+        vp9hip_convert_frames_bicubic; any of them without resize is a ValueError. Runs in the order of torch's current stream (or on
         `stream`, a hipStream_t handle; see _enqueue_for_torch) and does not wait: order it after the frames' producer (sync(), or
         vp9hip_slot_stream_wait), as for frame_tensors. Needs torch imported before the library
         was loaded (see _torch_first)."""
@@ -1076,15 +1097,15 @@ class Device:
         d = OutDesc(OUT_FORMATS[fmt], int(colorspace), int(bool(full_range)), int(w), int(h), int(pitch), int(frame_stride))
         rs = _resample_arg(len(bufs), resize, filter, src_rects, dst_rects, fill, self.bpp, int(colorspace), full_range)
         fn = ("vp9hip_convert_frames" if resize is None else
-              "vp9hip_convert_frames_scaled" if rs is None else "vp9hip_convert_frames_resampled")
+              "vp9hip_convert_frames_scaled" if rs is None else
+              "vp9hip_convert_frames_bicubic" if rs.filter == FILTER_BICUBIC else "vp9hip_convert_frames_resampled")
         if not bufs:
             raise Vp9HipError(fn, EINVAL)
         ow, oh = (w, h) if resize is None else self._resize_arg(fn, resize)
         flat, res, _, _ = self._convert_out(len(bufs), fmt, ow, oh, self.bpp, self.ss_h, self.ss_v, out, pitch, frame_stride)
         arr = (ctypes.c_int * len(bufs))(*bufs)
         if rs is not None:
-            call = lambda st: lib().vp9hip_convert_frames_resampled(self._c, arr, len(bufs), ctypes.byref(d), ctypes.byref(rs),
-                                                                    flat.data_ptr(), st)
+            call = lambda st: getattr(lib(), fn)(self._c, arr, len(bufs), ctypes.byref(d), ctypes.byref(rs), flat.data_ptr(), st)
         elif resize is None:
             call = lambda st: lib().vp9hip_convert_frames(self._c, arr, len(bufs), ctypes.byref(d), flat.data_ptr(), st)
         else:
@@ -1234,7 +1255,8 @@ class Decoder:
         one size, colour space and range) to `fmt` as Device.convert does, with the frames' own
         colour description (vp9hip_decoder_convert; with resize=(OW, OH)
         vp9hip_decoder_convert_scaled; with filter / src_rects / dst_rects / fill as well, which
-        mean what they mean there, vp9hip_decoder_convert_resampled), on torch's current stream; waits for it and releases
+        mean what they mean there, vp9hip_decoder_convert_resampled, or vp9hip_decoder_convert_bicubic for
+        filter="bicubic"), on torch's current stream; waits for it and releases
         the buffers. Returns the tensor(s)."""
         if not _torch_first:
             raise Vp9HipUnavailable("convert: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
@@ -1245,7 +1267,8 @@ class Decoder:
         cs = 2 if f.colorspace in (0, 6) else f.colorspace
         rs = _resample_arg(len(infos), resize, filter, src_rects, dst_rects, fill, f.bpp or 8, cs, f.full_range)
         fn = ("vp9hip_decoder_convert" if resize is None else
-              "vp9hip_decoder_convert_scaled" if rs is None else "vp9hip_decoder_convert_resampled")
+              "vp9hip_decoder_convert_scaled" if rs is None else
+              "vp9hip_decoder_convert_bicubic" if rs.filter == FILTER_BICUBIC else "vp9hip_decoder_convert_resampled")
         if not infos:
             raise Vp9HipError(fn, EINVAL)
         arr = (DecodedFrameInfo * len(infos))(*infos)
@@ -1255,8 +1278,8 @@ class Decoder:
         _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
                                                                 (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
         if rs is not None:
-            call = lambda st: lib().vp9hip_decoder_convert_resampled(self._d, arr, len(infos), OUT_FORMATS[fmt], ctypes.byref(rs),
-                                                                     flat.data_ptr(), 0, 0, st)
+            call = lambda st: getattr(lib(), fn)(self._d, arr, len(infos), OUT_FORMATS[fmt], ctypes.byref(rs),
+                                                 flat.data_ptr(), 0, 0, st)
         elif resize is None:
             call = lambda st: lib().vp9hip_decoder_convert(self._d, arr, len(infos), OUT_FORMATS[fmt], flat.data_ptr(), 0, 0, st)
         else:

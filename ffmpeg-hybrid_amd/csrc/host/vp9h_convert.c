@@ -78,6 +78,43 @@ int vp9hip_resample_weights(int filter, int n_src, int n_out, int o, int *first,
     return (int) (s1 - s0);
 }
 
+/* The bicubic definition (include/vp9hip.h), one output index of one axis, in plain 64-bit
+ * arithmetic from the formulas. With sizes up to 16384, T <= 2^15: u < 2^16, every partial sum
+ * of c is below 2^52, |c 2^Q| below 2^61 (tests/c/bicubic_weights_check.c sweeps the extreme
+ * sizes under UBSan). */
+#define BICUBIC_Q 14
+static int64_t bicubic_q(int64_t u, int64_t t)
+{
+    const int64_t t3 = t * t * t;
+    const int64_t c = u < t ? u * u * (3 * u - 5 * t) + 2 * t3 : ((5 * t - u) * u - 8 * t * t) * u + 4 * t3;
+    const int64_t num = c * ((int64_t) 1 << BICUBIC_Q) + t3, den = 2 * t3;
+    int64_t q = num / den;                             /* truncates: floor it */
+    if (num % den < 0) q--;
+    return q;
+}
+
+int vp9hip_bicubic_weights(int n_src, int n_out, int o, int *first, int32_t *weights, int cap, int64_t *sum,
+                           int64_t *abs_sum)
+{
+    if (n_src < 1 || n_src > 16384 || n_out < 1 || n_out > 16384 || o < 0 || o >= n_out || cap < 0) return VP9HIP_EINVAL;
+    const int64_t w = n_src, ow = n_out, t = 2 * (w > ow ? w : ow), k = (2 * (int64_t) o + 1) * w;
+    const int64_t lo = k - 2 * t + ow;                 /* (2 s + 1) ow > k - 2T */
+    int64_t s0 = lo < 0 ? 0 : lo / (2 * ow);
+    int64_t s1 = (k + 2 * t + ow - 1) / (2 * ow);      /* (2 s + 1) ow < k + 2T */
+    if (s1 > w) s1 = w;
+    int64_t d = 0, a = 0;
+    for (int64_t s = s0; s < s1; s++) {
+        const int64_t e = k - (2 * s + 1) * ow, q = bicubic_q(e < 0 ? -e : e, t);
+        if (weights && s - s0 < cap) weights[s - s0] = (int32_t) q;
+        d += q;
+        a += q < 0 ? -q : q;
+    }
+    if (first) *first = (int) s0;
+    if (sum) *sum = d;
+    if (abs_sum) *abs_sum = a;
+    return (int) (s1 - s0);
+}
+
 int vp9hip_out_coefs(int colorspace, int full_range, int bpp, int out_bits, int32_t c[5], int32_t *shift)
 {
     if (!c || !shift || (bpp != 8 && bpp != 10 && bpp != 12) || (out_bits != 8 && out_bits != bpp)) return VP9HIP_EINVAL;

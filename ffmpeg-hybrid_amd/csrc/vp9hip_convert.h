@@ -61,4 +61,14 @@ struct CvtResampleArgs {
 // One launch of k_convert_resample over n <= CVT_MAX_FRAMES frames; filter: VP9HIP_FILTER_*.
 hipError_t vp9hip_convert_resample_launch(const CvtResampleArgs &a, int format, int hbd, int filter, int n, hipStream_t st);
 
+// The fused bicubic resampling (vp9hip_convert_cubic.hip): the arguments of the resampling
+// kernel and the largest sample code of the source's depth, which the result is clipped to.
+struct CvtCubicArgs {
+    CvtResampleArgs r;
+    int32_t smax;                      // 2^bpp - 1
+};
+
+// One launch of k_convert_cubic over n <= CVT_MAX_FRAMES frames.
+hipError_t vp9hip_convert_cubic_launch(const CvtCubicArgs &a, int format, int hbd, int n, hipStream_t st);
+
 #endif

@@ -377,11 +377,11 @@ extern "C" int vp9hip_decoder_release(vp9hip_decoder *d, int buf)
 }
 
 // Received frames to an output format (vp9hip_convert_frames, vp9hip_convert_frames_scaled
-// when `scaled`, or vp9hip_convert_frames_resampled when `rs`). They are complete (their batch was checked by receive_frame), so nothing is
+// when `scaled`, or vp9hip_convert_frames_resampled when `rs`, vp9hip_convert_frames_bicubic when `cubic` as well). They are complete (their batch was checked by receive_frame), so nothing is
 // ordered here.
 static int decoder_convert(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n, int format, bool scaled,
                            int out_width, int out_height, void *dst_dev, int64_t pitch, int64_t frame_stride, void *stream,
-                           const vp9hip_resample *rs = nullptr)
+                           const vp9hip_resample *rs = nullptr, bool cubic = false)
 {
     if (!d || !frames || n <= 0 || !d->configured) return VP9HIP_EINVAL;
     std::vector<int> bufs(n);
@@ -400,6 +400,7 @@ static int decoder_convert(vp9hip_decoder *d, const vp9hip_decoded_frame *frames
     o.full_range = frames[0].full_range;
     o.width = frames[0].width; o.height = frames[0].height;
     o.pitch = pitch; o.frame_stride = frame_stride;
+    if (rs && cubic) return vp9hip_convert_frames_bicubic(d->ctx, bufs.data(), n, &o, rs, dst_dev, stream);
     if (rs) return vp9hip_convert_frames_resampled(d->ctx, bufs.data(), n, &o, rs, dst_dev, stream);
     if (scaled) return vp9hip_convert_frames_scaled(d->ctx, bufs.data(), n, &o, out_width, out_height, dst_dev, stream);
     return vp9hip_convert_frames(d->ctx, bufs.data(), n, &o, dst_dev, stream);
@@ -424,6 +425,14 @@ extern "C" int vp9hip_decoder_convert_resampled(vp9hip_decoder *d, const vp9hip_
 {
     if (!rs) return VP9HIP_EINVAL;
     return decoder_convert(d, frames, n, format, false, 0, 0, dst_dev, pitch, frame_stride, stream, rs);
+}
+
+extern "C" int vp9hip_decoder_convert_bicubic(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n, int format,
+                                              const vp9hip_resample *rs, void *dst_dev, int64_t pitch,
+                                              int64_t frame_stride, void *stream)
+{
+    if (!rs) return VP9HIP_EINVAL;
+    return decoder_convert(d, frames, n, format, false, 0, 0, dst_dev, pitch, frame_stride, stream, rs, true);
 }
 
 // Motion export: the flags go to the context before it is configured (the first keyframe).

@@ -3010,7 +3010,7 @@ extern "C" int vp9hip_motion_launch_dev(const void *frames_dev, int nframes, int
                                 shape, (hipStream_t) stream) == hipSuccess ? 0 : VP9HIP_EEXTERNAL;
 }
 
-// Output conversion (vp9hip_convert.hip, vp9hip_convert_scale.hip, vp9hip_convert_resample.hip): frames bufs[0 .. n-1] into
+// Output conversion (vp9hip_convert.hip, vp9hip_convert_scale.hip, vp9hip_convert_resample.hip, vp9hip_convert_cubic.hip): frames bufs[0 .. n-1] into
 // dst_dev, enqueued on `stream` (NULL: the current slot's main stream). Everything is
 // validated before the first launch, so a refused call writes nothing. The buffers' pointers
 // travel as kernel arguments, CVT_MAX_FRAMES per launch: no device table, no copy, nothing to
@@ -3128,12 +3128,34 @@ static int64_t resample_d_upper(int filter, int n_src, int n_out)
     return m2 * (m2 / n_out + 1);
 }
 
-// The same with a filter, a source and a destination rectangle per frame and the fill
-// (k_convert_resample). Every frame's rectangles are checked before the first launch.
-extern "C" int vp9hip_convert_frames_resampled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d,
-                                               const vp9hip_resample *rs, void *dst_dev, void *stream)
+// S = max over o of sum |q(o, s)| for one axis of the bicubic filter (vp9hip_bicubic_weights is
+// the definition): the bound's two factors. About 4 max(n_src, n_out) taps in all.
+static int64_t bicubic_max_s(int n_src, int n_out)
 {
-    if (!rs || (rs->filter != VP9HIP_FILTER_BOX && rs->filter != VP9HIP_FILTER_TRIANGLE)) return VP9HIP_EINVAL;
+    int64_t m = 0, a;
+    for (int o = 0; o < n_out; o++) {
+        vp9hip_bicubic_weights(n_src, n_out, o, nullptr, nullptr, 0, nullptr, &a);
+        m = std::max(m, a);
+    }
+    return m;
+}
+
+// S <= this, in O(1): |q| <= 2^14, and the taps of one output are the s with (2s+1) n_out inside
+// an open interval of length 4T = 8M, at most 4M / n_out + 1 of them. Only extreme reductions
+// need the exact maxima.
+static int64_t bicubic_s_upper(int n_src, int n_out)
+{
+    const int64_t m4 = 4 * (int64_t) std::max(n_src, n_out);
+    return ((int64_t) 1 << 14) * (m4 / n_out + 1);
+}
+
+// vp9hip_convert_frames_resampled and vp9hip_convert_frames_bicubic: a filter (VP9HIP_FILTER_*,
+// checked by the entry), a source and a destination rectangle per frame and the fill. Every
+// frame's rectangles are checked before the first launch.
+static int convert_resampled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d, const vp9hip_resample *rs,
+                             void *dst_dev, void *stream)
+{
+    const bool cubic = rs->filter == VP9HIP_FILTER_BICUBIC;
     const int OW = rs->out_width, OH = rs->out_height;
     if (OW < 1 || OW > 16384 || OH < 1 || OH > 16384) return VP9HIP_EINVAL;
     CvtResampleArgs s;
@@ -3155,7 +3177,7 @@ extern "C" int vp9hip_convert_frames_resampled(vp9hip_ctx *c, const int *bufs, i
     // the rectangles in effect, and the bound on every (source -> destination) geometry
     const vp9hip_rect whole_src = { 0, 0, d->width, d->height }, whole_dst = { 0, 0, OW, OH };
     std::vector<vp9hip_rect> src(n, whole_src), dst(n, whole_dst);
-    const unsigned __int128 lim = (unsigned __int128) 1 << 63;
+    const unsigned __int128 lim = (unsigned __int128) 1 << (cubic ? 62 : 63);
     const int64_t maxv = (1 << c->bpp) - 1;
     for (int i = 0; i < n; i++) {
         if (rs->src_rects) src[i] = rs->src_rects[i];
@@ -3172,9 +3194,14 @@ extern "C" int vp9hip_convert_frames_resampled(vp9hip_ctx *c, const int *bufs, i
             return (unsigned __int128) dx * (unsigned __int128) dy * (unsigned __int128) maxv >= lim;
         };
         for (const auto &g : geo)
-            if (over(resample_d_upper(rs->filter, g[0], g[2]), resample_d_upper(rs->filter, g[1], g[3])) &&
-                over(resample_max_d(rs->filter, g[0], g[2]), resample_max_d(rs->filter, g[1], g[3]))) return VP9HIP_EINVAL;
+            if (cubic) {
+                if (over(bicubic_s_upper(g[0], g[2]), bicubic_s_upper(g[1], g[3])) &&
+                    over(bicubic_max_s(g[0], g[2]), bicubic_max_s(g[1], g[3]))) return VP9HIP_EINVAL;
+            } else if (over(resample_d_upper(rs->filter, g[0], g[2]), resample_d_upper(rs->filter, g[1], g[3])) &&
+                       over(resample_max_d(rs->filter, g[0], g[2]), resample_max_d(rs->filter, g[1], g[3]))) return VP9HIP_EINVAL;
     }
+    CvtCubicArgs cu;
+    cu.smax = (int32_t) maxv;
     hipSetDevice(c->dev);
     hipStream_t st = stream ? (hipStream_t) stream : c->st;
     for (int i0 = 0; i0 < n; i0 += CVT_MAX_FRAMES) {
@@ -3185,9 +3212,29 @@ extern "C" int vp9hip_convert_frames_resampled(vp9hip_ctx *c, const int *bufs, i
             s.dst_rect[i] = dst[i0 + i];
         }
         a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
-        HIPCHK(vp9hip_convert_resample_launch(s, d->format, c->hb, rs->filter, k, st));
+        if (cubic) {
+            cu.r = s;
+            HIPCHK(vp9hip_convert_cubic_launch(cu, d->format, c->hb, k, st));
+        } else
+            HIPCHK(vp9hip_convert_resample_launch(s, d->format, c->hb, rs->filter, k, st));
     }
     return 0;
+}
+
+// The resampling with the box or the triangle filter (k_convert_resample).
+extern "C" int vp9hip_convert_frames_resampled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d,
+                                               const vp9hip_resample *rs, void *dst_dev, void *stream)
+{
+    if (!rs || (rs->filter != VP9HIP_FILTER_BOX && rs->filter != VP9HIP_FILTER_TRIANGLE)) return VP9HIP_EINVAL;
+    return convert_resampled(c, bufs, n, d, rs, dst_dev, stream);
+}
+
+// The same with the bicubic filter (k_convert_cubic).
+extern "C" int vp9hip_convert_frames_bicubic(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d,
+                                             const vp9hip_resample *rs, void *dst_dev, void *stream)
+{
+    if (!rs || rs->filter != VP9HIP_FILTER_BICUBIC) return VP9HIP_EINVAL;
+    return convert_resampled(c, bufs, n, d, rs, dst_dev, stream);
 }
 
 extern "C" int vp9hip_flush(vp9hip_ctx *c)

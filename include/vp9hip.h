@@ -43,7 +43,10 @@ extern "C" {
  * vp9hip_resample) came later, again as new symbols and new structs only: no existing struct
  * changed, so the version stayed. The motion export (vp9hip_set_export, vp9hip_frame_motion,
  * vp9hip_download_motion, vp9hip_motion_host, vp9hip_decoder_set_export,
- * vp9hip_decoder_frame_motion) likewise: new symbols only. */
+ * vp9hip_decoder_frame_motion) likewise: new symbols only. The bicubic filter
+ * (VP9HIP_FILTER_BICUBIC, vp9hip_convert_frames_bicubic, vp9hip_decoder_convert_bicubic,
+ * vp9hip_bicubic_weights) likewise: a new macro and new symbols, the filter enum and
+ * vp9hip_resample unchanged. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -333,7 +336,7 @@ int  vp9hip_convert_frames(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip
  * is the identity, and upscaling is nearest-neighbour with blended seams (an output sample
  * inside one source sample copies it, one across a boundary blends the two by area); the
  * interpolating (bilinear) filter is VP9HIP_FILTER_TRIANGLE of
- * vp9hip_convert_frames_resampled below; bicubic is not offered.
+ * vp9hip_convert_frames_resampled below, bicubic is vp9hip_convert_frames_bicubic.
  *
  * For a visible source of w x h luma and cw x ch chroma (cw = (w + ss_h) >> ss_h) and an
  * output of OW x OH:
@@ -402,8 +405,9 @@ int  vp9hip_convert_frames_scaled(vp9hip_ctx *ctx, const int *bufs, int n, const
  *
  * Checked as vp9hip_convert_frames, plus the above, before the first launch (a refused call
  * writes nothing): any violation, a NULL vp9hip_resample or an unknown filter is
- * VP9HIP_EINVAL. Not offered: bicubic / Lanczos (negative lobes need a clip and fixed-point
- * tables), siting-aware chroma, mean / std normalisation, rotation.
+ * VP9HIP_EINVAL (VP9HIP_FILTER_BICUBIC included: it has an entry of its own,
+ * vp9hip_convert_frames_bicubic below). Not offered: Lanczos, siting-aware chroma, mean / std
+ * normalisation, rotation.
  */
 enum { VP9HIP_FILTER_BOX, VP9HIP_FILTER_TRIANGLE };
 typedef struct vp9hip_rect { int32_t x, y, w, h; } vp9hip_rect;
@@ -423,6 +427,55 @@ int  vp9hip_convert_frames_resampled(vp9hip_ctx *ctx, const int *bufs, int n, co
  * out of range, cap < 0. */
 int  vp9hip_resample_weights(int filter, int n_src, int n_out, int o,
                              int *first, int32_t *weights, int cap, int64_t *sum);
+/*
+ * Bicubic resampling, with the struct, the rectangles, the fill, the formats and the layout of
+ * vp9hip_convert_frames_resampled, and one launch per 32 frames like it. Integer and exact,
+ * one right answer (DESIGN.md "Resampling: bicubic"). The filter is the Keys cubic with
+ * a = -1/2 (Catmull-Rom), widened when downscaling (antialiased): the kernel of torch's
+ * interpolate(mode="bicubic", antialias=True) and of PIL's BICUBIC.
+ *
+ * One axis of n_src source samples and n_out output samples: M = max(n_src, n_out), T = 2M,
+ * Q = 14. For output index o and source index s, 0 <= s < n_src:
+ *   u      = |(2o+1) n_src - (2s+1) n_out|     the distance in units of 1/T of the filter's
+ *                                              unit; the tap is present iff u < 2T
+ *   c(u)   = 3u^3 - 5T u^2 + 2T^3              for u < T
+ *          = -u^3 + 5T u^2 - 8T^2 u + 4T^3     for T <= u < 2T   (c / 2T^3 is Keys at x = u/T)
+ *   q(o,s) = floor((c(u) 2^Q + T^3) / (2T^3))  floor toward -inf: round half up;
+ *                                              -1,214 <= q <= 2^14 (Keys is >= -2/27)
+ *   D(o)   = sum_s q(o,s) over the present taps, > 0
+ * cub(P, ow, oh) of a w x h plane P of integer samples at bpp bits, with qx, Dx from (w, ow)
+ * and qy, Dy from (h, oh):
+ *   A(ox, oy) = sum_sy qy sum_sx qx P[sy][sx]                        exact signed integers
+ *   cub = clip(floor((A + (Dx Dy >> 1)) / (Dx Dy)), 0, 2^bpp - 1)
+ * One rounding, then one clip (the negative lobes overshoot); no normalised weight tables, so
+ * any evaluation order gives the same integers. Taps outside the plane, or outside the source
+ * rectangle, are absent from A and D alike. ow == w is the identity (every other tap has u a
+ * multiple of T, where c is 0 exactly); a constant plane stays constant. The weights are Keys
+ * rounded to Q = 14 bits, so the result is within one code of the rounded and clipped value of
+ * torch's float64 interpolate(mode="bicubic", antialias=True, align_corners=False), not that
+ * value itself (at 12 bits about 5 % of samples differ by that one); Q = 16 would pass 64 bits
+ * in c 2^Q at T = 2^15, so Q is not tunable.
+ * Bound: with S = max_o sum_s |q(o,s)| of an axis, a call is accepted only if
+ * Sx Sy (2^bpp - 1) < 2^62 for every (source geometry -> destination geometry) pair it uses,
+ * luma and chroma (7680 x 4320 at 12 bits -> 1 x 1 and -> 2 x 2 are over it, -> 4 x 4 and the
+ * 8-bit -> 1 x 1 are under it).
+ *
+ * rs->filter must be VP9HIP_FILTER_BICUBIC; everything else of rs, the source and destination
+ * rectangles' rules, the chroma rectangles and the fill codes are those of
+ * vp9hip_convert_frames_resampled. Checked before the first launch (a refused call writes
+ * nothing): any violation, a NULL rs or another filter is VP9HIP_EINVAL. Not offered: Lanczos,
+ * siting-aware chroma, mean / std normalisation, rotation.
+ */
+#define VP9HIP_FILTER_BICUBIC 2
+int  vp9hip_convert_frames_bicubic(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip_out_desc *d,
+                                   const vp9hip_resample *rs, void *dst_dev, void *stream);
+/* Host only: the C statement of the bicubic definition. The present taps of output index o of
+ * an axis of n_src source samples resampled to n_out (both 1..16384): returns their count,
+ * *first = the first source index, weights[0 .. min(count, cap) - 1] = q, *sum = D(o) and
+ * *abs_sum = sum |q|; first / weights / sum / abs_sum may be NULL. VP9HIP_EINVAL: a size or o
+ * out of range, cap < 0. */
+int  vp9hip_bicubic_weights(int n_src, int n_out, int o, int *first, int32_t *weights, int cap,
+                            int64_t *sum, int64_t *abs_sum);
 
 /* ---- motion export: the stream's own motion field and block modes as device tensors ----
  * The second product of the decode besides the pixels (FFmpeg's AV_FRAME_DATA_MOTION_VECTORS /
@@ -853,6 +906,10 @@ int  vp9hip_decoder_convert_scaled(vp9hip_decoder *dec, const vp9hip_decoded_fra
 int  vp9hip_decoder_convert_resampled(vp9hip_decoder *dec, const vp9hip_decoded_frame *frames, int n, int format,
                                       const vp9hip_resample *rs, void *dst_dev, int64_t pitch,
                                       int64_t frame_stride, void *stream);
+/* The same through vp9hip_convert_frames_bicubic (rs->filter == VP9HIP_FILTER_BICUBIC). */
+int  vp9hip_decoder_convert_bicubic(vp9hip_decoder *dec, const vp9hip_decoded_frame *frames, int n, int format,
+                                    const vp9hip_resample *rs, void *dst_dev, int64_t pitch,
+                                    int64_t frame_stride, void *stream);
 /* Motion export (see vp9hip_set_export): flags = VP9HIP_EXPORT_MOTION makes every decoded frame,
  * hidden ones included, leave its motion field beside its pixels. Call before the first
  * vp9hip_decoder_send_packet; VP9HIP_EINVAL afterwards. The flags reach the context before it is

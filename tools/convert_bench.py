@@ -22,7 +22,13 @@ caller does without it), beside the box kernel (resize= alone) and the new kerne
 filter at the same shapes; 32 rectangles of 256x256 out of 4 frames to 224x224; a 1920x1080 ->
 3840x2160 triangle upscale to rgb24; each with the copy of the same total bytes.
 
-    python tools/convert_bench.py [--out profiles/NAME.json] [--sections convert,resize,resample]
+The bicubic cases (vp9hip_convert_frames_bicubic) are `--frames` frames to 224x224 rgbp_f16, the
+whole output and letterboxed (letterbox_rect), each timed beside the triangle kernel on the same
+inputs and beside the full-size conversion followed by
+torch.nn.functional.interpolate(mode="bicubic", antialias=True) of the half tensor to the
+picture's size (the letterbox's paste into the fill is left out of that yardstick, in its favour).
+
+    python tools/convert_bench.py [--out profiles/NAME.json] [--sections convert,resize,resample,bicubic]
 
 Prints one JSON line. Needs a GPU; there is no fallback.
 """
@@ -142,6 +148,41 @@ def resample_cases(dev, args, copy_of, w, h, n):
     return out_cases
 
 
+def bicubic_cases(dev, args, w, h, n):
+    """The bicubic kernel, the triangle kernel and the two-step path on the same inputs."""
+    cases = []
+    bufs = list(range(n))
+    fmt, ow, oh = "rgbp_f16", 224, 224
+    dev.configure(w, h, 8, nbufs=n)
+    dev.fill(0, n, 0x55)
+    dev.sync()
+    out = torch.empty(n * v9.out_layout(fmt, ow, oh, 8)[0], dtype=torch.uint8, device="cuda")
+    full = torch.empty(n * v9.out_layout(fmt, w, h, 8)[0], dtype=torch.uint8, device="cuda")
+    for name, dst in (("whole output", None), ("letterbox", v9.letterbox_rect(w, h, ow, oh))):
+        pw, ph = (ow, oh) if dst is None else dst[2:]
+        cub = timed(lambda: dev.convert(bufs, fmt, colorspace=2, out=out, resize=(ow, oh), filter="bicubic", dst_rects=dst),
+                    args.warmup, args.reps)
+        tri = timed(lambda: dev.convert(bufs, fmt, colorspace=2, out=out, resize=(ow, oh), filter="triangle", dst_rects=dst),
+                    args.warmup, args.reps)
+
+        def two_step():
+            r = dev.convert(bufs, fmt, colorspace=2, out=full)
+            return torch.nn.functional.interpolate(r, size=(ph, pw), mode="bicubic", antialias=True)
+        e = {"case": name, "bpp": 8, "format": fmt, "source": [w, h], "frames": n, "resize": [ow, oh],
+             "dst_rect": None if dst is None else list(dst),
+             "bicubic_ms": {"median": cub[0], "min": cub[1], "max": cub[2]},
+             "triangle_ms": {"median": tri[0], "min": tri[1], "max": tri[2]},
+             "ratio_to_triangle": cub[0] / tri[0], "us_per_frame": 1e3 * cub[0] / n}
+        try:
+            two = timed(two_step, max(2, args.warmup // 4), max(5, args.reps // 4))
+            e["convert_then_framework_resize_ms"] = {"median": two[0], "min": two[1], "max": two[2]}
+            e["speedup_over_two_steps"] = two[0] / cub[0]
+        except RuntimeError as err:      # reported, not worked around: the yardstick is what it is
+            e["convert_then_framework_resize_error"] = str(err)[:300]
+        cases.append(e)
+    return cases
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="3840x2160")
@@ -150,7 +191,8 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--only", default=None,
                     help="comma list of cases to run, e.g. rgb24,rgbp_f16@224x224 (default: all); for profiler runs")
-    ap.add_argument("--sections", default="convert,resize,resample", help="comma list of convert, resize, resample")
+    ap.add_argument("--sections", default="convert,resize,resample,bicubic",
+                    help="comma list of convert, resize, resample, bicubic")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     sections = set(args.sections.split(","))
@@ -260,6 +302,8 @@ def main():
                     raise RuntimeError("hipMemcpyAsync failed")
             return timed(copy, args.warmup, args.reps)
         res["resample_cases"] = resample_cases(dev, args, copy_of, w, h, n)
+    if "bicubic" in sections and only is None:
+        res["bicubic_cases"] = bicubic_cases(dev, args, w, h, n)
     dev.close()
     line = json.dumps(res)
     print(line)
