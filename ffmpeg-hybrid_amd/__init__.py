@@ -301,6 +301,7 @@ def lib():
     L.vp9hip_intra_job_dev.argtypes = [ctypes.c_int] * 13 + [ctypes.POINTER(ctypes.c_int32)]
     L.vp9hip_plan_sched_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4
     L.vp9hip_plan_heights_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2
+    L.vp9hip_plan_emit_host.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4
     L.vp9hip_test_plan_records.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)] + [ctypes.c_void_p] * 4
     # motion export
     L.vp9hip_set_export.argtypes = [vp, ctypes.c_int]
@@ -435,6 +436,18 @@ def plan_heights_host(ss_h, ss_v, ja):
     heights = np.empty(len(ja), np.uint32)
     _check("vp9hip_plan_heights_host", lib().vp9hip_plan_heights_host(ss_h, ss_v, len(ja), ja.ctypes.data, heights.ctypes.data))
     return heights
+
+
+def plan_emit_host(ss_h, ss_v, ja):
+    """The same schedule from the device planner's own pass loop and emit run on the host
+    (vp9hip_plan_emit_host: the kernel's routines, a loop over 64 slots in place of the lanes); ja
+    as for plan_sched_host. Returns (order, passes, njobs) in plan_sched_host's layout."""
+    ja = np.ascontiguousarray(ja, np.uint32)
+    n = len(ja)
+    order, passes, njobs = np.full(n, 0xffff, np.uint16), np.empty(max(n, 1), np.uint32), ctypes.c_int(0)
+    npass = _check("vp9hip_plan_emit_host", lib().vp9hip_plan_emit_host(ss_h, ss_v, n, ja.ctypes.data, order.ctypes.data,
+                                                                       passes.ctypes.data, ctypes.addressof(njobs)))
+    return order, passes[:npass].copy(), njobs.value
 
 
 def intra_txfm_type(mode):

@@ -115,7 +115,8 @@ typedef struct PlanDev {
     uint32_t cap_cnt, cap_cntm, cap_rjobs, cap_mcs, cap_dlists, nkeys, nframes;
     unsigned long long *prof;        /* diagnostics (VP9HIP_PLAN_PROF): k_psb / k_pjplan cycles per phase, or null */
     int dbg;                         /* diagnostics (VP9HIP_PLAN_DBG): ablation switches, timing only:  */
-                                     /* 2 no pass building, 4 staged step order, 16 no heights relaxation */
+                                     /* 2 no pass building, 4 staged step order, 16 no heights relaxation, */
+                                     /* 32 no emit after the pass loop (records missing: planner-only runs) */
     int static_lists;                /* the intra step lists were staged by the host (static plan):  */
                                      /* no step keys; an intra-frame SB without intra jobs fails    */
     const uint32_t *stat_ko;         /* static plan: the step lists' offsets (nkeys + 1), k_psort    */

@@ -436,15 +436,17 @@ template <int JCAP> struct alignas(16) PlanLds {   // 16: jmap rows are stored 1
             union {
                 uint16_t dep[4 * JCAP];
                 struct {
-                    uint32_t mk[JCAP];        // pl_deps' masks of job j: the units it waits for
-                    // units whose job an earlier pass took: bit u of drow[p * 16 + v] and bit v
-                    // of dcol[p * 16 + u] for unit (u, v) of plane p (a fourth plane's worth, and
-                    // indices masked to 63, so that no job word can address past them)
-                    uint32_t drow[64], dcol[64];
+                    // pl_deps' masks of job j: the units it waits for (after the pass loop: the
+                    // pass words, counted from the positions' records)
+                    uint32_t mk[JCAP];
+                    // units whose job an earlier pass took: bit u of the 16-bit row p * 16 + v and
+                    // bit v of the 16-bit column p * 16 + u for unit (u, v) of plane p, two rows
+                    // to a word (pl_done_bits; a fourth plane's worth, and indices masked, so that
+                    // no job word can address past them)
+                    uint32_t drow[32], dcol[32];
                 } rd;
             } d;
             uint32_t hs[64];              // height histogram -> list starts (before: the heights' spare words)
-            uint16_t tk[16];              // jobs taken by the pass being built
         } b;
     } u;
 };
@@ -457,6 +459,15 @@ DEV uint32_t needs_of(uint32_t a)
     return (uint32_t) pl_slot_needs((int) ((a >> 8) & 15));
 }
 DEV uint32_t wor(uint32_t v) { return rdl(wscan_dpp<OP_OR>(v), 63); }
+DEV bool wany(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
+// f(integral_constant<int, c>) for c = 0 .. N - 1: an unrolled loop over the chunks of a lane's register arrays
+template <int N, class F> DEV void each_chunk(F &&f)
+{
+    if constexpr (N > 0) {
+        each_chunk<N - 1>(f);
+        f(std::integral_constant<int, N - 1>());
+    }
+}
 
 // One wave per SB: the residual jobs (every coded tx block, bucketed by transform) and the
 // intra job words of the SB, from k_psb's records alone: no block, no eob entry is read again.
@@ -692,7 +703,7 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, const SbGeo &G, PlanLds<2
         hreg[c] = j < NJ ? pl_min((int) S.u.b.h.hgt[j], 63) : -1;
         if (j < NJ) S.u.b.d.rd.mk[j] = mreg[c];
     }
-    S.u.b.d.rd.drow[lane] = S.u.b.d.rd.dcol[lane] = 0;
+    if (lane < 32) S.u.b.d.rd.drow[lane] = S.u.b.d.rd.dcol[lane] = 0;
     S.u.b.hs[lane] = 0;
     wsync();
 #pragma unroll
@@ -729,89 +740,149 @@ DEV void plan_sb(const PlanDev &D, const PlanFrame &F, const SbGeo &G, PlanLds<2
     wsync();
     PPT(10);
     // ---- list scheduling (merge_mixed): each pass takes, in priority order, every ready job
-    // (all producers in earlier passes) that still fits in 64 lanes; lane groups by size
+    // (all producers in earlier passes) that still fits in 64 lanes; lane groups by size.
+    // The pass loop only decides: a taken lane notes its pass and its rank among the pass's jobs
+    // of its size, and marks its units done. The jobs and the pass words are written once, after
+    // the loop, chunk-wide (the epilogue below).
     uint32_t *gpass = D.passes + (size_t) slot * JCAP;
     PJob *gjob = D.pjobs + (size_t) slot * JCAP;
     int done = 0, npass = 0;
     // Each lane holds, per chunk c of the priority order, position c * 64 + lane: its job with
-    // its size code and the done words of its two runs (job | ts << 10 | top run's drow index
-    // << 12 | left run's dcol index << 18; index 0 of the plane where the job has no such run:
-    // its mask is empty there), its masks, and bit c of `pend` while it is unscheduled. A job is
-    // ready when the done words hold every unit of its masks: two independent LDS reads.
-    uint32_t jwreg[NCH], mkreg[NCH];
+    // its size code and the done rows of its two runs (pl_jw), its masks, what it ORs into the
+    // done bits once taken (pl_done_bits for its rows and its columns, pl_done_reg: computed here,
+    // once, not at every take), its record once taken (pl_take_rec; registers, not LDS: the
+    // resource report allows it), and bit c of `pend` while it is unscheduled. A job is ready
+    // when the done rows hold every unit of its masks: two independent 16-bit LDS reads.
+    uint32_t jwreg[NCH], mkreg[NCH], rcreg[NCH], drreg[NCH], dcreg[NCH], dxreg[NCH];
     uint32_t pend = 0;
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
         const int pos = c * 64 + lane;
-        jwreg[c] = mkreg[c] = 0;
+        jwreg[c] = mkreg[c] = drreg[c] = dcreg[c] = dxreg[c] = 0;
+        rcreg[c] = PL_REC_NONE;
         if (pos < NJ) {
             const uint32_t j = S.u.b.h.ord[pos], a = S.ja[j];
-            const uint32_t p = a & 3, ux0 = (a >> 12) & 15, uy0 = (a >> 16) & 15;
-            jwreg[c] = j | ((a >> 2) & 3) << 10 | (p * 16 + (uy0 ? uy0 - 1 : 0)) << 12 | (p * 16 + (ux0 ? ux0 - 1 : 0)) << 18;
+            const int p = a & 3, ts = (a >> 2) & 3, ux0 = (a >> 12) & 15, uy0 = (a >> 16) & 15;
+            jwreg[c] = pl_jw(j, a);
+            drreg[c] = pl_done_bits(ts, ux0, uy0);
+            dcreg[c] = pl_done_bits(ts, uy0, ux0);
+            dxreg[c] = pl_done_reg(p, ts, ux0, uy0);
             mkreg[c] = S.u.b.d.rd.mk[j];
             pend |= 1u << c;
         }
     }
+    const uint16_t *drow16 = (const uint16_t *) S.u.b.d.rd.drow, *dcol16 = (const uint16_t *) S.u.b.d.rd.dcol;      // the 16-bit rows
     if (D.dbg & 2) done = NJ;                 // ablation (timing only): no pass building
     while (done < NJ) {
-        int budget = 64, ntake = 0;
+        // No job of a pass may see another job of the same pass as done, and the takes below
+        // mark their units at once. So the readiness of every chunk is read here, at the top of
+        // the pass, before the first update (the batched form: one bit per chunk in one register,
+        // 2 NCH reads back to back with no branch around them, at 4:4:4 too: the reads' results
+        // die into `rdy` one by one and cost no registers). The wave's LDS operations execute
+        // in program order; wsync() at the pass's end holds the compiler to it.
+        uint32_t rdy = 0;
 #pragma unroll
         for (int c = 0; c < NCH; c++) {
-            if (budget < 4) break;
-            bool cand = (pend >> c) & 1u;
-            if (!__any(cand)) continue;           // every job of this chunk is scheduled
             const uint32_t jw = jwreg[c], mk = mkreg[c];
             // every lane reads (scheduled and empty positions too: their indices are valid)
-            const uint32_t have = S.u.b.d.rd.drow[(jw >> 12) & 63] | S.u.b.d.rd.dcol[(jw >> 18) & 63] << 16;
-            cand = cand && (have & mk) == mk;
-            if (!__any(cand)) continue;           // nothing ready in this chunk
-            // takes in priority order by lane-size prefix sums: the longest prefix of the chunk's
+            const uint32_t have = drow16[PL_JW_ROW(jw)] | (uint32_t) dcol16[PL_JW_COL(jw)] << 16;
+            rdy |= (have & mk) == mk ? 1u << c : 0u;
+        }
+        rdy &= pend;
+        int budget = 64;
+        uint32_t pc = 0;                      // class counts of the pass so far, a byte each
+        // (each_chunk, not a loop under #pragma unroll: at 4:4:4 the compiler leaves the twelve
+        // visits rolled, and the lanes' register arrays then go through indexed moves)
+        each_chunk<NCH>([&](auto C) {
+            constexpr int c = decltype(C)::value;
+            if (budget < 4) return;
+            const bool cand = (rdy >> c) & 1u;
+            if (!wany(cand)) return;              // nothing ready in this chunk
+            // takes in priority order by one packed prefix sum: the longest prefix of the chunk's
             // ready jobs that fits. (A second round over the jobs skipped can take nothing: the
             // first one skipped is larger than the lanes left, and so is every prefix sum after
             // it. Any packing that respects the producers is exact; only the pass count
             // depends on it.)
-            const uint32_t incl = wscan_incl(cand ? 4u << ((jw >> 10) & 3) : 0u, lane);
+            // (the position's word through an empty asm: what the take derives from it is the
+            // same in every pass, and hoisted out of the loop it costs some 50 registers at 4:2:0)
+            uint32_t jw = jwreg[c];
+            asm volatile("" : "+v"(jw));
+            const uint32_t ts8 = PL_JW_TS8(jw);
+            const uint32_t pre = wscan_incl(cand ? pl_take_val(ts8) : 0u, lane), incl = pl_take_lanes(pre);
             const bool take = cand && incl <= (uint32_t) budget;
-            const uint64_t m = __ballot(take);
-            if (!m) continue;
+            const uint64_t m = __builtin_amdgcn_ballot_w64(take);
+            if (!m) return;
+            // the job's units are done for the passes that follow: one 32-bit OR for its rows and
+            // one for its columns, and the next word (16x16) or three (32x32) in the visits that
+            // take such a job
+            uint32_t dx = dxreg[c];
+            asm volatile("" : "+v"(dx));           // (as jw above: its fields are not hoisted)
+            const uint32_t dr = drreg[c], dc = dcreg[c], ri = PL_DONE_ROW(dx), ci = PL_DONE_COL(dx);
             if (take) {
                 pend &= ~(1u << c);
-                S.u.b.tk[ntake + (int) mbcnt(m)] = (uint16_t) (jw & 1023);
+                rcreg[c] = pl_take_rec(npass, pre, pc, ts8);
+                atomicOr(&S.u.b.d.rd.drow[ri], dr);
+                atomicOr(&S.u.b.d.rd.dcol[ci], dc);
             }
-            ntake += __popcll(m);
-            budget -= (int) rdl(incl, 63 - __builtin_clzll(m));
-        }
-        wsync();
-        if (ntake == 0) { st |= PLS_SCHED; break; }
-        // emit: sizes 32, 16, 8, 4, take order within a size
-        const int J = lane < ntake ? S.u.b.tk[lane] : 0;
-        const int ts = lane < ntake ? (int) ((S.ja[J] >> 2) & 3) : -1;
-        uint32_t cnt[4], at = 0;
-        int mypos = 0;
-        for (int q = 3; q >= 0; q--) {
-            const uint64_t m = __ballot(ts == q);
-            cnt[q] = (uint32_t) __popcll(m);
-            if (ts == q) mypos = (int) (at + mbcnt(m));
-            at += cnt[q];
-        }
-        if (lane < ntake) {
-            const uint32_t a = S.ja[J];
-            PJob pj;
-            pj.a = a & ~JA_TRX;
-            pj.roff = ((a >> 4) & 1) ? rbase + pl_resid_unit(a & 3, (a >> 12) & 15, (a >> 16) & 15, SSH, SSV) : 0u;
-            if (inb(D, (uint32_t) (done + mypos), JCAP, 128u)) gjob[done + mypos] = pj;
-            // the job's units are done for the passes that follow (after the take: the jobs of
-            // one pass do not see each other)
-            const uint32_t n4 = 1u << ((a >> 2) & 3), ux0 = (a >> 12) & 15, uy0 = (a >> 16) & 15, bits = (1u << n4) - 1u;
-            for (uint32_t i = 0; i < n4; i++) {
-                atomicOr(&S.u.b.d.rd.drow[((a & 3) * 16 + uy0 + i) & 63], bits << ux0);
-                atomicOr(&S.u.b.d.rd.dcol[((a & 3) * 16 + ux0 + i) & 63], bits << uy0);
+            const bool big = take && PL_DONE_TS(dx) >= 2;
+            if (wany(big)) {
+                if (big) {
+                    atomicOr(&S.u.b.d.rd.drow[(ri + 1) & 31], dr);
+                    atomicOr(&S.u.b.d.rd.dcol[(ci + 1) & 31], dc);
+                }
+                if (big && PL_DONE_TS(dx) == 3)
+                    for (uint32_t i = 2; i < 4; i++) {
+                        atomicOr(&S.u.b.d.rd.drow[(ri + i) & 31], dr);
+                        atomicOr(&S.u.b.d.rd.dcol[(ci + i) & 31], dc);
+                    }
             }
-        }
-        if (lane == 0 && inb(D, (uint32_t) npass, JCAP, 256u)) gpass[npass] = (uint32_t) done << 14 | cnt[0] << 9 | cnt[1] << 5 | cnt[2] << 2 | cnt[3];
-        done += ntake;
+            const int last = 63 - __builtin_clzll(m);
+            pc += rdl(pre, last);
+            budget -= (int) rdl(incl, last);
+        });
+        if (pc == 0) { st |= PLS_SCHED; break; }
+        done += (int) pl_take_count(pc);
         npass++;
         wsync();
+    }
+    // ---- epilogue: the pass words and the jobs, once. The passes' class counts are counted
+    // from the records (one LDS add per chunk of positions; the masks' words are dead), lanes own
+    // passes for the scan that gives each pass its first job, and each position's index is its
+    // pass's first job, the jobs of larger sizes in the pass, and its rank (pl_emit_index).
+    // (VP9HIP_PLAN_DBG bit 5, timing only: no epilogue; the records are then missing)
+    if (!(D.dbg & 32)) {
+        uint32_t *pw = S.u.b.d.rd.mk;
+        for (int P = lane; P < npass; P += 64) pw[P] = 0;
+        wsync();
+        each_chunk<NCH>([&](auto C) {
+            constexpr int c = decltype(C)::value;
+            if (c * 64 < NJ && rcreg[c] != PL_REC_NONE) atomicAdd(&pw[rcreg[c] & 1023u], pl_take_val(PL_JW_TS8(jwreg[c])));
+        });
+        wsync();
+        uint32_t carry = 0;
+        for (int g = 0; g < npass; g += 64) {
+            const int P = g + lane;
+            const uint32_t cls = P < npass ? pw[P] : 0u, tot = pl_take_count(cls);
+            const uint32_t incl = wscan_incl(tot, lane);
+            const uint32_t w = pl_pass_word(pl_pass_first(carry, incl, tot), cls);
+            carry += rdl(incl, 63);
+            if (P < npass) {
+                pw[P] = w;
+                if (inb(D, (uint32_t) P, JCAP, 256u)) gpass[P] = w;
+            }
+        }
+        wsync();
+        each_chunk<NCH>([&](auto C) {
+            constexpr int c = decltype(C)::value;
+            const uint32_t rc = rcreg[c], jw = jwreg[c];
+            if (c * 64 < NJ && rc != PL_REC_NONE) {
+                const uint32_t a = S.ja[PL_JW_J(jw)], at = pl_emit_index(pw[rc & 1023u], rc, PL_JW_TS(jw));
+                PJob pj;
+                pj.a = a & ~JA_TRX;
+                pj.roff = ((a >> 4) & 1) ? rbase + pl_resid_unit(a & 3, (a >> 12) & 15, (a >> 16) & 15, SSH, SSV) : 0u;
+                if (inb(D, at, JCAP, 128u)) gjob[at] = pj;
+            }
+        });
     }
     if (lane == 0) {
         SBRec sr;

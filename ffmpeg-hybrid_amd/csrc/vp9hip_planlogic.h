@@ -274,6 +274,79 @@ PL_HD void pl_heights_chunk(uint32_t *hgt, const uint16_t *dep, const uint16_t *
     }
 }
 
+/* ---- the pass loop's take and the emit after it (plan_sb of vp9hip_plan.hip; on the host
+ * vp9hip_plan_emit_host, a loop over 64 slots in place of the wave's lanes). A pass takes, chunk
+ * by chunk of 64 priority positions, the longest prefix of the chunk's ready jobs that fits the
+ * lanes left of 64. One inclusive scan over the chunk serves the budget test and the order
+ * inside the pass: a ready lane of size class ts (a job of 4 << ts lanes) scans 1 << 8 ts, one
+ * byte per class (a field reaches 64 at most), and the lanes of a prefix are the dot product of
+ * its four fields with 4, 8, 16, 32. The taken lanes are a prefix of the ready ones, so a taken
+ * lane's own field is its rank + 1 among the chunk's taken jobs of its class, and the scan's
+ * value at the last taken lane is the chunk's class counts: their sum over the pass's chunks so
+ * far (`pc`) is the carry of the ranks and, at the pass's end, the pass word's counts. */
+PL_HD uint32_t pl_take_val(uint32_t ts8) { return 1u << ts8; }                  /* ts8 = 8 ts */
+PL_HD uint32_t pl_take_lanes(uint32_t pre)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_udot4(pre, 0x20100804u, 0u, false);
+#else
+    return 4u * (pre & 255) + 8u * ((pre >> 8) & 255) + 16u * ((pre >> 16) & 255) + 32u * (pre >> 24);
+#endif
+}
+PL_HD uint32_t pl_take_count(uint32_t pc) { return (pc * 0x01010101u) >> 24; }     /* jobs of all classes (at most 16 a pass) */
+/* What a taken lane records for its priority position: the pass | its rank among the pass's jobs
+ * of its class << 10 (at most 16 jobs a pass, at most 768 passes); pre: the scan at the lane. */
+#define PL_REC_NONE 0xffffu
+PL_HD uint32_t pl_take_rec(int npass, uint32_t pre, uint32_t pc, uint32_t ts8)
+{
+    return (uint32_t) npass | ((((pre + pc) >> ts8) & 255u) - 1u) << 10;
+}
+/* The done bits: per plane p (a fourth plane's worth, indices masked) sixteen 16-bit rows, bit u
+ * of row p * 16 + v for unit (u, v), two rows to a 32-bit word, and the same by columns. Jobs
+ * are aligned squares, so all rows of a job take the same bits: a 4x4 or 8x8 job is one 32-bit
+ * OR (one row of the word, or both), a 16x16 job two words, a 32x32 job four. pl_done_bits: the
+ * value for a job of 1 << ts units at `along` (ux0 for the rows) whose first row is `first`
+ * (uy0); pl_done_idx: its first word; the columns swap the two. Both depend on the job alone,
+ * so the pass loop keeps them in registers (pl_done_reg: the two word indices, the size code). */
+PL_HD uint32_t pl_done_bits(int ts, int along, int first)
+{
+    const uint32_t m = (((1u << (1u << ts)) - 1u) << along) & 0xffffu;
+    return ts ? m | m << 16 : m << (16 * (first & 1));
+}
+PL_HD uint32_t pl_done_idx(int p, int first) { return (uint32_t) ((p * 16 + first) >> 1) & 31u; }
+PL_HD int pl_done_words(int ts) { return ts < 2 ? 1 : ts == 2 ? 2 : 4; }
+PL_HD uint32_t pl_done_reg(int p, int ts, int ux0, int uy0) { return pl_done_idx(p, uy0) | pl_done_idx(p, ux0) << 8 | (uint32_t) ts << 16; }
+#define PL_DONE_ROW(r)  ((r) & 31u)
+#define PL_DONE_COL(r)  (((r) >> 8) & 31u)
+#define PL_DONE_TS(r)   ((int) ((r) >> 16))
+/* The pass word from the pass's first job and its class counts */
+PL_HD uint32_t pl_pass_word(uint32_t first, uint32_t pc)
+{
+    return first << 14 | (pc & 255u) << 9 | ((pc >> 8) & 255u) << 5 | ((pc >> 16) & 255u) << 2 | pc >> 24;
+}
+/* A pass's first job from the scan of the passes' job counts: incl = the inclusive scan over a
+ * group of 64 passes at this pass, tot = its own count, carry = the jobs of the groups before. */
+PL_HD uint32_t pl_pass_first(uint32_t carry, uint32_t incl, uint32_t tot) { return carry + incl - tot; }
+/* Position in the SB's job array of the job with record rec and class ts, in a pass with word
+ * pw: the pass's first job, the larger classes' jobs, its rank (sizes descending, take order). */
+PL_HD uint32_t pl_emit_index(uint32_t pw, uint32_t rec, int ts)
+{
+    return (pw >> 14) + (ts < 3 ? pw & 3u : 0u) + (ts < 2 ? (pw >> 2) & 7u : 0u) + (ts < 1 ? (pw >> 5) & 15u : 0u) + (rec >> 10);
+}
+/* A priority position's word in the pass loop: job | 8 ts << 10 | done row of its top run
+ * << 15 | done column of its left run << 21 (the 16-bit rows p * 16 + uy0 - 1 and p * 16 + ux0 - 1;
+ * row / column 0 of the plane where uy0 / ux0 is 0: the mask is empty there). */
+PL_HD uint32_t pl_jw(uint32_t j, uint32_t a)
+{
+    const uint32_t p = a & 3, ux0 = (a >> 12) & 15, uy0 = (a >> 16) & 15;
+    return j | ((a >> 2) & 3) << 13 | (p * 16 + (uy0 ? uy0 - 1 : 0)) << 15 | (p * 16 + (ux0 ? ux0 - 1 : 0)) << 21;
+}
+#define PL_JW_J(w)    ((w) & 1023u)
+#define PL_JW_TS8(w)  (((w) >> 10) & 31u)
+#define PL_JW_TS(w)   ((int) (((w) >> 13) & 3u))
+#define PL_JW_ROW(w)  (((w) >> 15) & 63u)
+#define PL_JW_COL(w)  (((w) >> 21) & 63u)
+
 /* The units of OTHER SBs the job reads, in frame unit coordinates (fx, fy = the job's
  * first unit): left, top and top-left SBs (above-right reads stay inside the block's
  * columns, vp9recon.c:71-121). fn(ux, uy) with ux >= -1 / uy >= -1 unchecked. */

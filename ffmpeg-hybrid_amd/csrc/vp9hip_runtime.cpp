@@ -3549,6 +3549,120 @@ extern "C" int vp9hip_plan_heights_host(int ss_h, int ss_v, int nj, const uint32
     return 0;
 }
 
+// The pass loop and the emit of plan_sb on the host, from the kernel's own routines (the pl_take_*,
+// pl_done_*, pl_pass_* and pl_emit_index of vp9hip_planlogic.h) with a loop over 64 slots in place
+// of the wave's lanes, in the kernel's order: the readiness of every chunk at the top of a pass,
+// then per chunk the packed scan, the take, the records and the done words; after the loop the
+// pass words counted from the records, their scan in groups of 64 passes, and the positions.
+// The masks are pl_deps', the priority order the one-sweep heights' (clamped at 63, then index),
+// which tests/test_plan_heights_host.py shows to be the relaxation's.
+extern "C" int vp9hip_plan_emit_host(int ss_h, int ss_v, int nj, const uint32_t *ja, uint16_t *order, uint32_t *passes,
+                                     int *njobs)
+{
+    if ((ss_h | ss_v | 1) != 1 || nj < 0 || nj > pl_rcap(ss_h, ss_v) || (nj && !ja) || !order || !passes) return -1;
+    const int CW = 16 >> ss_h, CH = 16 >> ss_v, NCH = pl_rcap(ss_h, ss_v) / 64;
+    std::vector<uint16_t> jm(3 * 256, (uint16_t) PL_JM_NONE);
+    for (int j = 0; j < nj; j++) {
+        const uint32_t a = ja[j];
+        const int p = a & 3, n4 = 1 << ((a >> 2) & 3), ux0 = (a >> 12) & 15, uy0 = (a >> 16) & 15;
+        if (p > 2 || (ux0 & (n4 - 1)) || (uy0 & (n4 - 1)) || ux0 >= (p ? CW : 16) || uy0 >= (p ? CH : 16)) return -1;
+        for (int v = uy0; v < uy0 + n4 && v < (p ? CH : 16); v++)
+            for (int u = ux0; u < ux0 + n4 && u < (p ? CW : 16); u++)
+                jm[(size_t) (p * 256 + v * 16 + u)] = (uint16_t) PL_JM_ENT(j, ux0 + n4 - 1 - u, uy0 + n4 - 1 - v);
+    }
+    std::vector<uint32_t> mk((size_t) nj, 0);
+    std::vector<int> h((size_t) nj, 1), ord((size_t) nj);
+    std::vector<std::vector<int>> prod((size_t) nj);
+    for (int j = 0; j < nj; j++) {
+        const uint32_t a = ja[j];
+        const int p = a & 3;
+        mk[(size_t) j] = pl_deps(&jm[(size_t) p * 256], j, (a >> 12) & 15, (a >> 16) & 15, 1 << ((a >> 2) & 3),
+                                 pl_slot_needs((int) ((a >> 8) & 15)), (int) ((a >> 30) & 1), p ? CW : 16, p ? CH : 16,
+                                 [&](int d) { prod[(size_t) j].push_back(d); });
+    }
+    for (int j = nj - 1; j >= 0; j--)
+        for (int d : prod[(size_t) j]) h[(size_t) d] = std::max(h[(size_t) d], h[(size_t) j] + 1);
+    for (int j = 0; j < nj; j++) ord[(size_t) j] = j;
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return std::min(h[(size_t) x], 63) > std::min(h[(size_t) y], 63); });
+    // the lanes' registers: slot c * 64 + lane
+    const size_t NS = (size_t) NCH * 64;
+    std::vector<uint32_t> jw(NS, 0), mkr(NS, 0), rc(NS, PL_REC_NONE), dr(NS, 0), dc(NS, 0), dx(NS, 0);
+    std::vector<uint8_t> pend(NS, 0);
+    for (int pos = 0; pos < nj; pos++) {
+        const int j = ord[(size_t) pos];
+        const uint32_t a = ja[j];
+        const int p = a & 3, ts = (a >> 2) & 3, ux0 = (a >> 12) & 15, uy0 = (a >> 16) & 15;
+        jw[(size_t) pos] = pl_jw((uint32_t) j, a);
+        dr[(size_t) pos] = pl_done_bits(ts, ux0, uy0);
+        dc[(size_t) pos] = pl_done_bits(ts, uy0, ux0);
+        dx[(size_t) pos] = pl_done_reg(p, ts, ux0, uy0);
+        mkr[(size_t) pos] = mk[(size_t) j];
+        pend[(size_t) pos] = 1;
+    }
+    uint32_t drow[32] = { 0 }, dcol[32] = { 0 };
+    auto half = [](const uint32_t *w, uint32_t i) { return (w[i >> 1] >> (16 * (i & 1))) & 0xffffu; };
+    int done = 0, npass = 0;
+    std::vector<uint8_t> rdy(NS);
+    while (done < nj) {
+        for (size_t i = 0; i < NS; i++) {
+            const uint32_t have = half(drow, PL_JW_ROW(jw[i])) | half(dcol, PL_JW_COL(jw[i])) << 16;
+            rdy[i] = pend[i] && (have & mkr[i]) == mkr[i];
+        }
+        int budget = 64;
+        uint32_t pc = 0;
+        for (int c = 0; c < NCH; c++) {
+            if (budget < 4) break;
+            uint32_t pre[64], run = 0;
+            int last = -1;
+            for (int l = 0; l < 64; l++) {
+                const size_t i = (size_t) c * 64 + l;
+                run += rdy[i] ? pl_take_val(PL_JW_TS8(jw[i])) : 0u;
+                pre[l] = run;
+                if (rdy[i] && pl_take_lanes(run) <= (uint32_t) budget) last = l;
+            }
+            if (last < 0) continue;
+            for (int l = 0; l < 64; l++) {
+                const size_t i = (size_t) c * 64 + l;
+                if (!(rdy[i] && pl_take_lanes(pre[l]) <= (uint32_t) budget)) continue;
+                const uint32_t w = jw[i];
+                pend[i] = 0;
+                rc[i] = pl_take_rec(npass, pre[l], pc, PL_JW_TS8(w));
+                for (int k = 0; k < pl_done_words(PL_DONE_TS(dx[i])); k++) {
+                    drow[(PL_DONE_ROW(dx[i]) + (uint32_t) k) & 31] |= dr[i];
+                    dcol[(PL_DONE_COL(dx[i]) + (uint32_t) k) & 31] |= dc[i];
+                }
+            }
+            pc += pre[last];
+            budget -= (int) pl_take_lanes(pre[last]);
+        }
+        if (pc == 0) return -2;
+        done += (int) pl_take_count(pc);
+        npass++;
+    }
+    std::vector<uint32_t> pw((size_t) npass + 64, 0);
+    for (size_t i = 0; i < NS; i++)
+        if (rc[i] != PL_REC_NONE) pw[rc[i] & 1023u] += pl_take_val(PL_JW_TS8(jw[i]));
+    uint32_t carry = 0;
+    for (int g = 0; g < npass; g += 64) {
+        uint32_t incl = 0;
+        for (int l = 0; l < 64; l++) {
+            const int P = g + l;
+            const uint32_t cls = P < npass ? pw[(size_t) P] : 0u, tot = pl_take_count(cls);
+            incl += tot;
+            if (P < npass) passes[P] = pw[(size_t) P] = pl_pass_word(pl_pass_first(carry, incl, tot), cls);
+        }
+        carry += incl;
+    }
+    for (size_t i = 0; i < NS; i++)
+        if (rc[i] != PL_REC_NONE) {
+            const uint32_t at = pl_emit_index(pw[rc[i] & 1023u], rc[i], PL_JW_TS(jw[i]));
+            if (at >= (uint32_t) nj) return -2;
+            order[at] = (uint16_t) PL_JW_J(jw[i]);
+        }
+    if (njobs) *njobs = done;
+    return npass;
+}
+
 // The current slot's device-planned intra schedule, copied to the host (include/vp9hip.h).
 extern "C" int vp9hip_test_plan_records(vp9hip_ctx *c, int cap_slots, int *jcap, uint32_t *sbs, uint32_t *wgs,
                                         uint32_t *passes, uint32_t *jobs_a)

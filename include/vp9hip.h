@@ -157,6 +157,14 @@ int  vp9hip_plan_sched_host(int ss_h, int ss_v, int nj, const uint32_t *ja, uint
  * longest path to a sink, not clamped. Returns 0, -1 for bad arguments, -2 for overlapping jobs. */
 int  vp9hip_plan_heights_host(int ss_h, int ss_v, int nj, const uint32_t *ja, uint32_t *heights);
 
+/* Test only, no device: the same schedule from the device planner's own pass loop and emit (the
+ * routines k_pjplan runs: the packed take scan, the ranks, the packed done words, the pass-word
+ * scan and the positions; a loop over 64 slots in place of the wave's lanes). order and passes as
+ * vp9hip_plan_sched_host's, *njobs (may be NULL) the jobs placed. Returns the number of passes,
+ * -1 for bad arguments, -2 if a pass can take no job. */
+int  vp9hip_plan_emit_host(int ss_h, int ss_v, int nj, const uint32_t *ja, uint16_t *order, uint32_t *passes,
+                           int *njobs);
+
 /* Allocate `nbufs` device frame buffers of w x h (padded to 64 internally). */
 int  vp9hip_configure(vp9hip_ctx *ctx, int width, int height, int bpp, int ss_h, int ss_v,
                       int nbufs);
