@@ -316,6 +316,15 @@ def lib():
     L.vp9hip_decoder_frame_motion.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(ctypes.c_void_p),
                                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int),
                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)]
+    # residual export
+    i64p3, vp3 = ctypes.POINTER(ctypes.c_int64 * 3), ctypes.POINTER(ctypes.c_void_p * 3)
+    L.vp9hip_frame_residual.argtypes = [vp, ctypes.c_int, vp3, i64p3, ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
+    L.vp9hip_download_residual.argtypes = [vp, ctypes.c_int, vp3, ctypes.POINTER(ctypes.c_ssize_t * 3)]
+    L.vp9hip_residual_host.argtypes = [ctypes.POINTER(FramePacket), vp3, ctypes.POINTER(ctypes.c_ssize_t * 3),
+                                       ctypes.POINTER(ctypes.c_int * 3)]
+    L.vp9hip_residual_relaunch.argtypes = [vp, ctypes.c_void_p]
+    L.vp9hip_decoder_frame_residual.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), vp3, i64p3]
     _lib_handle = L
     return L
 
@@ -773,6 +782,57 @@ def _motion_views(mv, info, gw, gh, pitch, device):
     return torch.as_tensor(_Mv(), device=device or "cuda"), torch.as_tensor(_Info(), device=device or "cuda")
 
 
+EXPORT_RESIDUAL = 2            # VP9HIP_EXPORT_RESIDUAL
+
+
+def residual_shapes(width, height, ss_h=1, ss_v=1):
+    """(rows, columns) of the three planes of a residual field's coded area (include/vp9hip.h):
+    Y of 8 rows8 x 8 cols8, U and V of that shifted by the subsampling."""
+    cw, ch = 8 * ((width + 7) >> 3), 8 * ((height + 7) >> 3)
+    return [(ch, cw), (ch >> ss_v, cw >> ss_h), (ch >> ss_v, cw >> ss_h)]
+
+
+def _plane_ptrs(planes):
+    return ((ctypes.c_void_p * 3)(*[a.ctypes.data for a in planes]),
+            (ctypes.c_ssize_t * 3)(*[a.strides[0] for a in planes]))
+
+
+def residual_host(frame):
+    """The residual field of one packet (SynthFrame, a parsed packet or a FramePacket) on the host,
+    vp9hip_residual_host, the C++ statement of the definition in include/vp9hip.h: three int16
+    arrays of the coded area (residual_shapes), clip(r, -m, m) where a coded tx block lies, 0
+    elsewhere."""
+    pkt = frame.pkt if hasattr(frame, "pkt") else frame
+    if pkt.width <= 0 or pkt.height <= 0:
+        raise Vp9HipError("vp9hip_residual_host", EINVAL)
+    planes = [np.full(s, 0x5a5a, np.int16) for s in residual_shapes(pkt.width, pkt.height, pkt.ss_h, pkt.ss_v)]
+    ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in planes])
+    pitch = (ctypes.c_ssize_t * 3)(*[a.shape[1] for a in planes])
+    rows = (ctypes.c_int * 3)(*[a.shape[0] for a in planes])
+    _check("vp9hip_residual_host", lib().vp9hip_residual_host(ctypes.byref(pkt), ctypes.byref(ptrs), ctypes.byref(pitch),
+                                                              ctypes.byref(rows)))
+    return planes
+
+
+def _residual_views(ptrs, pitch, width, height, ss_h, ss_v, device):
+    """Zero-copy torch int16 views of a field's three device planes, of the visible size, strided
+    over the planes' pitch."""
+    if not _torch_first:
+        raise Vp9HipUnavailable("residual: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+    import torch
+    out = []
+    for p in range(3):
+        pw = width if p == 0 else (width + ss_h) >> ss_h
+        ph = height if p == 0 else (height + ss_v) >> ss_v
+
+        class _View:
+            __cuda_array_interface__ = {"shape": (ph, pw), "typestr": "<i2", "data": (ptrs[p], False),
+                                        "strides": (pitch[p] * 2, 2), "version": 2}
+        out.append(torch.as_tensor(_View(), device=device or "cuda"))
+    return out
+
+
 def alloc_planes(width, height, bpp, ss_h=1, ss_v=1, pad=64):
     """Host planes padded to 64 luma pixels (the layout the oracle expects)."""
     dt = np.uint8 if bpp == 8 else np.uint16
@@ -849,10 +909,38 @@ class Device:
         _check("vp9hip_configure", lib().vp9hip_configure(self._c, width, height, bpp, ss_h, ss_v, nbufs))
         self.w, self.h, self.bpp, self.ss_h, self.ss_v = width, height, bpp, ss_h, ss_v
 
-    def set_export(self, motion=True):
-        """Motion export on / off for the next configure (vp9hip_set_export): every batch then
-        leaves each frame's motion field beside its pixels (motion / download_motion)."""
-        _check("vp9hip_set_export", lib().vp9hip_set_export(self._c, EXPORT_MOTION if motion else 0))
+    def set_export(self, motion=True, residual=False):
+        """Motion and / or residual export on / off for the next configure (vp9hip_set_export):
+        every batch then leaves each frame's motion field (motion / download_motion) and / or
+        residual field (residual / download_residual) beside its pixels."""
+        _check("vp9hip_set_export", lib().vp9hip_set_export(self._c, (EXPORT_MOTION if motion else 0) |
+                                                            (EXPORT_RESIDUAL if residual else 0)))
+
+    def frame_residual(self, buf):
+        """The residual field of buffer `buf` in place (vp9hip_frame_residual): ([ptr] * 3,
+        [pitch in int16 elements] * 3, (width, height) of the frame, hipStream_t handle)."""
+        ptrs, pitch = (ctypes.c_void_p * 3)(), (ctypes.c_int64 * 3)()
+        w, h, st = ctypes.c_int(), ctypes.c_int(), ctypes.c_void_p()
+        _check("vp9hip_frame_residual", lib().vp9hip_frame_residual(self._c, buf, ctypes.byref(ptrs), ctypes.byref(pitch),
+                                                                    ctypes.byref(w), ctypes.byref(h), ctypes.byref(st)))
+        return list(ptrs), list(pitch), (w.value, h.value), st.value
+
+    def residual(self, buf, device=None):
+        """Zero-copy torch int16 views (Y, U, V) of buffer `buf`'s residual field, of the frame's
+        visible size, strided over the planes' pitch. Call sync() first (or order consumers
+        after the slot that wrote the frame), as for frame_tensors."""
+        ptrs, pitch, (w, h), _ = self.frame_residual(buf)
+        return _residual_views(ptrs, pitch, w, h, self.ss_h, self.ss_v, device)
+
+    def download_residual(self, buf):
+        """Buffer `buf`'s residual field as three numpy int16 arrays of the coded area
+        (residual_shapes; vp9hip_download_residual, which waits for the batches writing the
+        buffer)."""
+        _, _, (w, h), _ = self.frame_residual(buf)
+        planes = [np.empty(s, np.int16) for s in residual_shapes(w, h, self.ss_h, self.ss_v)]
+        ptrs, ls = _plane_ptrs(planes)
+        _check("vp9hip_download_residual", lib().vp9hip_download_residual(self._c, buf, ctypes.byref(ptrs), ctypes.byref(ls)))
+        return planes
 
     def frame_motion(self, buf):
         """The field of buffer `buf` in place (vp9hip_frame_motion): (mv pointer, info pointer,
@@ -1188,7 +1276,7 @@ class Decoder:
     """
 
     def __init__(self, device=0, max_batch=16, extra_bufs=4, max_width=0, max_height=0, parse_threads=None,
-                 export_motion=False):
+                 export_motion=False, export_residual=False):
         self.params = DecoderParams()
         lib().vp9hip_decoder_defaults(ctypes.byref(self.params))
         self.params.device, self.params.max_batch, self.params.extra_bufs = device, max_batch, extra_bufs
@@ -1198,8 +1286,10 @@ class Decoder:
         self._d = ctypes.c_void_p()
         _check("vp9hip_decoder_open", lib().vp9hip_decoder_open(ctypes.byref(self.params), ctypes.byref(self._d)))
         self.eof = False
-        if export_motion:
-            _check("vp9hip_decoder_set_export", lib().vp9hip_decoder_set_export(self._d, EXPORT_MOTION))
+        if export_motion or export_residual:
+            _check("vp9hip_decoder_set_export",
+                   lib().vp9hip_decoder_set_export(self._d, (EXPORT_MOTION if export_motion else 0) |
+                                                   (EXPORT_RESIDUAL if export_residual else 0)))
 
     def close(self):
         if self._d:
@@ -1262,6 +1352,23 @@ class Decoder:
         m, i = np.empty((gh.value, gw.value, 2, 2), np.int16), np.empty((gh.value, gw.value, 4), np.uint8)
         _check("vp9hip_download_motion", lib().vp9hip_download_motion(self.context(), info.buf, m.ctypes.data, i.ctypes.data))
         return m, i
+
+    def residual(self, info, download=False, device=None):
+        """The residual field of a frame of receive_frame(download=False), valid until
+        release(info.buf) (vp9hip_decoder_frame_residual; needs export_residual=True): zero-copy
+        torch int16 views (Y, U, V) of the visible size as Device.residual returns them, or numpy
+        copies of the coded area with download=True. A show_existing_frame output has the field
+        of the frame it shows."""
+        ptrs, pitch = (ctypes.c_void_p * 3)(), (ctypes.c_int64 * 3)()
+        _check("vp9hip_decoder_frame_residual",
+               lib().vp9hip_decoder_frame_residual(self._d, ctypes.byref(info), ctypes.byref(ptrs), ctypes.byref(pitch)))
+        if not download:
+            return _residual_views(list(ptrs), list(pitch), info.width, info.height, info.ss_h, info.ss_v, device)
+        planes = [np.empty(s, np.int16) for s in residual_shapes(info.width, info.height, info.ss_h, info.ss_v)]
+        hp, ls = _plane_ptrs(planes)
+        _check("vp9hip_download_residual",
+               lib().vp9hip_download_residual(self.context(), info.buf, ctypes.byref(hp), ctypes.byref(ls)))
+        return planes
 
     def convert(self, infos, fmt, out=None, resize=None, filter="box", src_rects=None, dst_rects=None, fill=None):
         """Convert the frames of receive_frame(download=False) (their DecodedFrameInfos, all of

@@ -455,6 +455,14 @@ extern "C" int vp9hip_decoder_frame_motion(vp9hip_decoder *d, const vp9hip_decod
     return vp9hip_frame_motion(d->ctx, f->buf, mv, info, gw, gh, pitch_cells, nullptr);
 }
 
+extern "C" int vp9hip_decoder_frame_residual(vp9hip_decoder *d, const vp9hip_decoded_frame *f, void *planes[3],
+                                             int64_t pitch[3])
+{
+    if (!d || !f || !d->configured || !(d->export_flags & VP9HIP_EXPORT_RESIDUAL)) return VP9HIP_EINVAL;
+    if (f->buf < 0 || f->buf >= d->nbufs || d->pins[f->buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+    return vp9hip_frame_residual(d->ctx, f->buf, planes, pitch, nullptr, nullptr, nullptr);
+}
+
 // avcodec_flush_buffers (vp9.c:1865-1883): drop the decoder delay and the reference
 // state; frames already handed out stay valid until released.
 extern "C" int vp9hip_decoder_flush(vp9hip_decoder *d)

@@ -18,7 +18,7 @@
 #if defined(__HIPCC__)
 #define R4_HD __host__ __device__ __forceinline__
 #else
-#define R4_HD static inline
+#define R4_HD inline      /* a host C++ compiler: the policies' members add their own `static` */
 #endif
 
 /* Transform arithmetic policy. 8-bit: uint32 bit patterns (defined wrap-around, identical to

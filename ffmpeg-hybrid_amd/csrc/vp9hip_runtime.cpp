@@ -42,6 +42,7 @@
 #include "vp9hip_plan.h"
 #include "vp9hip_convert.h"
 #include "vp9hip_motion.h"
+#include "vp9hip_residual.h"
 #include "vp9hip_residn.h"
 
 extern "C" {
@@ -217,6 +218,13 @@ struct Staged {
     size_t o_mot = 0;
     std::vector<int> mot_buf;                        // per frame: its output buffer
     std::vector<std::pair<int, int>> mot_grid;       // per frame: GW, GH
+    // residual export: every run launches k_residual over the batch's SB slots, from the
+    // ResidFrame records uploaded with the batch (o_res) and the planner's tx records
+    bool residual = false;
+    size_t o_res = 0;
+    int res_max_sb = 0;
+    std::vector<int> res_buf;                        // per frame: its output buffer
+    std::vector<std::pair<int, int>> res_size;       // per frame: visible width, height
 };
 
 } // namespace
@@ -322,6 +330,11 @@ struct vp9hip_ctx {
     std::vector<uint8_t *> mot;
     std::vector<std::pair<int, int>> mot_gwh;
     int mot_pitch = 0, mot_rows = 0;
+    // residual export: per frame buffer one allocation with three int16 planes of the pixel
+    // planes' padded geometry (pitch[] elements a row, plane_off[] / bypp elements apart);
+    // res_wh: the visible size of the frame whose field a buffer holds, { 0, 0 } when none
+    std::vector<uint8_t *> res;
+    std::vector<std::pair<int, int>> res_wh;
     uint32_t *ptab = nullptr;           // intra predictor formula table (device)
     uint8_t *nz = nullptr;              // nonzero bounding boxes per (tcode, txtp, eob) (device, planner)
     bool host_plan = false;             // VP9HIP_HOST_PLAN=1: plan batches on host threads (A/B, tests)
@@ -510,6 +523,9 @@ static void free_bufs(vp9hip_ctx *c)
     for (auto *b : c->mot) hipFree(b);
     c->mot.clear();
     c->mot_gwh.clear();
+    for (auto *b : c->res) hipFree(b);
+    c->res.clear();
+    c->res_wh.clear();
 }
 
 // Forget the staged batches of every slot (their FrameDescs, graphs and launch lists name
@@ -686,6 +702,14 @@ extern "C" int vp9hip_configure(vp9hip_ctx *c, int width, int height, int bpp, i
             if (hipMalloc(&b, (size_t) c->mot_pitch * c->mot_rows * 12) != hipSuccess) { free_bufs(c); return VP9HIP_ENOMEM; }
             c->mot.push_back(b);
             c->mot_gwh.push_back({ 0, 0 });
+        }
+    }
+    if (c->export_flags & VP9HIP_EXPORT_RESIDUAL) {
+        for (int i = 0; i < nbufs; i++) {
+            uint8_t *b = nullptr;
+            if (hipMalloc(&b, c->buf_bytes / c->bypp * 2) != hipSuccess) { free_bufs(c); return VP9HIP_ENOMEM; }
+            c->res.push_back(b);
+            c->res_wh.push_back({ 0, 0 });
         }
     }
     int r = upload_ptab(c);
@@ -1122,6 +1146,7 @@ struct DevIn {
     bool fuse, lfr_any;
     const int *out_bufs;
     bool motion;                 // the batch exports its frames' motion fields
+    bool residual;               // the batch exports its frames' residual fields
 };
 
 // row-LF counter blocks of a staged batch, zeroed; word 3 of each block is the spin bound of
@@ -1456,6 +1481,8 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
     s.o_ctr = o; o = al(o + (size_t) s.n_ctr * 4);
     s.motion = in.motion;
     s.o_mot = o; o = al(o + (s.motion ? (size_t) n * sizeof(MotionFrame) : 0));
+    s.residual = in.residual;
+    s.o_res = o; o = al(o + (s.residual ? (size_t) n * sizeof(ResidFrame) : 0));
     s.o_blocks = o; o = al(o + nb * sizeof(vp9h_block));
     s.o_eobs = o; o = al(o + ne * 2);
     s.o_coefs = o; o = al(o + nc * in.csz + VP9HIP_COEF_PAD);
@@ -1553,6 +1580,27 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
             mf[i].info = (uint64_t) (mp + (size_t) c->mot_pitch * c->mot_rows * 8);
             mf[i].pitch = (uint32_t) c->mot_pitch;
             mf[i].pad = 0;
+        }
+    }
+    s.res_max_sb = 0;
+    if (s.residual) {
+        ResidFrame *rf = (ResidFrame *) (img + s.o_res);
+        for (int i = 0; i < n; i++) {
+            uint8_t *rp = c->res[in.out_bufs[i]];
+            // as for motion: of several frames writing one buffer only the last exports
+            bool last = true;
+            for (int j = i + 1; j < n && last; j++) last = in.out_bufs[j] != in.out_bufs[i];
+            memset(&rf[i], 0, sizeof(rf[i]));
+            for (int p = 0; p < 3; p++) rf[i].plane[p] = (uint64_t) (rp + c->plane_off[p] / c->bypp * 2);
+            rf[i].pitch[0] = (uint32_t) c->pitch[0]; rf[i].pitch[1] = (uint32_t) c->pitch[1];
+            rf[i].slot0 = pf[i].slot0;
+            // a frame larger than the context's buffers exports nothing (staging refuses it anyway)
+            const bool fits = fbs[i].sb_cols <= c->sb_cols && fbs[i].sb_rows <= c->sb_rows;
+            rf[i].nsb = last && fits ? (uint32_t) (fbs[i].sb_cols * fbs[i].sb_rows) : 0;
+            rf[i].sb_cols = (uint32_t) fbs[i].sb_cols; rf[i].sb_rows = (uint32_t) fbs[i].sb_rows;
+            rf[i].ss_h = (uint32_t) c->ss_h; rf[i].ss_v = (uint32_t) c->ss_v;
+            rf[i].maxv = (1u << c->bpp) - 1;
+            s.res_max_sb = std::max(s.res_max_sb, (int) rf[i].nsb);
         }
     }
     {   // packets: blocks, eobs, coefficients (frames copied in parallel)
@@ -2133,6 +2181,7 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
     }
     s.dev = false;
     s.motion = false;
+    s.residual = false;
     if (!c->host_plan) {
         DevIn in;
         in.pkts = pkts; in.n = n; in.G = G; in.maxpos = maxpos; in.NP = NP; in.csz = csz;
@@ -2142,6 +2191,8 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
         in.motion = (c->export_flags & VP9HIP_EXPORT_MOTION) && !tiled;
         // the buffers' fields: the frames' grids once the batch ran; none for a sharded batch
         for (int i = 0; i < n && !c->mot_gwh.empty(); i++) c->mot_gwh[out_bufs[i]] = { 0, 0 };
+        in.residual = (c->export_flags & VP9HIP_EXPORT_RESIDUAL) && !tiled;
+        for (int i = 0; i < n && !c->res_wh.empty(); i++) c->res_wh[out_bufs[i]] = { 0, 0 };
         const int r = stage_dev(c, in);
         if (r) return r;
         s.mot_buf.clear(); s.mot_grid.clear();
@@ -2149,6 +2200,12 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
             s.mot_buf.push_back(out_bufs[i]);
             s.mot_grid.push_back({ 2 * fbs[i].cols, 2 * fbs[i].rows });
             c->mot_gwh[out_bufs[i]] = s.mot_grid.back();
+        }
+        s.res_buf.clear(); s.res_size.clear();
+        for (int i = 0; i < n && in.residual; i++) {
+            s.res_buf.push_back(out_bufs[i]);
+            s.res_size.push_back({ pkts[i].width, pkts[i].height });
+            c->res_wh[out_bufs[i]] = s.res_size.back();
         }
         STAGE_T(1);
         if (stage_trace) fprintf(stderr, "vp9hip stage (device plan): %d frames: setup %.1f upload %.1f ms\n", n, st_ms[0], st_ms[1]);
@@ -2510,6 +2567,18 @@ static bool same_launches(const std::vector<Launch> &a, const std::vector<Launch
     return true;
 }
 
+static hipError_t launch_residual(vp9hip_ctx *c, const Staged &s, hipStream_t st)
+{
+    ResidArgs ra;
+    ra.frames = (const ResidFrame *) (s.arena + s.o_res);
+    ra.txrec = (const TxRec *) (s.arena + s.o_txrec);
+    ra.sb_tn = (const uint32_t *) (s.arena + s.o_sbtn);
+    ra.sb_coef0 = (const uint32_t *) (s.arena + s.o_sbcoef0);
+    ra.coefs = s.arena + s.o_coefs;
+    ra.total_coefs = s.ncoef; ra.jcap = (uint32_t) s.jcap; ra.nslots = s.nslots;
+    return vp9hip_residual_launch(ra, s.nframes, s.res_max_sb, c->hb ? 1 : 0, st);
+}
+
 // Run the staged batch. Without per-launch timing the ~300 launches of a 4K batch are
 // captured once into a HIP graph (both frame-group streams) and replayed.
 extern "C" int vp9hip_run_batch(vp9hip_ctx *c)
@@ -2521,6 +2590,7 @@ extern "C" int vp9hip_run_batch(vp9hip_ctx *c)
         const int r = plan_dev(c);
         if (r) {                          // nothing was launched: no field of this batch is valid
             for (size_t i = 0; s.motion && i < s.mot_buf.size(); i++) c->mot_gwh[s.mot_buf[i]] = { 0, 0 };
+            for (size_t i = 0; s.residual && i < s.res_buf.size(); i++) c->res_wh[s.res_buf[i]] = { 0, 0 };
             return r;
         }
         if (c->plan_only) return 0;       // diagnostics: the planner alone
@@ -2538,6 +2608,14 @@ extern "C" int vp9hip_run_batch(vp9hip_ctx *c)
                                     (const vp9h_block *) (s.arena + s.o_blocks), 0, c->st));
         // (again) the fields of this run: a refused earlier run or a fill in between cleared them
         for (size_t i = 0; i < s.mot_buf.size(); i++) c->mot_gwh[s.mot_buf[i]] = s.mot_grid[i];
+    }
+    // residual export: one launch over the batch's SB slots, after the planner's records (the
+    // waits above, or plan_dev's host synchronise) and outside the graph like k_motion. It reads
+    // what no later kernel writes (the tx records, the slots' counts and coefficient bases, the
+    // coefficients), so a re-run that skips the planner exports the same bytes.
+    if (s.dev && s.residual) {
+        HIPCHK(launch_residual(c, s, c->st));
+        for (size_t i = 0; i < s.res_buf.size(); i++) c->res_wh[s.res_buf[i]] = s.res_size[i];
     }
     // this slot's last work on the main stream: its next planning waits for it
     if (!s.done_ev) HIPCHK(hipEventCreateWithFlags(&s.done_ev, hipEventDisableTiming));
@@ -2930,6 +3008,7 @@ extern "C" int vp9hip_upload_frame(vp9hip_ctx *c, int buf, const uint8_t *const 
     hipSetDevice(c->dev);
     HIPCHK(sync_all(c));
     if (!c->mot_gwh.empty()) c->mot_gwh[buf] = { 0, 0 };   // pixels from elsewhere: no field
+    if (!c->res_wh.empty()) c->res_wh[buf] = { 0, 0 };
     for (int p = 0; p < 3; p++) {
         const int bw = c->buf_wh[buf].first, bh = c->buf_wh[buf].second;
         int pw = p ? (bw + c->ss_h) >> c->ss_h : bw, ph = p ? (bh + c->ss_v) >> c->ss_v : bh;
@@ -2963,7 +3042,7 @@ extern "C" int vp9hip_frame_device(vp9hip_ctx *c, int buf, void *planes[3], ptrd
 // ---- motion export (include/vp9hip.h "motion export"; k_motion in vp9hip_motion.hip) ----
 extern "C" int vp9hip_set_export(vp9hip_ctx *c, int flags)
 {
-    if (!c || (flags & ~VP9HIP_EXPORT_MOTION)) return VP9HIP_EINVAL;
+    if (!c || (flags & ~(VP9HIP_EXPORT_MOTION | VP9HIP_EXPORT_RESIDUAL))) return VP9HIP_EINVAL;
     if (flags && c->host_plan) return VP9HIP_ENOSYS;      // host-planned batches do not upload the blocks
     if (!c->bufs.empty() && flags != c->export_flags) return VP9HIP_EINVAL;
     c->export_flags = flags;
@@ -2997,6 +3076,51 @@ extern "C" int vp9hip_download_motion(vp9hip_ctx *c, int buf, int16_t *mv, uint8
     if (info) HIPCHK(hipMemcpy2DAsync(info, (size_t) gw * 4, infod, (size_t) pitch * 4, (size_t) gw * 4, gh, hipMemcpyDeviceToHost, c->dst_dl));
     HIPCHK(hipStreamSynchronize(c->dst_dl));
     return 0;
+}
+
+// ---- residual export (include/vp9hip.h "residual export"; k_residual in vp9hip_residual.hip) ----
+extern "C" int vp9hip_frame_residual(vp9hip_ctx *c, int buf, void *planes[3], int64_t pitch[3], int *width, int *height,
+                                     void **stream)
+{
+    if (!c || c->res.empty() || buf < 0 || buf >= (int) c->res.size()) return VP9HIP_EINVAL;
+    if (!c->res_wh[buf].first) return VP9HIP_EAGAIN;
+    for (int p = 0; p < 3; p++) {
+        if (planes) planes[p] = c->res[buf] + c->plane_off[p] / c->bypp * 2;
+        if (pitch) pitch[p] = c->pitch[p ? 1 : 0];
+    }
+    if (width) *width = c->res_wh[buf].first;
+    if (height) *height = c->res_wh[buf].second;
+    if (stream) *stream = (void *) c->st;
+    return 0;
+}
+
+extern "C" int vp9hip_download_residual(vp9hip_ctx *c, int buf, int16_t *const planes[3], const ptrdiff_t linesize[3])
+{
+    void *dp[3];
+    int64_t pitch[3];
+    int w = 0, h = 0;
+    if (const int r = vp9hip_frame_residual(c, buf, dp, pitch, &w, &h, nullptr)) return r;
+    if (!planes || !linesize) return VP9HIP_EINVAL;
+    hipSetDevice(c->dev);
+    if (const int r = wait_writers(c, buf)) return r;
+    if (!c->dst_dl) HIPCHK(hipStreamCreateWithFlags(&c->dst_dl, hipStreamNonBlocking));
+    for (int p = 0; p < 3; p++) {
+        if (!planes[p]) continue;
+        const size_t cw = (size_t) (8 * ((w + 7) >> 3) >> (p ? c->ss_h : 0)), ch = (size_t) (8 * ((h + 7) >> 3) >> (p ? c->ss_v : 0));
+        if (linesize[p] < (ptrdiff_t) (cw * 2)) return VP9HIP_EINVAL;
+        HIPCHK(hipMemcpy2DAsync(planes[p], (size_t) linesize[p], dp[p], (size_t) pitch[p] * 2, cw * 2, ch, hipMemcpyDeviceToHost, c->dst_dl));
+    }
+    HIPCHK(hipStreamSynchronize(c->dst_dl));
+    return 0;
+}
+
+// Diagnostics (tools/residual_bench.py): k_residual once more over the current slot's batch, which
+// has run (its records are resident), on `stream`; the caller orders it against the batch.
+extern "C" int vp9hip_residual_relaunch(vp9hip_ctx *c, void *stream)
+{
+    if (!c || !c->stg.ready || !c->stg.dev || !c->stg.residual || !c->stg.planned || !c->stg.arena) return VP9HIP_EINVAL;
+    hipSetDevice(c->dev);
+    return launch_residual(c, c->stg, (hipStream_t) stream) == hipSuccess ? 0 : VP9HIP_EEXTERNAL;
 }
 
 // Diagnostics (tools/motion_bench.py): one k_motion launch over caller-built MotionFrame records
@@ -3253,6 +3377,7 @@ extern "C" int vp9hip_fill_buffers(vp9hip_ctx *c, int buf0, int count, int value
     HIPCHK(sync_all(c));                 // neither slot's work may still read the buffers
     for (int i = buf0; i < buf0 + count; i++) HIPCHK(hipMemsetAsync(c->bufs[i], value & 255, c->buf_bytes, c->st));
     for (int i = buf0; i < buf0 + count && !c->mot_gwh.empty(); i++) c->mot_gwh[i] = { 0, 0 };
+    for (int i = buf0; i < buf0 + count && !c->res_wh.empty(); i++) c->res_wh[i] = { 0, 0 };
     // every slot's later work (whichever stream it runs on) follows the fill
     if (!c->fill_ev) HIPCHK(hipEventCreateWithFlags(&c->fill_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(c->fill_ev, c->st));

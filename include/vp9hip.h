@@ -46,7 +46,9 @@ extern "C" {
  * vp9hip_decoder_frame_motion) likewise: new symbols only. The bicubic filter
  * (VP9HIP_FILTER_BICUBIC, vp9hip_convert_frames_bicubic, vp9hip_decoder_convert_bicubic,
  * vp9hip_bicubic_weights) likewise: a new macro and new symbols, the filter enum and
- * vp9hip_resample unchanged. */
+ * vp9hip_resample unchanged. The residual export (VP9HIP_EXPORT_RESIDUAL, vp9hip_frame_residual,
+ * vp9hip_download_residual, vp9hip_residual_host, vp9hip_decoder_frame_residual) likewise: new
+ * symbols only. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -516,7 +518,8 @@ int  vp9hip_bicubic_weights(int n_src, int n_out, int o, int *first, int32_t *we
  * under reference scaling. Not exported: transform sizes, the interpolation filter, chroma
  * vectors. */
 #define VP9HIP_EXPORT_MOTION 1
-/* Export flags (0 or VP9HIP_EXPORT_MOTION) of the next vp9hip_configure, which then allocates
+/* Export flags (0, VP9HIP_EXPORT_MOTION, and / or VP9HIP_EXPORT_RESIDUAL, "residual export"
+ * below) of the next vp9hip_configure, which then allocates
  * two side planes per frame buffer, freed with the buffers: mv (8 bytes per cell) and info (4
  * bytes per cell), of the fixed cell pitch 2 ((cfg_width + 7) >> 3) and 2 ((cfg_height + 7) >> 3)
  * rows; a smaller frame in a larger context uses the top-left of its planes. VP9HIP_EINVAL:
@@ -551,6 +554,69 @@ int  vp9hip_download_motion(vp9hip_ctx *ctx, int buf, int16_t *mv, uint8_t *info
  * (a cell two blocks cover counts twice), or VP9HIP_EINVAL for a NULL argument or a packet
  * without a size. */
 int  vp9hip_motion_host(const vp9h_frame *pkt, int16_t *mv, uint8_t *info);
+
+/* ---- residual export: what the transforms add to the prediction, as device tensors ----
+ * The third input of compressed-domain models besides I-frame pixels and motion vectors. The
+ * decode computes the residual of every coded transform block anyway (keyframes hold it in a
+ * scratch for a moment, inter frames add it into the prediction in place); with
+ * VP9HIP_EXPORT_RESIDUAL one more kernel (k_residual) per batch puts it where a consumer can
+ * read it: three int16 planes per frame in picture geometry. Off by default; with it off nothing
+ * is allocated and nothing is launched.
+ *
+ * Definition, in integers. For a frame of visible size w x h at bpp bits let m = 2^bpp - 1,
+ * cols8 = (w + 7) >> 3 and rows8 = (h + 7) >> 3. The residual field is three int16 planes: Y of
+ * 8 cols8 x 8 rows8 samples, U and V of (8 cols8 >> ss_h) x (8 rows8 >> ss_v): the coded area.
+ * Take a tx block of the packet (the enumeration of vp9h_frame.eobs) with eob > 0, of plane p,
+ * top-left (x0, y0) in that plane, size N and type (tx, txtp): the WHT in lossless frames; for
+ * luma of an intra block below 32x32 the type of vp9hip_intra_txfm_type(mode); DCT_DCT for
+ * everything else. Let r[y][x] be what itxfm_add adds before its clip
+ * (vp9dsp_template.c:1139-1180: (out + (1 << (bits - 1))) >> bits, the DC-only shortcut
+ * included). Then
+ *   res[p][y0 + y][x0 + x] = clip(r[y][x], -m, m)
+ * and every sample of the coded area that no such block covers is 0: skip blocks, eob 0, and
+ * what a frame-edge partition leaves uncoded. Samples of a tx block outside the coded area are
+ * unspecified (stored or dropped); nothing is written outside the buffer's 64-padded planes.
+ * Why the clip: a prediction lies in [0, m], so clip(pred + r, 0, m) == clip(pred + clip(r, -m,
+ * m), 0, m) for every pred: the clipped residual is all of the residual any picture can see, and
+ * it fits int16 at 12 bits. It is also checkable against the reference's itxfm_add alone, on a
+ * flat block of 0 and a flat block of m:
+ *   clip(r, -m, m) = add(0) + (add(m) - m)
+ * where add(v) is the pixel itxfm_add leaves on a block that was v everywhere (add(0) = clip(r,
+ * 0, m), add(m) - m = clip(r, -m, 0)). Not exported: the prediction, the reconstruction before
+ * the loop filter, coefficients in the frequency domain.
+ *
+ * vp9hip_set_export accepts VP9HIP_EXPORT_MOTION | VP9HIP_EXPORT_RESIDUAL in any combination,
+ * under the rules stated there. With the residual flag vp9hip_configure allocates, per frame
+ * buffer, one block of three int16 planes, freed with the buffers, in the pixel planes' padded
+ * geometry: the pixel planes' pitches counted in elements and their 64-aligned heights, so a
+ * consumer indexes residual and pixels alike and a whole tx block always fits. A field lives as a
+ * motion field does: staging an exporting batch marks its output buffers, every vp9hip_run_batch
+ * writes the whole coded area of their fields (zeros included) on the slot's main stream ahead of
+ * the pixel work, so vp9hip_sync_slot / vp9hip_slot_stream_wait / vp9hip_sync cover it; a re-run
+ * writes the same bytes; a buffer several frames of one batch write keeps the last writer's
+ * field; the field of a frame the planner rejects is unspecified; vp9hip_stage_batch_tiles does
+ * not export, and it, vp9hip_upload_frame, vp9hip_fill_buffers and a run the planner refuses
+ * leave the buffers without a field. */
+#define VP9HIP_EXPORT_RESIDUAL 2
+/* The field of device buffer `buf`, in place: device pointers of the three int16 planes, their
+ * pitches in elements, the visible size of the frame last exported into the buffer (the planes
+ * hold its coded area, see above) and the current slot's main hipStream_t; any output pointer
+ * may be NULL. Ordering is the caller's, as for the pixels. VP9HIP_EINVAL without the flag or
+ * for a bad buf; VP9HIP_EAGAIN if the buffer holds no field. */
+int  vp9hip_frame_residual(vp9hip_ctx *ctx, int buf, void *planes[3], int64_t pitch[3], int *width, int *height,
+                           void **stream);
+/* Copy the coded area of the field of `buf` into host planes (a NULL plane is skipped) of
+ * linesize[] bytes a row (at least two bytes per sample of the coded width). Waits for the batches
+ * writing the buffer, like vp9hip_download_frame. Errors as vp9hip_frame_residual. */
+int  vp9hip_download_residual(vp9hip_ctx *ctx, int buf, int16_t *const planes[3], const ptrdiff_t linesize[3]);
+/* Host only, no device: the C++ statement of the definition above over the packet alone, with
+ * the kernel's 1-D transforms and record guards. planes[p] has pitch[p] int16 elements a row and
+ * rows[p] rows, each at least the coded area, which is written: zeros, then the blocks (samples
+ * outside the coded area are dropped). Every block, eob and coefficient index is checked
+ * against the packet's counts and the plane sizes before anything is read or written: a packet
+ * that breaks them returns VP9HIP_EINVALIDDATA with the planes untouched. VP9HIP_EINVAL for
+ * NULL arguments, a packet without a size or format, or planes smaller than the coded area. */
+int  vp9hip_residual_host(const vp9h_frame *pkt, int16_t *const planes[3], const ptrdiff_t pitch[3], const int rows[3]);
 
 /* Upload host planes into device buffer `buf` (test hook for reference frames). */
 int  vp9hip_upload_frame(vp9hip_ctx *ctx, int buf, const uint8_t *const planes[3],
@@ -930,6 +996,13 @@ int  vp9hip_decoder_set_export(vp9hip_decoder *d, int flags);
  * for a frame the caller does not hold. */
 int  vp9hip_decoder_frame_motion(vp9hip_decoder *d, const vp9hip_decoded_frame *frame, void **mv, void **info,
                                  int *gw, int *gh, int64_t *pitch_cells);
+/* The residual field of a received frame, in place (as vp9hip_frame_residual), under the rules
+ * of vp9hip_decoder_frame_motion: valid while the frame is un-released, a show_existing_frame
+ * output returns the field of the frame it shows, hidden frames export too. Needs
+ * VP9HIP_EXPORT_RESIDUAL in vp9hip_decoder_set_export's flags; VP9HIP_EINVAL without it or for
+ * a frame the caller does not hold. */
+int  vp9hip_decoder_frame_residual(vp9hip_decoder *d, const vp9hip_decoded_frame *frame, void *planes[3],
+                                   int64_t pitch[3]);
 /* avcodec_flush_buffers: drop queued frames and reference state (seek). */
 int  vp9hip_decoder_flush(vp9hip_decoder *d);
 
