@@ -26,6 +26,17 @@ struct CvtArgs {
     float   fscale;                    // half output: float(1.0 / maxv)
 };
 
+// What every launcher checks before it indexes its kernel table and sizes its grid.
+inline bool cvt_launch_ok(int format, int n) { return format >= 0 && format <= 3 && n >= 1 && n <= CVT_MAX_FRAMES; }
+
+// The resize kernels' workgroup: CVT_TILE_H waves, each one row of CVT_TILE_W output columns,
+// and the grid that covers n frames of ow x oh with it.
+constexpr int CVT_TILE_W = 128, CVT_TILE_H = 4;
+inline dim3 cvt_tile_grid(int ow, int oh, int n)
+{
+    return dim3((ow + CVT_TILE_W - 1) / CVT_TILE_W, (oh + CVT_TILE_H - 1) / CVT_TILE_H, n);
+}
+
 // One launch over n <= CVT_MAX_FRAMES frames of `format` (VP9HIP_OUT_*); hbd: 16-bit source
 // samples. Returns the launch's hipError_t.
 hipError_t vp9hip_convert_launch(const CvtArgs &a, int format, int hbd, int ss_h, int ss_v, int n, hipStream_t st);

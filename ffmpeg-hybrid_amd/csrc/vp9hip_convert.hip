@@ -13,8 +13,7 @@
 // The arithmetic is the integer definition of include/vp9hip.h / DESIGN.md "Output
 // conversion": nearest chroma sample, coefficients with `shift` fractional bits as kernel
 // arguments, round half up, clip.
-#include "vp9hip_convert.h"
-#include "../../include/vp9hip.h"
+#include "vp9hip_convert_dev.h"
 
 #include <array>
 #include <utility>
@@ -72,8 +71,6 @@ __device__ __forceinline__ void store_run(uint8_t *p, const uint32_t (&w)[NW], i
     }
 }
 
-__device__ __forceinline__ int clip(int v, int hi) { return min(max(v, 0), hi); }
-
 // FMT: VP9HIP_OUT_*; HBD: 16-bit source samples; SSH / SSV: chroma subsampling.
 template <int FMT, int HBD, int SSH, int SSV>
 __global__ __launch_bounds__(256) void k_convert(const CvtArgs a)
@@ -123,19 +120,7 @@ __global__ __launch_bounds__(256) void k_convert(const CvtArgs a)
         } else {
             int R[16], G[16], B[16];
 #pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const int u = U[i >> SSH], v = V[i >> SSH];
-                if (a.rgb) {                           // planes G, B, R
-                    R[i] = min((v + a.rnd) >> a.shift, a.maxv);
-                    G[i] = min((Y[i] + a.rnd) >> a.shift, a.maxv);
-                    B[i] = min((u + a.rnd) >> a.shift, a.maxv);
-                } else {
-                    const int yy = (Y[i] - a.yoff) * a.c[0] + a.rnd, cu = u - a.coff, cv = v - a.coff;
-                    R[i] = clip((yy + a.c[1] * cv) >> a.shift, a.maxv);
-                    G[i] = clip((yy - a.c[2] * cu - a.c[3] * cv) >> a.shift, a.maxv);
-                    B[i] = clip((yy + a.c[4] * cu) >> a.shift, a.maxv);
-                }
-            }
+            for (int i = 0; i < 16; i++) cvtdev::cvt_rgb(a, Y[i], U[i >> SSH], V[i >> SSH], R[i], G[i], B[i]);
             if constexpr (FMT == VP9HIP_OUT_RGB24) {
                 uint32_t w[12] = {};
 #pragma unroll
@@ -156,6 +141,8 @@ __global__ __launch_bounds__(256) void k_convert(const CvtArgs a)
                     store_run<4, 1>(row + p * a.plane + x0, w, npx);
                 }
             } else {                                   // half: one float multiply, round to nearest even
+                // (pairs compile to v_cvt_pk_f16_f32 of two float products: the two roundings
+                // of the definition without cvtdev::to_half's asm)
 #pragma unroll
                 for (int p = 0; p < 3; p++) {
                     const int (&C)[16] = p == 0 ? R : p == 1 ? G : B;
@@ -185,7 +172,7 @@ const std::array<KFn, 32> g_kernels = kernel_table(std::make_index_sequence<32>(
 
 hipError_t vp9hip_convert_launch(const CvtArgs &a, int format, int hbd, int ss_h, int ss_v, int n, hipStream_t st)
 {
-    if (format < 0 || format > 3 || n < 1 || n > CVT_MAX_FRAMES) return hipErrorInvalidValue;
+    if (!cvt_launch_ok(format, n)) return hipErrorInvalidValue;
     const int runs = (a.w + 15) / 16, rows = (a.h + ss_v) >> ss_v;
     const dim3 grid((runs + 63) / 64, (rows + 3) / 4, n), block(64, 4, 1);
     hipLaunchKernelGGL(g_kernels[format << 3 | !!hbd << 2 | !!ss_h << 1 | !!ss_v], grid, block, 0, st, a);

@@ -37,40 +37,17 @@
 // right edge, rows are the rectangle's rows only. A tile without a pixel of the destination
 // rectangle loads nothing and stores the fill. Pixels outside the destination rectangle take
 // the fill codes in place of the resampled samples and go through the same conversion.
-#include "vp9hip_convert.h"
-#include "../../include/vp9hip.h"
+#include "vp9hip_convert_dev.h"
 
 #include <array>
 #include <utility>
 
 namespace {
 
-constexpr int TW = 128, TH = 4;        // output tile: TH waves, each one row of TW columns
-constexpr int CHUNK = 256;             // source columns per pass: 64 lanes x 4 samples
+using namespace cvtdev;
+
 constexpr int QCAP = 512;              // a wave's qy table: source rows per block
 constexpr int QBITS = 14;              // Q
-
-__device__ __forceinline__ int clip(int v, int hi) { return min(max(v, 0), hi); }
-
-// The half output keeps its two roundings (see to_half in vp9hip_convert_scale.hip): the float
-// product is a value of its own, then rounded to the nearest-even half.
-__device__ __forceinline__ _Float16 to_half(int v, float fscale)
-{
-    float f = (float) v * fscale;
-    asm volatile("" : "+v"(f));
-    return (_Float16) f;
-}
-
-// floor(t / d) for 0 <= t < 2^30, 0 < d, with rcp = 1.0 / d in double: the estimate is within
-// one of the quotient, the remainder corrects it.
-__device__ __forceinline__ int floordiv(int t, int d, double rcp)
-{
-    int q = (int) ((double) t * rcp);
-    const int r = t - q * d;
-    if (r < 0) q--;
-    else if (r >= d) q++;
-    return q;
-}
 
 // LDS writes of a wave's lanes before, reads by its other lanes after: a wave's LDS operations
 // complete in order, so only the compiler has to keep them in place.
@@ -129,24 +106,6 @@ struct Axis {
     }
     __device__ __forceinline__ int weight(int k, int x) const { return q(k < x ? x - k : k - x); }
 };
-
-template <int HBD>
-__device__ __forceinline__ void add_row(const uint8_t *p, int32_t wy, int64_t (&v)[4])
-{
-    if constexpr (HBD) {
-        const uint2 s = *reinterpret_cast<const uint2 *>(p);
-        v[0] += (int64_t) wy * (int32_t) (s.x & 0xffff); v[1] += (int64_t) wy * (int32_t) (s.x >> 16);
-        v[2] += (int64_t) wy * (int32_t) (s.y & 0xffff); v[3] += (int64_t) wy * (int32_t) (s.y >> 16);
-    } else {
-        const uint32_t s = *reinterpret_cast<const uint32_t *>(p);
-        v[0] += (int64_t) wy * (int32_t) (s & 0xff); v[1] += (int64_t) wy * (int32_t) (s >> 8 & 0xff);
-        v[2] += (int64_t) wy * (int32_t) (s >> 16 & 0xff); v[3] += (int64_t) wy * (int32_t) (s >> 24);
-    }
-}
-
-// One plane geometry of one frame: the source rectangle (x, y, w, h) of planes with `pitch`,
-// resampled to dw x dh and placed at (dx, dy) of the output plane.
-struct Geo { int x, y, w, h, dx, dy, dw, dh; };
 
 // The workgroup's LDS: every wave's column sums (two planes), the tile's qx for one chunk, every
 // wave's qy for one block of source rows.
@@ -306,70 +265,21 @@ __global__ __launch_bounds__(256) void k_convert_cubic(const CvtCubicArgs ca)
     const CvtArgs &a = s.c;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH, oy = ty0 + wave;
-    constexpr int BS = HBD ? 2 : 1;
     const int z = blockIdx.z;
     const uint8_t *src = a.src[z];
     uint8_t *dst = a.dst + (int64_t) z * a.frame_stride;
 
-    const vp9hip_rect sr = s.src_rect[z], dr = s.dst_rect[z];
-    const Geo gy = { sr.x, sr.y, sr.w, sr.h, dr.x, dr.y, dr.w, dr.h };
-    // the chroma planes: the source rectangle at their subsampling; the destination rectangle
-    // at the output's (semi-planar: the source's; RGB: none)
-    const Geo gc = { sr.x >> s.ss_h, sr.y >> s.ss_v, (sr.w + s.ss_h) >> s.ss_h, (sr.h + s.ss_v) >> s.ss_v,
-                     dr.x >> s.ds_h, dr.y >> s.ds_v, (dr.w + s.ds_h) >> s.ds_h, (dr.h + s.ds_v) >> s.ds_v };
+    Geo gy, gc;
+    frame_geo(s, z, gy, gc);
     int Yk[1][2], UV[2][2] = {};
     const uint8_t *const py[1] = { src + a.src_off[0] }, *const puv[2] = { src + a.src_off[1], src + a.src_off[2] };
     const int fy[1] = { s.fill[0] }, fuv[2] = { s.fill[1], s.fill[2] };
     resample_row<HBD, 1>(py, a.src_pitch[0], gy, tx0, ty0, oy, L, wave, lane, fy, ca.smax, Yk);
     const bool ctile = tx0 < s.cow;                    // uniform: semi-planar chroma has fewer tiles
     if (ctile) resample_row<HBD, 2>(puv, a.src_pitch[1], gc, tx0, ty0, oy, L, wave, lane, fuv, ca.smax, UV);
-    const int (&Y)[2] = Yk[0], (&U)[2] = UV[0], (&V)[2] = UV[1];
 #pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const int x = tx0 + lane + 64 * k;
-        if constexpr (FMT == VP9HIP_OUT_SEMIPLANAR) {
-            if (x < s.ow && oy < s.oh) {
-                uint8_t *p = dst + (int64_t) oy * a.pitch + (int64_t) x * BS;
-                if constexpr (HBD) *reinterpret_cast<uint16_t *>(p) = (uint16_t) (Y[k] << a.msb);
-                else *p = (uint8_t) Y[k];
-            }
-            if (ctile && x < s.cow && oy < s.coh) {
-                uint8_t *p = dst + a.plane + (int64_t) oy * a.pitch + (int64_t) x * 2 * BS;
-                if constexpr (HBD) {
-                    reinterpret_cast<uint16_t *>(p)[0] = (uint16_t) (U[k] << a.msb);
-                    reinterpret_cast<uint16_t *>(p)[1] = (uint16_t) (V[k] << a.msb);
-                } else {
-                    p[0] = (uint8_t) U[k]; p[1] = (uint8_t) V[k];
-                }
-            }
-        } else {
-            if (x >= s.ow || oy >= s.oh) continue;
-            int R, G, B;
-            if (a.rgb) {                               // planes G, B, R
-                R = min((V[k] + a.rnd) >> a.shift, a.maxv);
-                G = min((Y[k] + a.rnd) >> a.shift, a.maxv);
-                B = min((U[k] + a.rnd) >> a.shift, a.maxv);
-            } else {
-                const int yy = (Y[k] - a.yoff) * a.c[0] + a.rnd, cu = U[k] - a.coff, cv = V[k] - a.coff;
-                R = clip((yy + a.c[1] * cv) >> a.shift, a.maxv);
-                G = clip((yy - a.c[2] * cu - a.c[3] * cv) >> a.shift, a.maxv);
-                B = clip((yy + a.c[4] * cu) >> a.shift, a.maxv);
-            }
-            uint8_t *row = dst + (int64_t) oy * a.pitch;
-            if constexpr (FMT == VP9HIP_OUT_RGB24) {
-                uint8_t *p = row + (int64_t) x * 3;
-                p[0] = (uint8_t) R; p[1] = (uint8_t) G; p[2] = (uint8_t) B;
-            } else if constexpr (FMT == VP9HIP_OUT_RGBP_U8) {
-                row[x] = (uint8_t) R; row[a.plane + x] = (uint8_t) G; row[2 * a.plane + x] = (uint8_t) B;
-            } else {                                   // half: one float multiply, round to nearest even
-                _Float16 *p = reinterpret_cast<_Float16 *>(row) + x;
-                const int64_t pl = a.plane / 2;
-                p[0] = to_half(R, a.fscale);
-                p[pl] = to_half(G, a.fscale);
-                p[2 * pl] = to_half(B, a.fscale);
-            }
-        }
-    }
+    for (int k = 0; k < 2; k++)
+        cvt_store_px<FMT, HBD>(a, dst, tx0 + lane + 64 * k, oy, s.ow, s.oh, s.cow, s.coh, ctile, Yk[0][k], UV[0][k], UV[1][k]);
 }
 
 typedef void (*KFn)(const CvtCubicArgs);
@@ -385,8 +295,7 @@ const std::array<KFn, 8> g_kernels = kernel_table(std::make_index_sequence<8>())
 
 hipError_t vp9hip_convert_cubic_launch(const CvtCubicArgs &a, int format, int hbd, int n, hipStream_t st)
 {
-    if (format < 0 || format > 3 || n < 1 || n > CVT_MAX_FRAMES) return hipErrorInvalidValue;
-    const dim3 grid((a.r.ow + TW - 1) / TW, (a.r.oh + TH - 1) / TH, n), block(64 * TH, 1, 1);
-    hipLaunchKernelGGL(g_kernels[format << 1 | !!hbd], grid, block, 0, st, a);
+    if (!cvt_launch_ok(format, n)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(g_kernels[format << 1 | !!hbd], cvt_tile_grid(a.r.ow, a.r.oh, n), dim3(64 * TH, 1, 1), 0, st, a);
     return hipGetLastError();
 }

@@ -30,38 +30,14 @@
 //   - a tile without a pixel of the destination rectangle loads nothing and stores the fill.
 // Pixels outside the destination rectangle take the fill codes in place of the resampled
 // samples and go through the same conversion, so the fill is the conversion of the codes.
-#include "vp9hip_convert.h"
-#include "../../include/vp9hip.h"
+#include "vp9hip_convert_dev.h"
 
 #include <array>
 #include <utility>
 
 namespace {
 
-constexpr int TW = 128, TH = 4;        // output tile: TH waves, each one row of TW columns
-constexpr int CHUNK = 256;             // source columns per pass: 64 lanes x 4 samples
-
-__device__ __forceinline__ int clip(int v, int hi) { return min(max(v, 0), hi); }
-
-// The half output keeps its two roundings (see to_half in vp9hip_convert_scale.hip): the float
-// product is a value of its own, then rounded to the nearest-even half.
-__device__ __forceinline__ _Float16 to_half(int v, float fscale)
-{
-    float f = (float) v * fscale;
-    asm volatile("" : "+v"(f));
-    return (_Float16) f;
-}
-
-// floor(t / d) for 0 <= t < 2^30, 0 < d, with rcp = 1.0 / d in double: the estimate is within
-// one of the quotient, the remainder corrects it.
-__device__ __forceinline__ int floordiv(int t, int d, double rcp)
-{
-    int q = (int) ((double) t * rcp);
-    const int r = t - q * d;
-    if (r < 0) q--;
-    else if (r >= d) q++;
-    return q;
-}
+using namespace cvtdev;
 
 // One axis of one plane's geometry: n_src source samples -> n_out output samples. An output
 // index o has a key, a source index s a term (both below 2^30); weight(key, term) is the
@@ -94,24 +70,6 @@ struct Axis {
         else return (uint32_t) (min(k + n_src, t + n_out) - max(k, t));
     }
 };
-
-template <int HBD>
-__device__ __forceinline__ void add_row(const uint8_t *p, uint32_t wy, uint64_t (&v)[4])
-{
-    if constexpr (HBD) {
-        const uint2 s = *reinterpret_cast<const uint2 *>(p);
-        v[0] += (uint64_t) wy * (s.x & 0xffff); v[1] += (uint64_t) wy * (s.x >> 16);
-        v[2] += (uint64_t) wy * (s.y & 0xffff); v[3] += (uint64_t) wy * (s.y >> 16);
-    } else {
-        const uint32_t s = *reinterpret_cast<const uint32_t *>(p);
-        v[0] += (uint64_t) wy * (s & 0xff); v[1] += (uint64_t) wy * (s >> 8 & 0xff);
-        v[2] += (uint64_t) wy * (s >> 16 & 0xff); v[3] += (uint64_t) wy * (s >> 24);
-    }
-}
-
-// One plane geometry of one frame: the source rectangle (x, y, w, h) of planes with `pitch`,
-// resampled to dw x dh and placed at (dx, dy) of the output plane.
-struct Geo { int x, y, w, h, dx, dy, dw, dh; };
 
 // out[p][k] = the output plane's sample at column tx0 + lane + 64 k of row oy, k = 0, 1, for NP
 // planes of one geometry (U and V): the resampled rectangle inside the destination rectangle,
@@ -182,22 +140,14 @@ __device__ __forceinline__ void resample_row(const uint8_t *const (&P)[NP], int 
         }
         __syncthreads();
     }
-    // one division per output sample: the quotient is below 2^16 and the estimate within
-    // 2^-30 of it; the exact remainder (|r| < 2 den < 2^63) corrects it
+    // one division per output sample, by the sum of the weights it took
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         if (!ok[k]) continue;
         const uint64_t den = (uint64_t) dsum_x[k] * dsum_y;
         const double rcp = 1.0 / (double) den;
 #pragma unroll
-        for (int p = 0; p < NP; p++) {
-            const uint64_t A = acc[p][k] + (den >> 1);
-            uint32_t q = (uint32_t) ((double) A * rcp);
-            const int64_t r = (int64_t) (A - q * den);
-            if (r < 0) q--;
-            else if (r >= (int64_t) den) q++;
-            out[p][k] = (int) q;
-        }
+        for (int p = 0; p < NP; p++) out[p][k] = rounded_quot(acc[p][k], den, rcp);
     }
 }
 
@@ -209,71 +159,22 @@ __global__ __launch_bounds__(256) void k_convert_resample(const CvtResampleArgs 
     const CvtArgs &a = s.c;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH, oy = ty0 + wave;
-    constexpr int BS = HBD ? 2 : 1;
     const int z = blockIdx.z;
     const uint8_t *src = a.src[z];
     uint8_t *dst = a.dst + (int64_t) z * a.frame_stride;
     uint64_t *cs = colsum[wave];
 
-    const vp9hip_rect sr = s.src_rect[z], dr = s.dst_rect[z];
-    const Geo gy = { sr.x, sr.y, sr.w, sr.h, dr.x, dr.y, dr.w, dr.h };
-    // the chroma planes: the source rectangle at their subsampling; the destination rectangle
-    // at the output's (semi-planar: the source's; RGB: none)
-    const Geo gc = { sr.x >> s.ss_h, sr.y >> s.ss_v, (sr.w + s.ss_h) >> s.ss_h, (sr.h + s.ss_v) >> s.ss_v,
-                     dr.x >> s.ds_h, dr.y >> s.ds_v, (dr.w + s.ds_h) >> s.ds_h, (dr.h + s.ds_v) >> s.ds_v };
+    Geo gy, gc;
+    frame_geo(s, z, gy, gc);
     int Yk[1][2], UV[2][2] = {};
     const uint8_t *const py[1] = { src + a.src_off[0] }, *const puv[2] = { src + a.src_off[1], src + a.src_off[2] };
     const int fy[1] = { s.fill[0] }, fuv[2] = { s.fill[1], s.fill[2] };
     resample_row<FILT, HBD, 1>(py, a.src_pitch[0], gy, tx0, ty0, oy, cs, lane, fy, Yk);
     const bool ctile = tx0 < s.cow;                    // uniform: semi-planar chroma has fewer tiles
     if (ctile) resample_row<FILT, HBD, 2>(puv, a.src_pitch[1], gc, tx0, ty0, oy, cs, lane, fuv, UV);
-    const int (&Y)[2] = Yk[0], (&U)[2] = UV[0], (&V)[2] = UV[1];
 #pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const int x = tx0 + lane + 64 * k;
-        if constexpr (FMT == VP9HIP_OUT_SEMIPLANAR) {
-            if (x < s.ow && oy < s.oh) {
-                uint8_t *p = dst + (int64_t) oy * a.pitch + (int64_t) x * BS;
-                if constexpr (HBD) *reinterpret_cast<uint16_t *>(p) = (uint16_t) (Y[k] << a.msb);
-                else *p = (uint8_t) Y[k];
-            }
-            if (ctile && x < s.cow && oy < s.coh) {
-                uint8_t *p = dst + a.plane + (int64_t) oy * a.pitch + (int64_t) x * 2 * BS;
-                if constexpr (HBD) {
-                    reinterpret_cast<uint16_t *>(p)[0] = (uint16_t) (U[k] << a.msb);
-                    reinterpret_cast<uint16_t *>(p)[1] = (uint16_t) (V[k] << a.msb);
-                } else {
-                    p[0] = (uint8_t) U[k]; p[1] = (uint8_t) V[k];
-                }
-            }
-        } else {
-            if (x >= s.ow || oy >= s.oh) continue;
-            int R, G, B;
-            if (a.rgb) {                               // planes G, B, R
-                R = min((V[k] + a.rnd) >> a.shift, a.maxv);
-                G = min((Y[k] + a.rnd) >> a.shift, a.maxv);
-                B = min((U[k] + a.rnd) >> a.shift, a.maxv);
-            } else {
-                const int yy = (Y[k] - a.yoff) * a.c[0] + a.rnd, cu = U[k] - a.coff, cv = V[k] - a.coff;
-                R = clip((yy + a.c[1] * cv) >> a.shift, a.maxv);
-                G = clip((yy - a.c[2] * cu - a.c[3] * cv) >> a.shift, a.maxv);
-                B = clip((yy + a.c[4] * cu) >> a.shift, a.maxv);
-            }
-            uint8_t *row = dst + (int64_t) oy * a.pitch;
-            if constexpr (FMT == VP9HIP_OUT_RGB24) {
-                uint8_t *p = row + (int64_t) x * 3;
-                p[0] = (uint8_t) R; p[1] = (uint8_t) G; p[2] = (uint8_t) B;
-            } else if constexpr (FMT == VP9HIP_OUT_RGBP_U8) {
-                row[x] = (uint8_t) R; row[a.plane + x] = (uint8_t) G; row[2 * a.plane + x] = (uint8_t) B;
-            } else {                                   // half: one float multiply, round to nearest even
-                _Float16 *p = reinterpret_cast<_Float16 *>(row) + x;
-                const int64_t pl = a.plane / 2;
-                p[0] = to_half(R, a.fscale);
-                p[pl] = to_half(G, a.fscale);
-                p[2 * pl] = to_half(B, a.fscale);
-            }
-        }
-    }
+    for (int k = 0; k < 2; k++)
+        cvt_store_px<FMT, HBD>(a, dst, tx0 + lane + 64 * k, oy, s.ow, s.oh, s.cow, s.coh, ctile, Yk[0][k], UV[0][k], UV[1][k]);
 }
 
 typedef void (*KFn)(const CvtResampleArgs);
@@ -289,8 +190,7 @@ const std::array<KFn, 16> g_kernels = kernel_table(std::make_index_sequence<16>(
 
 hipError_t vp9hip_convert_resample_launch(const CvtResampleArgs &a, int format, int hbd, int filter, int n, hipStream_t st)
 {
-    if (format < 0 || format > 3 || filter < 0 || filter > 1 || n < 1 || n > CVT_MAX_FRAMES) return hipErrorInvalidValue;
-    const dim3 grid((a.ow + TW - 1) / TW, (a.oh + TH - 1) / TH, n), block(64 * TH, 1, 1);
-    hipLaunchKernelGGL(g_kernels[format << 2 | !!hbd << 1 | filter], grid, block, 0, st, a);
+    if (!cvt_launch_ok(format, n) || filter < 0 || filter > 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(g_kernels[format << 2 | !!hbd << 1 | filter], cvt_tile_grid(a.ow, a.oh, n), dim3(64 * TH, 1, 1), 0, st, a);
     return hipGetLastError();
 }

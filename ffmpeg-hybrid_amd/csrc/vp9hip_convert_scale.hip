@@ -20,68 +20,26 @@
 // The chunk loop covers any footprint (-> 1 x 1 walks the whole plane with one wave: correct,
 // not fast). U and V have one geometry and are taken in one pass. The three planes of an RGB
 // output are resampled to the same grid, so a lane holds Y, U and V of its pixels and runs the
-// matrix of vp9hip_convert.hip unchanged. Semi-planar chroma has its own grid (OCW x OCH): the
-// workgroups whose tile lies inside it take it too. The footprints' bounds are divisions by
+// matrix of the full-size conversion (cvt_store_px, vp9hip_convert_dev.h). Semi-planar chroma
+// has its own grid (OCW x OCH): the workgroups whose tile lies inside it take it too. The footprints' bounds are divisions by
 // an argument; they use the host's reciprocal and a correction as the quotient does. Loads
 // are aligned groups of 4 samples below the footprint's end, which is at most the visible
 // width, so they stay inside the 64-padded plane and padding has weight zero. Stores are per
 // element, lanes on consecutive pixels, only at ox < out_w, oy < out_h.
-#include "vp9hip_convert.h"
-#include "../../include/vp9hip.h"
+#include "vp9hip_convert_dev.h"
 
 #include <array>
 #include <utility>
 
 namespace {
 
-constexpr int TW = 128, TH = 4;        // output tile: TH waves, each one row of TW columns
-constexpr int CHUNK = 256;             // source columns per pass: 64 lanes x 4 samples
-
-__device__ __forceinline__ int clip(int v, int hi) { return min(max(v, 0), hi); }
-
-// The half output: the float product rounded to float, then to the nearest-even half, as the
-// definition says. Left to the compiler, the two become one v_fma_mixlo_f16 here, which rounds
-// once and differs where the float product rounds onto a half's midpoint (12-bit samples
-// show it); the empty asm keeps the float product a value of its own.
-__device__ __forceinline__ _Float16 to_half(int v, float fscale)
-{
-    float f = (float) v * fscale;
-    asm volatile("" : "+v"(f));
-    return (_Float16) f;
-}
+using namespace cvtdev;
 
 // lo = o n_src: the overlap of [lo, lo + n_src) and [so, so + n_out), so = s n_out: the weight
 // of source s for output o
 __device__ __forceinline__ uint32_t overlap(int lo, int n_src, int so, int n_out)
 {
     return (uint32_t) (min(lo + n_src, so + n_out) - max(lo, so));
-}
-
-// floor(t / d) for 0 <= t < 2^29, 0 < d, with the host's double rcp = 1.0 / d: the estimate is
-// within one of the quotient (its error is below 2^-23), the remainder corrects it. A few
-// instructions where the compiler's expansion of an integer division by a kernel argument
-// takes about 25, and a wave needs 16 of them before its first load.
-__device__ __forceinline__ int floordiv(int t, int d, double rcp)
-{
-    int q = (int) ((double) t * rcp);
-    const int r = t - q * d;
-    if (r < 0) q--;
-    else if (r >= d) q++;
-    return q;
-}
-
-template <int HBD>
-__device__ __forceinline__ void add_row(const uint8_t *p, uint32_t wy, uint32_t (&v)[4])
-{
-    if constexpr (HBD) {
-        const uint2 s = *reinterpret_cast<const uint2 *>(p);
-        v[0] += wy * (s.x & 0xffff); v[1] += wy * (s.x >> 16);
-        v[2] += wy * (s.y & 0xffff); v[3] += wy * (s.y >> 16);
-    } else {
-        const uint32_t s = *reinterpret_cast<const uint32_t *>(p);
-        v[0] += wy * (s & 0xff); v[1] += wy * (s >> 8 & 0xff);
-        v[2] += wy * (s >> 16 & 0xff); v[3] += wy * (s >> 24);
-    }
 }
 
 // out[p][k] = box(P[p], ow, oh) at (tx0 + lane + 64 k, oy), k = 0, 1, for NP planes of one
@@ -136,19 +94,11 @@ __device__ __forceinline__ void box_row(const uint8_t *const (&P)[NP], int pitch
         }
         __syncthreads();
     }
-    // the quotient is below 2^16 (16-bit samples at most) and the estimate within 2^-30 of it
     const uint64_t den = (uint64_t) w * (uint64_t) h;
 #pragma unroll
     for (int p = 0; p < NP; p++)
 #pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const uint64_t A = acc[p][k] + (den >> 1);
-            uint32_t q = (uint32_t) ((double) A * rcp);
-            const int64_t r = (int64_t) (A - q * den);
-            if (r < 0) q--;
-            else if (r >= (int64_t) den) q++;
-            out[p][k] = (int) q;
-        }
+        for (int k = 0; k < 2; k++) out[p][k] = rounded_quot(acc[p][k], den, rcp);
 }
 
 // FMT: VP9HIP_OUT_*; HBD: 16-bit source samples.
@@ -159,7 +109,6 @@ __global__ __launch_bounds__(256) void k_convert_scale(const CvtScaleArgs s)
     const CvtArgs &a = s.c;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tx0 = blockIdx.x * TW, oy = blockIdx.y * TH + wave;
-    constexpr int BS = HBD ? 2 : 1;
     const uint8_t *src = a.src[blockIdx.z];
     uint8_t *dst = a.dst + (int64_t) blockIdx.z * a.frame_stride;
     uint32_t *cs = colsum[wave];
@@ -170,53 +119,9 @@ __global__ __launch_bounds__(256) void k_convert_scale(const CvtScaleArgs s)
     const bool ctile = tx0 < s.cow;                    // uniform: semi-planar chroma has fewer tiles
     if (ctile)
         box_row<HBD, 2>(puv, a.src_pitch[1], a.cw, a.ch, s.cow, s.coh, tx0, oy, oy < s.coh, s.rcp[1], s.rx[1], s.ry[1], cs, lane, UV);
-    const int (&Y)[2] = Yk[0], (&U)[2] = UV[0], (&V)[2] = UV[1];
 #pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const int x = tx0 + lane + 64 * k;
-        if constexpr (FMT == VP9HIP_OUT_SEMIPLANAR) {
-            if (x < s.ow && oy < s.oh) {
-                uint8_t *p = dst + (int64_t) oy * a.pitch + (int64_t) x * BS;
-                if constexpr (HBD) *reinterpret_cast<uint16_t *>(p) = (uint16_t) (Y[k] << a.msb);
-                else *p = (uint8_t) Y[k];
-            }
-            if (ctile && x < s.cow && oy < s.coh) {
-                uint8_t *p = dst + a.plane + (int64_t) oy * a.pitch + (int64_t) x * 2 * BS;
-                if constexpr (HBD) {
-                    reinterpret_cast<uint16_t *>(p)[0] = (uint16_t) (U[k] << a.msb);
-                    reinterpret_cast<uint16_t *>(p)[1] = (uint16_t) (V[k] << a.msb);
-                } else {
-                    p[0] = (uint8_t) U[k]; p[1] = (uint8_t) V[k];
-                }
-            }
-        } else {
-            if (x >= s.ow || oy >= s.oh) continue;
-            int R, G, B;
-            if (a.rgb) {                               // planes G, B, R
-                R = min((V[k] + a.rnd) >> a.shift, a.maxv);
-                G = min((Y[k] + a.rnd) >> a.shift, a.maxv);
-                B = min((U[k] + a.rnd) >> a.shift, a.maxv);
-            } else {
-                const int yy = (Y[k] - a.yoff) * a.c[0] + a.rnd, cu = U[k] - a.coff, cv = V[k] - a.coff;
-                R = clip((yy + a.c[1] * cv) >> a.shift, a.maxv);
-                G = clip((yy - a.c[2] * cu - a.c[3] * cv) >> a.shift, a.maxv);
-                B = clip((yy + a.c[4] * cu) >> a.shift, a.maxv);
-            }
-            uint8_t *row = dst + (int64_t) oy * a.pitch;
-            if constexpr (FMT == VP9HIP_OUT_RGB24) {
-                uint8_t *p = row + (int64_t) x * 3;
-                p[0] = (uint8_t) R; p[1] = (uint8_t) G; p[2] = (uint8_t) B;
-            } else if constexpr (FMT == VP9HIP_OUT_RGBP_U8) {
-                row[x] = (uint8_t) R; row[a.plane + x] = (uint8_t) G; row[2 * a.plane + x] = (uint8_t) B;
-            } else {                                   // half: one float multiply, round to nearest even
-                _Float16 *p = reinterpret_cast<_Float16 *>(row) + x;
-                const int64_t pl = a.plane / 2;
-                p[0] = to_half(R, a.fscale);
-                p[pl] = to_half(G, a.fscale);
-                p[2 * pl] = to_half(B, a.fscale);
-            }
-        }
-    }
+    for (int k = 0; k < 2; k++)
+        cvt_store_px<FMT, HBD>(a, dst, tx0 + lane + 64 * k, oy, s.ow, s.oh, s.cow, s.coh, ctile, Yk[0][k], UV[0][k], UV[1][k]);
 }
 
 typedef void (*KFn)(const CvtScaleArgs);
@@ -232,8 +137,7 @@ const std::array<KFn, 8> g_kernels = kernel_table(std::make_index_sequence<8>())
 
 hipError_t vp9hip_convert_scale_launch(const CvtScaleArgs &a, int format, int hbd, int n, hipStream_t st)
 {
-    if (format < 0 || format > 3 || n < 1 || n > CVT_MAX_FRAMES) return hipErrorInvalidValue;
-    const dim3 grid((a.ow + TW - 1) / TW, (a.oh + TH - 1) / TH, n), block(64 * TH, 1, 1);
-    hipLaunchKernelGGL(g_kernels[format << 1 | !!hbd], grid, block, 0, st, a);
+    if (!cvt_launch_ok(format, n)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(g_kernels[format << 1 | !!hbd], cvt_tile_grid(a.ow, a.oh, n), dim3(64 * TH, 1, 1), 0, st, a);
     return hipGetLastError();
 }

@@ -3180,6 +3180,25 @@ static int convert_args(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_
     return 0;
 }
 
+// The launches of a validated call, on `stream` (NULL: the current slot's main stream): frames
+// i0 .. i0 + k - 1 each, k <= CVT_MAX_FRAMES, their buffers in a.src[] and a.dst at frame i0;
+// launch(i0, k, st) sets what else is per frame, launches and returns 0 or an error code.
+template <class F>
+static int convert_launches(vp9hip_ctx *c, const int *bufs, int n, CvtArgs &a, void *dst_dev, int64_t stride, void *stream,
+                            F launch)
+{
+    hipSetDevice(c->dev);
+    hipStream_t st = stream ? (hipStream_t) stream : c->st;
+    for (int i0 = 0; i0 < n; i0 += CVT_MAX_FRAMES) {
+        const int k = std::min(n - i0, CVT_MAX_FRAMES);
+        for (int i = 0; i < k; i++) a.src[i] = c->bufs[bufs[i0 + i]];
+        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
+        const int r = launch(i0, k, st);
+        if (r < 0) return r;
+    }
+    return 0;
+}
+
 extern "C" int vp9hip_convert_frames(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d, void *dst_dev,
                                      void *stream)
 {
@@ -3187,15 +3206,10 @@ extern "C" int vp9hip_convert_frames(vp9hip_ctx *c, const int *bufs, int n, cons
     int64_t stride;
     const int r = convert_args(c, bufs, n, d, d ? d->width : 0, d ? d->height : 0, dst_dev, a, &stride);
     if (r < 0) return r;
-    hipSetDevice(c->dev);
-    hipStream_t st = stream ? (hipStream_t) stream : c->st;
-    for (int i0 = 0; i0 < n; i0 += CVT_MAX_FRAMES) {
-        const int k = std::min(n - i0, CVT_MAX_FRAMES);
-        for (int i = 0; i < k; i++) a.src[i] = c->bufs[bufs[i0 + i]];
-        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
+    return convert_launches(c, bufs, n, a, dst_dev, stride, stream, [&](int, int k, hipStream_t st) {
         HIPCHK(vp9hip_convert_launch(a, d->format, c->hb, c->ss_h, c->ss_v, k, st));
-    }
-    return 0;
+        return 0;
+    });
 }
 
 // The same with the box-filter resize to out_width x out_height fused in (k_convert_scale).
@@ -3217,15 +3231,10 @@ extern "C" int vp9hip_convert_frames_scaled(vp9hip_ctx *c, const int *bufs, int 
     s.rcp[1] = 1.0 / ((double) a.cw * (double) a.ch);
     s.rx[0] = 1.0 / s.ow; s.rx[1] = 1.0 / s.cow;
     s.ry[0] = 1.0 / s.oh; s.ry[1] = 1.0 / s.coh;
-    hipSetDevice(c->dev);
-    hipStream_t st = stream ? (hipStream_t) stream : c->st;
-    for (int i0 = 0; i0 < n; i0 += CVT_MAX_FRAMES) {
-        const int k = std::min(n - i0, CVT_MAX_FRAMES);
-        for (int i = 0; i < k; i++) a.src[i] = c->bufs[bufs[i0 + i]];
-        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
+    return convert_launches(c, bufs, n, a, dst_dev, stride, stream, [&](int, int k, hipStream_t st) {
         HIPCHK(vp9hip_convert_scale_launch(s, d->format, c->hb, k, st));
-    }
-    return 0;
+        return 0;
+    });
 }
 
 // max over o of D(o) for one axis (vp9hip_resample_weights is the definition): the bound's two
@@ -3326,23 +3335,18 @@ static int convert_resampled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip
     }
     CvtCubicArgs cu;
     cu.smax = (int32_t) maxv;
-    hipSetDevice(c->dev);
-    hipStream_t st = stream ? (hipStream_t) stream : c->st;
-    for (int i0 = 0; i0 < n; i0 += CVT_MAX_FRAMES) {
-        const int k = std::min(n - i0, CVT_MAX_FRAMES);
+    return convert_launches(c, bufs, n, a, dst_dev, stride, stream, [&](int i0, int k, hipStream_t st) {
         for (int i = 0; i < k; i++) {
-            a.src[i] = c->bufs[bufs[i0 + i]];
             s.src_rect[i] = src[i0 + i];
             s.dst_rect[i] = dst[i0 + i];
         }
-        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
         if (cubic) {
             cu.r = s;
             HIPCHK(vp9hip_convert_cubic_launch(cu, d->format, c->hb, k, st));
         } else
             HIPCHK(vp9hip_convert_resample_launch(s, d->format, c->hb, rs->filter, k, st));
-    }
-    return 0;
+        return 0;
+    });
 }
 
 // The resampling with the box or the triangle filter (k_convert_resample).
