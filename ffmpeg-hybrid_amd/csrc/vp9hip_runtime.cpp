@@ -15,13 +15,14 @@
 //     wavefront (t = x + 2y) that reproduces the reference's SB-raster LF order
 //     (vp9.c:1419-1429).
 // Everything is uploaded into one HBM arena per staged batch; run launches only.
+// The policy of a launch list (batch phases, the fused-phase schedule, the k_lfr task table)
+// is in vp9hip_sched.h, shared by the host planner, the static plan and the device plan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
-#include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -39,6 +40,7 @@
 #include "vp9_tables.h"
 #include "vp9hip_work.h"
 #include "vp9hip_planlogic.h"
+#include "vp9hip_sched.h"
 #include "vp9hip_plan.h"
 #include "vp9hip_convert.h"
 #include "vp9hip_motion.h"
@@ -91,16 +93,6 @@ struct Launch { int kind; uint32_t off; uint32_t n; int arg; int grp; int ph; in
                 int flow = -1;  // K_PRED of a level phase as one k_predd launch: its counter block;
                                 // K_LFR with the phase's intra SBs inside (off2 / n2 their list)
 };
-#define PLF_LAG 3   // see the schedule in stage()
-// Residuals run inside the fused launches (one intra diagonal ahead) for phases of fewer
-// frames than this; wide phases (keyframe batches) keep their separate k_resid launches:
-// measured C2 +6.5 % fused, C3 -2 %, C4 -8 %
-#define RES_FUSE_MAX_FRAMES 8
-// The loop filter of phases of fewer frames than this runs as one row-pipelined k_lfr launch
-// (its tail after the fused diagonals); wide phases keep diagonal launches: measured C2
-// +8-10 %, C3 -6 % with k_lfr everywhere (its long-lived workgroups crowd the other groups'
-// intra wavefronts)
-#define LFR_MAX_FRAMES 8
 enum { PART_RECON, PART_LF };           // a phase's reconstruction launches, then its loop filter
 #define MAX_GROUPS 8                    // independent frame groups = concurrent launch chains
 #define MAX_SLOTS VP9HIP_MAX_SLOTS      // batch slots per context (include/vp9hip.h)
@@ -399,6 +391,47 @@ struct vp9hip_ctx {
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
     fprintf(stderr, "vp9hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return VP9HIP_EEXTERNAL; } } while (0)
 
+// Grow a slot's buffer (device, or pinned host) to `need` bytes, contents not kept; empty if it fails.
+template <class T>
+static int grow(T *&p, size_t &cap, size_t need, bool pinned = false)
+{
+    if (need <= cap) return 0;
+    if (p) pinned ? hipHostFree(p) : hipFree(p);
+    p = nullptr;
+    const hipError_t e = pinned ? hipHostMalloc((void **) &p, need, hipHostMallocDefault) : hipMalloc((void **) &p, need);
+    cap = e == hipSuccess ? need : 0;
+    return e == hipSuccess ? 0 : VP9HIP_ENOMEM;
+}
+// fn(i) for every frame i < n of a batch, on min(n, host_threads) threads, the caller among them.
+template <class F>
+static void for_frames(const vp9hip_ctx *c, int n, F &&fn)
+{
+    std::atomic<int> next(0);
+    auto worker = [&]() { for (int i; (i = next.fetch_add(1)) < n;) fn(i); };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < std::min(n, c->host_threads); t++) pool.emplace_back(worker);
+    worker();
+    for (auto &t : pool) t.join();
+}
+// Frame i is the last of the batch's n frames to write its output buffer.
+static bool last_writer(const int *out_bufs, int n, int i)
+{
+    return std::find(out_bufs + i + 1, out_bufs + n, out_bufs[i]) == out_bufs + n;
+}
+// The SBs of a frame in raster order: fn(x, y, slot = y * sb_cols + x, intra diagonal x_in_tile + y).
+template <class F>
+static void for_sbs(int sb_cols, int sb_rows, int log2_tile_cols, F &&fn)
+{
+    for (int y = 0; y < sb_rows; y++)
+        for (int x = 0; x < sb_cols; x++) {
+            int ts0;
+            pl_tile_of(x, sb_cols, log2_tile_cols, &ts0);
+            fn(x, y, (uint32_t) (y * sb_cols + x), (x - ts0) + y);
+        }
+}
+// The pixel format word of the kernels' launchers: high bit depth, chroma subsampling.
+static int fmt_word(const vp9hip_ctx *c) { return c->hb | c->ss_h << 1 | c->ss_v << 2; }
+
 // The planner's stream: the slot's main stream with per-slot streams, else its own.
 static hipStream_t plan_stream(const vp9hip_ctx *c) { return c->slot_streams ? c->st : c->pst; }
 // Slot k's staged batch (the current one lives in c->stg).
@@ -688,30 +721,24 @@ extern "C" int vp9hip_configure(vp9hip_ctx *c, int width, int height, int bpp, i
     c->plane_off[1] = (size_t) c->pitch[0] * hy * c->bypp;
     c->plane_off[2] = c->plane_off[1] + (size_t) c->pitch[1] * hc * c->bypp;
     c->buf_bytes = c->plane_off[2] + (size_t) c->pitch[1] * hc * c->bypp;
-    for (int i = 0; i < nbufs; i++) {
-        uint8_t *b = nullptr;
-        if (hipMalloc(&b, c->buf_bytes) != hipSuccess) { free_bufs(c); return VP9HIP_ENOMEM; }
-        hipMemsetAsync(b, 0, c->buf_bytes, c->st);
-        c->bufs.push_back(b);
-        c->buf_wh.push_back({ width, height });
-    }
+    // nbufs allocations of `bytes`, each with its size record; all buffers are freed if one fails
+    auto alloc = [&](std::vector<uint8_t *> &v, std::vector<std::pair<int, int>> &wh, std::pair<int, int> wh0, size_t bytes) {
+        for (int i = 0; i < nbufs; i++) {
+            uint8_t *b = nullptr;
+            if (hipMalloc(&b, bytes) != hipSuccess) { free_bufs(c); return false; }
+            v.push_back(b);
+            wh.push_back(wh0);
+        }
+        return true;
+    };
+    if (!alloc(c->bufs, c->buf_wh, { width, height }, c->buf_bytes)) return VP9HIP_ENOMEM;
+    for (uint8_t *b : c->bufs) hipMemsetAsync(b, 0, c->buf_bytes, c->st);
     if (c->export_flags & VP9HIP_EXPORT_MOTION) {
         c->mot_pitch = 2 * c->cols; c->mot_rows = 2 * c->rows;
-        for (int i = 0; i < nbufs; i++) {
-            uint8_t *b = nullptr;
-            if (hipMalloc(&b, (size_t) c->mot_pitch * c->mot_rows * 12) != hipSuccess) { free_bufs(c); return VP9HIP_ENOMEM; }
-            c->mot.push_back(b);
-            c->mot_gwh.push_back({ 0, 0 });
-        }
+        if (!alloc(c->mot, c->mot_gwh, { 0, 0 }, (size_t) c->mot_pitch * c->mot_rows * 12)) return VP9HIP_ENOMEM;
     }
-    if (c->export_flags & VP9HIP_EXPORT_RESIDUAL) {
-        for (int i = 0; i < nbufs; i++) {
-            uint8_t *b = nullptr;
-            if (hipMalloc(&b, c->buf_bytes / c->bypp * 2) != hipSuccess) { free_bufs(c); return VP9HIP_ENOMEM; }
-            c->res.push_back(b);
-            c->res_wh.push_back({ 0, 0 });
-        }
-    }
+    if ((c->export_flags & VP9HIP_EXPORT_RESIDUAL) && !alloc(c->res, c->res_wh, { 0, 0 }, c->buf_bytes / c->bypp * 2))
+        return VP9HIP_ENOMEM;
     int r = upload_ptab(c);
     if (!r) r = upload_nz(c);
     if (r) return r;
@@ -1138,11 +1165,12 @@ static double sb_bytes(const vp9hip_ctx *c, const vp9h_frame &f, int sbx, int sb
 // residual segments, intra-step keys, LF diagonal lists, k_lfr task tables: O(SBs), no
 // per-block work) and one upload of the packets; plan_dev (every run): the device planner
 // (vp9hip_plan.hip), a readback of its summary (record counts, status) and the launch list.
-struct DevIn {
+// What stage() hands to stage_dev (and to stage_host, the host planner)
+struct StageIn {
     const vp9h_frame *pkts;
-    int n, G, maxpos, NP, csz;
+    int n, csz;
     const std::vector<FrameBuild> *fbs;
-    const std::vector<char> *res_fused, *lvl_ph;
+    const SchedPhases *ph;       // groups, chain positions and phases of the batch
     bool fuse, lfr_any;
     const int *out_bufs;
     bool motion;                 // the batch exports its frames' motion fields
@@ -1157,12 +1185,36 @@ static void init_lfr_ctr(const vp9hip_ctx *c, const Staged &s, uint32_t *ctr)
     for (uint32_t o : s.lfr_ctr) ctr[o + 3] = c->lfr_spin;
 }
 
+// The launch of one step of sched_fused_phase: K_PLF, or K_LF (then b and rr are zero).
+static Launch fused_launch(int g, int ph, int fused, int step, SchedRange a, SchedRange b, const SchedRange *rr)
+{
+    Launch L = { fused ? K_PLF : K_LF, a.first, a.second, 0, g, ph, fused ? PART_RECON : PART_LF, step };
+    L.off2 = b.first; L.n2 = b.second;
+    for (int k = 0; k < 5; k++) { L.roff[k] = rr[k].first; L.rn[k] = rr[k].second; }
+    return L;
+}
+// That launch for phase P of a device-planned batch (static plan and plan_dev), with the
+// algorithmic bytes it moves out of the separate kernels' totals in `bytes`.
+static void push_fused(Staged &s, const Staged::DevPhase &P, double *bytes, int g, int ph, int fused, int step,
+                       SchedRange a, SchedRange b, const SchedRange *rr)
+{
+    s.launches.push_back(fused_launch(g, ph, fused, step, a, b, rr));
+    if (fused && a.second && step < (int) P.pred_bytes.size()) {
+        bytes[K_PRED] -= P.pred_bytes[step];
+        bytes[K_PLF] += P.pred_bytes[step];
+    }
+    if (fused && b.second) {
+        bytes[K_LF] -= P.lf_bytes[step - PLF_LAG];
+        bytes[K_PLF] += P.lf_bytes[step - PLF_LAG];
+    }
+}
+
 // Keyframe batches (every phase wide, not fused, no k_lfr, intra frames only): the launch
 // list plan_dev would build, from the geometry. Intra frames have intra work in every SB
 // (PLS_ORDER rejects an SB without blocks), so step key k holds every SB of its phase's
 // frames on intra diagonal k - key0, and the step lists' offsets are the prefix sums of
 // those counts (k_pkeys). Residual launches take their job ranges from the summary.
-static void build_static_plan(vp9hip_ctx *c, const DevIn &in, const std::vector<uint32_t> &slot0)
+static void build_static_plan(vp9hip_ctx *c, const StageIn &in, const std::vector<uint32_t> &slot0)
 {
     Staged &s = c->stg;
     const bool off = !c->static_plan;
@@ -1177,35 +1229,23 @@ static void build_static_plan(vp9hip_ctx *c, const DevIn &in, const std::vector<
         for (int i : P.frames)
             if (!(in.pkts[i].keyframe || in.pkts[i].intraonly)) return;
     }
+    // fn(key, slot) for every SB of the batch: frames in phase order, raster order inside a frame
+    auto for_keys = [&](auto &&fn) {
+        for (const Staged::DevPhase &P : s.dph)
+            for (int i : P.frames)
+                for_sbs(fbs[i].sb_cols, fbs[i].sb_rows, fbs[i].f->log2_tile_cols, [&](int, int, uint32_t slot, int d) {
+                    const uint32_t k = P.key0 + (uint32_t) d;
+                    if (k < s.nkey) fn(k, slot0[i] + slot);
+                });
+    };
     std::vector<uint32_t> kc(s.nkey, 0);
-    for (const Staged::DevPhase &P : s.dph)
-        for (int i : P.frames) {
-            const FrameBuild &fb = fbs[i];
-            for (int y = 0; y < fb.sb_rows; y++)
-                for (int x = 0; x < fb.sb_cols; x++) {
-                    int ts0;
-                    pl_tile_of(x, fb.sb_cols, fb.f->log2_tile_cols, &ts0);
-                    const uint32_t k = P.key0 + (uint32_t) ((x - ts0) + y);
-                    if (k < s.nkey) kc[k]++;
-                }
-        }
+    for_keys([&](uint32_t k, uint32_t) { kc[k]++; });
     s.exp_ko.assign(s.nkey + 1, 0);
     for (uint32_t k = 0; k < s.nkey; k++) s.exp_ko[k + 1] = s.exp_ko[k] + kc[k];
-    // the step lists themselves (k_plists' output): key k's SBs, frames in phase order,
-    // raster order inside a frame
+    // the step lists themselves (k_plists' output): key k's SBs in that order
     s.stat_lists.assign(s.exp_ko[s.nkey], 0);
     std::vector<uint32_t> fill(s.exp_ko.begin(), s.exp_ko.end() - 1);
-    for (const Staged::DevPhase &P : s.dph)
-        for (int i : P.frames) {
-            const FrameBuild &fb = fbs[i];
-            for (int y = 0; y < fb.sb_rows; y++)
-                for (int x = 0; x < fb.sb_cols; x++) {
-                    int ts0;
-                    pl_tile_of(x, fb.sb_cols, fb.f->log2_tile_cols, &ts0);
-                    const uint32_t k = P.key0 + (uint32_t) ((x - ts0) + y);
-                    if (k < s.nkey) s.stat_lists[fill[k]++] = slot0[i] + (uint32_t) (y * fb.sb_cols + x);
-                }
-        }
+    for_keys([&](uint32_t k, uint32_t slot) { s.stat_lists[fill[k]++] = slot; });
     for (int k = 0; k < K_N; k++) s.alg_stat[k] = s.alg_base[k];
     const uint32_t H = s.host_lists;
     const int nph = (int) s.dph.size();
@@ -1235,35 +1275,20 @@ static void build_static_plan(vp9hip_ctx *c, const DevIn &in, const std::vector<
                 L.devr = 1;
                 s.launches.push_back(L);
             }
-            const int np = P.np, nlf = P.nlf;
-            const int nt = std::max(np, nlf ? nlf + PLF_LAG : 0);
-            for (int t = 0; t < nt; t++) {
-                const uint32_t k = P.key0 + (uint32_t) t;
-                const uint32_t pn = t < np && k < s.nkey ? kc[k] : 0u;
-                const int j = t - PLF_LAG;
-                const std::pair<uint32_t, uint32_t> lv = j >= 0 && j < nlf ? P.lf[j] : std::make_pair(0u, 0u);
-                if (!pn) {
-                    if (lv.second) s.launches.push_back(Launch{ K_LF, lv.first, lv.second, 0, g, ph, PART_LF, j });
-                    continue;
-                }
-                Launch L = { K_PLF, H + s.exp_ko[k], pn, 0, g, ph, PART_RECON, t };
-                L.off2 = lv.first;
-                L.n2 = lv.second;
-                if (t < (int) P.pred_bytes.size()) {
-                    s.alg_stat[K_PRED] -= P.pred_bytes[t];
-                    s.alg_stat[K_PLF] += P.pred_bytes[t];
-                }
-                if (lv.second) {
-                    s.alg_stat[K_LF] -= P.lf_bytes[j];
-                    s.alg_stat[K_PLF] += P.lf_bytes[j];
-                }
-                s.launches.push_back(L);
-            }
+            sched_fused_phase(P.np, P.nlf, 0,
+                [&](int t) {
+                    const uint32_t k = P.key0 + (uint32_t) t;
+                    return k < s.nkey ? SchedRange(H + s.exp_ko[k], kc[k]) : SchedRange(0u, 0u);
+                },
+                [&](int j) { return P.lf[j]; }, [](int, int) { return SchedRange(0u, 0u); },
+                [&](int fused, int step, SchedRange a, SchedRange b, const SchedRange *rr) {
+                    push_fused(s, P, s.alg_stat, g, ph, fused, step, a, b, rr);
+                });
         }
     s.stat = true;
 }
 
-static int stage_dev(vp9hip_ctx *c, const DevIn &in)
+static int stage_dev(vp9hip_ctx *c, const StageIn &in)
 {
     Staged &s = c->stg;
     const int n = in.n;
@@ -1284,19 +1309,20 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
     const uint32_t NS = slot0[n];
     s.nslots = NS;
     std::vector<uint32_t> slot_pos(NS, 0), seg_pre4, seg_sz, seg_pre1, gidx, hl;
-    s.dph.assign(in.NP, Staged::DevPhase());
+    const int NP = in.ph->NP;
+    s.dph.assign(NP, Staged::DevPhase());
     for (int i = 0; i < n; i++) s.dph[fbs[i].phase].frames.push_back(i);
     std::vector<PlanFrame> pf(n);
     memset(pf.data(), 0, pf.size() * sizeof(PlanFrame));
     uint32_t base = 0, segs = 0, keys = 0, sbs_before = 0;
     s.n_ctr = 0;
     s.lfr_ctr.clear();
-    for (int ph = 0; ph < in.NP; ph++) {
+    for (int ph = 0; ph < NP; ph++) {
         Staged::DevPhase &P = s.dph[ph];
         if (P.frames.empty()) continue;
-        P.group = ph / (in.maxpos + 1);
-        P.fused = (*in.res_fused)[ph];
-        P.levels = (*in.lvl_ph)[ph];
+        P.group = ph / (in.ph->maxpos + 1);
+        P.fused = in.ph->res_fused[ph];
+        P.levels = in.ph->lvl_ph[ph];
         P.lfr = in.lfr_any && (c->lf_rows > 1 || (int) P.frames.size() < LFR_MAX_FRAMES);
         P.all_lf = true;
         for (int i : P.frames) P.all_lf &= fbs[i].f->filter_level != 0;
@@ -1327,14 +1353,10 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
         for (int i : P.frames) {
             const FrameBuild &fb = fbs[i];
             const bool intra = fb.f->keyframe || fb.f->intraonly;
-            for (int y = 0; y < fb.sb_rows; y++)
-                for (int x = 0; x < fb.sb_cols; x++) {
-                    int ts0;
-                    pl_tile_of(x, fb.sb_cols, fb.f->log2_tile_cols, &ts0);
-                    const int d = (x - ts0) + y;
-                    slot_pos[slot0[i] + (uint32_t) (y * fb.sb_cols + x)] = P.seg_sz[P.fused ? d : 0]++;
-                    if (intra) P.pred_bytes[d] += sb_bytes(c, *fb.f, x, y);
-                }
+            for_sbs(fb.sb_cols, fb.sb_rows, fb.f->log2_tile_cols, [&](int x, int y, uint32_t slot, int d) {
+                slot_pos[slot0[i] + slot] = P.seg_sz[P.fused ? d : 0]++;
+                if (intra) P.pred_bytes[d] += sb_bytes(c, *fb.f, x, y);
+            });
         }
         uint32_t S = 0;
         for (uint32_t z : P.seg_sz) S += z;
@@ -1375,48 +1397,23 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
             P.lf[j] = { (uint32_t) hl.size(), (uint32_t) lfd[j].size() };
             hl.insert(hl.end(), lfd[j].begin(), lfd[j].end());
         }
-        // LF diagonals fused into the intra launches (the rest: k_lfr), as in stage()
-        const int nres = P.fused ? P.nseg : 0;
-        const int jlfr = std::max(0, std::max(P.np, nres - 1) - PLF_LAG);
-        P.nlf = P.lfr ? std::min(jlfr, nlfd) : nlfd;
+        // LF diagonals fused into the intra launches (the rest: k_lfr)
+        P.nlf = sched_fused_nlf(P.np, P.fused ? P.nseg : 0, nlfd, P.lfr);
         if (P.lfr) {
-            const int j0 = (!in.fuse || P.levels) ? 0 : P.nlf;
-            // task table: one task per (frame, SB row), rows-major, each naming the task of
-            // the row above and its SBs' LF records (= slots) left to right
-            std::vector<std::vector<uint32_t>> tid;
+            // task table over the filtered frames; an SB's LF record is its slot
             std::vector<int> lff;
-            int maxr = 0;
+            std::vector<std::pair<int, int>> dims;
             for (int i : P.frames)
-                if (fbs[i].f->filter_level) { lff.push_back(i); maxr = std::max(maxr, fbs[i].sb_rows); }
-            tid.resize(lff.size());
-            std::vector<uint32_t> recs, offs;
-            auto start = [&](int r) { return std::max(0, j0 - 2 * r); };
-            for (int r = 0; r < maxr; r++)
-                for (size_t k = 0; k < lff.size(); k++) {
-                    const FrameBuild &fb = fbs[lff[k]];
-                    if (r >= fb.sb_rows) continue;
-                    const int nc = fb.sb_cols, c0 = start(r);
-                    if (c0 >= nc) { tid[k].push_back(~0u); continue; }
-                    tid[k].push_back((uint32_t) offs.size());
-                    offs.push_back((uint32_t) recs.size());
-                    const uint32_t dep = r ? tid[k][r - 1] : ~0u;
-                    recs.push_back(dep);
-                    recs.push_back((uint32_t) nc);
-                    recs.push_back((uint32_t) c0);
-                    recs.push_back(dep != ~0u ? (uint32_t) std::max(0, start(r - 1) - 1) : 0u);
-                    for (int x = c0; x < nc; x++) recs.push_back(slot0[lff[k]] + (uint32_t) (r * nc + x));
-                    for (int x = c0; x < nc; x++) P.lfr_bytes += 2.0 * sb_bytes(c, *fb.f, x, r);
-                }
-            if (!offs.empty()) {
-                const uint32_t nt = (uint32_t) offs.size();
-                for (uint32_t &o : offs) o += nt;
-                P.lfr_off = (uint32_t) hl.size();
-                P.lfr_n = nt;
-                hl.insert(hl.end(), offs.begin(), offs.end());
-                hl.insert(hl.end(), recs.begin(), recs.end());
+                if (fbs[i].f->filter_level) { lff.push_back(i); dims.push_back({ fbs[i].sb_rows, fbs[i].sb_cols }); }
+            P.lfr_off = (uint32_t) hl.size();
+            P.lfr_n = sched_lfr_tasks(dims, (!in.fuse || P.levels) ? 0 : P.nlf, [&](int k, int r, int x) {
+                P.lfr_bytes += 2.0 * sb_bytes(c, *fbs[lff[k]].f, x, r);
+                return slot0[lff[k]] + (uint32_t) (r * fbs[lff[k]].sb_cols + x);
+            }, hl);
+            if (P.lfr_n) {
                 P.lfr_ctr = (int) s.n_ctr;
                 s.lfr_ctr.push_back(s.n_ctr);
-                s.n_ctr += 4 + nt;         // ticket, done, timeouts, spin; progress per task
+                s.n_ctr += 4 + P.lfr_n;    // ticket, done, timeouts, spin; progress per task
             } else {
                 P.lfr = false;
             }
@@ -1522,35 +1519,10 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
     s.cap_mcs = (uint32_t) (nmc + 1);
     s.scan_bytes = std::max<size_t>(vp9hip_plan_scan_bytes(std::max<uint64_t>(nb, s.ncnt) + 1), 256);
     s.o_scan = o; o = al(o + s.scan_bytes);
-    if (o > s.arena_cap) {
-        if (s.arena) hipFree(s.arena);
-        s.arena = nullptr;
-        s.arena_cap = 0;
-        if (hipMalloc(&s.arena, o) != hipSuccess) return VP9HIP_ENOMEM;
-        s.arena_cap = o;
-    }
-    if (up > s.pinned_cap) {
-        if (s.pinned) hipHostFree(s.pinned);
-        s.pinned = nullptr;
-        s.pinned_cap = 0;
-        if (hipHostMalloc((void **) &s.pinned, up, hipHostMallocDefault) != hipSuccess) return VP9HIP_ENOMEM;
-        s.pinned_cap = up;
-    }
-    if (s.summary_words * 4 > s.summary_cap) {
-        if (s.summary_h) hipHostFree(s.summary_h);
-        s.summary_h = nullptr;
-        s.summary_cap = 0;
-        if (hipHostMalloc((void **) &s.summary_h, s.summary_words * 4, hipHostMallocDefault) != hipSuccess) return VP9HIP_ENOMEM;
-        s.summary_cap = s.summary_words * 4;
-    }
-    const size_t rbytes = ((size_t) NS + 1) * s.rcap * 32;
-    if (rbytes > s.resid_cap) {
-        if (s.resid) hipFree(s.resid);
-        s.resid = nullptr;
-        s.resid_cap = 0;
-        if (hipMalloc(&s.resid, rbytes) != hipSuccess) return VP9HIP_ENOMEM;
-        s.resid_cap = rbytes;
-    }
+    if (grow(s.arena, s.arena_cap, o) || grow(s.pinned, s.pinned_cap, up, true) ||
+        grow(s.summary_h, s.summary_cap, s.summary_words * 4, true) ||
+        grow(s.resid, s.resid_cap, ((size_t) NS + 1) * s.rcap * 32))
+        return VP9HIP_ENOMEM;
     uint8_t *img = s.pinned;
     memcpy(img + s.o_frames, s.frames.data(), n * sizeof(FrameDesc));
     memcpy(img + s.o_pf, pf.data(), n * sizeof(PlanFrame));
@@ -1572,9 +1544,7 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
             uint8_t *mp = c->mot[in.out_bufs[i]];
             // a buffer the batch writes more than once keeps the field of its last writer: the
             // launch runs all frames' workgroups at once, so an earlier writer exports nothing
-            bool last = true;
-            for (int j = i + 1; j < n && last; j++) last = in.out_bufs[j] != in.out_bufs[i];
-            mf[i].blk0 = pf[i].blk0; mf[i].nblk = last ? pf[i].nblk : 0;
+            mf[i].blk0 = pf[i].blk0; mf[i].nblk = last_writer(in.out_bufs, n, i) ? pf[i].nblk : 0;
             mf[i].cols8 = (uint32_t) fbs[i].cols; mf[i].rows8 = (uint32_t) fbs[i].rows;
             mf[i].mv = (uint64_t) mp;
             mf[i].info = (uint64_t) (mp + (size_t) c->mot_pitch * c->mot_rows * 8);
@@ -1588,8 +1558,7 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
         for (int i = 0; i < n; i++) {
             uint8_t *rp = c->res[in.out_bufs[i]];
             // as for motion: of several frames writing one buffer only the last exports
-            bool last = true;
-            for (int j = i + 1; j < n && last; j++) last = in.out_bufs[j] != in.out_bufs[i];
+            const bool last = last_writer(in.out_bufs, n, i);
             memset(&rf[i], 0, sizeof(rf[i]));
             for (int p = 0; p < 3; p++) rf[i].plane[p] = (uint64_t) (rp + c->plane_off[p] / c->bypp * 2);
             rf[i].pitch[0] = (uint32_t) c->pitch[0]; rf[i].pitch[1] = (uint32_t) c->pitch[1];
@@ -1603,23 +1572,13 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
             s.res_max_sb = std::max(s.res_max_sb, (int) rf[i].nsb);
         }
     }
-    {   // packets: blocks, eobs, coefficients (frames copied in parallel)
-        std::atomic<int> next(0);
-        auto worker = [&]() {
-            for (int i; (i = next.fetch_add(1)) < n;) {
-                const vp9h_frame *f = &pkts[i];
-                const PlanFrame &F = pf[i];
-                if (f->nblocks) memcpy(img + s.o_blocks + (size_t) F.blk0 * sizeof(vp9h_block), f->blocks, (size_t) f->nblocks * sizeof(vp9h_block));
-                if (f->neobs) memcpy(img + s.o_eobs + (size_t) F.eob0 * 2, f->eobs, (size_t) f->neobs * 2);
-                if (f->ncoefs) memcpy(img + s.o_coefs + (size_t) F.coef0 * in.csz, f->coefs, (size_t) f->ncoefs * in.csz);
-            }
-        };
-        const int nt = std::min(n, c->host_threads);
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nt; t++) pool.emplace_back(worker);
-        worker();
-        for (auto &t : pool) t.join();
-    }
+    for_frames(c, n, [&](int i) {   // packets: blocks, eobs, coefficients (frames copied in parallel)
+        const vp9h_frame *f = &pkts[i];
+        const PlanFrame &F = pf[i];
+        if (f->nblocks) memcpy(img + s.o_blocks + (size_t) F.blk0 * sizeof(vp9h_block), f->blocks, (size_t) f->nblocks * sizeof(vp9h_block));
+        if (f->neobs) memcpy(img + s.o_eobs + (size_t) F.eob0 * 2, f->eobs, (size_t) f->neobs * 2);
+        if (f->ncoefs) memcpy(img + s.o_coefs + (size_t) F.coef0 * in.csz, f->coefs, (size_t) f->ncoefs * in.csz);
+    });
     if (c->test_reject) {   // test hook (vp9hip_test_hooks): the k-th batch the context stages
         // gets an intra block with a mode the device planner rejects as the first block of its
         // frame f, so the front ends' handling of a rejected frame can be tested from real
@@ -1651,8 +1610,8 @@ static int stage_dev(vp9hip_ctx *c, const DevIn &in)
 // The per-frame verdicts of a rejected batch from its summary: frames whose status bits are
 // set are rejected, the others get `good` (0: reconstructed, EAGAIN: not run). A status that
 // names no frame (PLS_BOUNDS: a shared buffer's capacity; PLS_TOTAL: a frame's totals shift
-// the batch-wide scans) rejects every frame. Returns the number rejected.
-static int frame_verdicts(Staged &s, const uint32_t *sm, int good)
+// the batch-wide scans) rejects every frame. Says how many were rejected.
+static void frame_verdicts(Staged &s, const uint32_t *sm, int good)
 {
     const uint32_t *fbad = sm + 1 + s.n_gidx + s.nkey + 1 + 4 * (size_t) s.nframes;
     const bool all = (sm[0] & (PLS_BOUNDS | PLS_TOTAL)) != 0;
@@ -1660,7 +1619,29 @@ static int frame_verdicts(Staged &s, const uint32_t *sm, int good)
     int nbad = 0;
     for (int i = 0; i < s.nframes; i++)
         if (all || fbad[i]) { s.fstat[i] = VP9HIP_EINVALIDDATA; nbad++; }
-    return nbad;
+    fprintf(stderr, "vp9hip: %d of %d frames rejected by the device planner (status 0x%x, bounds 0x%x)\n", nbad,
+            s.nframes, sm[0], sm[s.summary_words - 1]);
+}
+
+// The algorithmic bytes of a run: `base` (header-derived), the planner's own (the packet's blocks and
+// eobs) and the summary's per-frame residual and MC totals; fused frames' residuals count in k_plf.
+static void summary_bytes(Staged &s, const double *base)
+{
+    const uint32_t *fb32 = s.summary_h + 1 + s.n_gidx + s.nkey + 1;
+    auto fbytes = [&](int i, int k) {
+        return (double) ((uint64_t) fb32[2 * (2 * i + k)] | (uint64_t) fb32[2 * (2 * i + k) + 1] << 32);
+    };
+    for (int k = 0; k < K_N; k++) s.alg_bytes[k] = base[k];
+    s.alg_bytes[K_PLAN] = (double) s.nblk * sizeof(vp9h_block) + (double) s.neob * 2;
+    for (int i = 0; i < s.nframes; i++) {
+        s.alg_bytes[K_RESID] += fbytes(i, 0);
+        s.alg_bytes[K_MC] += fbytes(i, 1);
+        if (s.frame_fused[i]) {
+            const double b = s.frame_res_bytes[i] + fbytes(i, 0);
+            s.alg_bytes[K_RESID] -= b;
+            s.alg_bytes[K_PLF] += b;
+        }
+    }
 }
 
 // A static-plan batch's summary, once its run is complete (the caller waited for it):
@@ -1680,9 +1661,7 @@ static int finish_summary(vp9hip_ctx *c, Staged &s)
     if (sm[0]) {
         // k_pguard neutralised the rejected frames only (the whole batch if no frame is named):
         // the others ran as if alone
-        const int nbad = frame_verdicts(s, sm, 0);
-        fprintf(stderr, "vp9hip: %d of %d frames rejected by the device planner (status 0x%x, bounds 0x%x)\n", nbad,
-                s.nframes, sm[0], sm[s.summary_words - 1]);
+        frame_verdicts(s, sm, 0);
         s.status = VP9HIP_EINVALIDDATA;
         return s.status;
     }
@@ -1698,13 +1677,7 @@ static int finish_summary(vp9hip_ctx *c, Staged &s)
                 return s.status;
             }
         }
-    const uint32_t *ko = sm + 1 + s.n_gidx, *fb32 = ko + s.nkey + 1;
-    for (int k = 0; k < K_N; k++) s.alg_bytes[k] = s.alg_stat[k];
-    s.alg_bytes[K_PLAN] = (double) s.nblk * sizeof(vp9h_block) + (double) s.neob * 2;
-    for (int i = 0; i < s.nframes; i++) {
-        s.alg_bytes[K_RESID] += (double) ((uint64_t) fb32[4 * i] | (uint64_t) fb32[4 * i + 1] << 32);
-        s.alg_bytes[K_MC] += (double) ((uint64_t) fb32[4 * i + 2] | (uint64_t) fb32[4 * i + 3] << 32);
-    }
+    summary_bytes(s, s.alg_stat);
     return 0;
 }
 
@@ -1837,27 +1810,11 @@ static int plan_dev(vp9hip_ctx *c)
     const uint32_t *sm = s.summary_h;
     if (sm[0]) {                                              // the packets are inconsistent (PLS_*)
         // nothing was launched: the frames the planner did not reject are valid, not run
-        const int nbad = frame_verdicts(s, sm, VP9HIP_EAGAIN);
-        fprintf(stderr, "vp9hip: %d of %d frames rejected by the device planner (status 0x%x, bounds 0x%x)\n", nbad,
-                s.nframes, sm[0], sm[s.summary_words - 1]);
+        frame_verdicts(s, sm, VP9HIP_EAGAIN);
         return VP9HIP_EINVALIDDATA;
     }
-    const uint32_t *gv = sm + 1, *ko = sm + 1 + s.n_gidx, *fb32 = ko + s.nkey + 1;
-    auto fbytes = [&](int i, int k) {
-        return (double) ((uint64_t) fb32[2 * (2 * i + k)] | (uint64_t) fb32[2 * (2 * i + k) + 1] << 32);
-    };
-    for (int k = 0; k < K_N; k++) s.alg_bytes[k] = s.alg_base[k];
-    // the planner's algorithmic bytes: the packet it plans from (blocks and eobs)
-    s.alg_bytes[K_PLAN] = (double) s.nblk * sizeof(vp9h_block) + (double) s.neob * 2;
-    for (int i = 0; i < s.nframes; i++) {
-        s.alg_bytes[K_RESID] += fbytes(i, 0);
-        s.alg_bytes[K_MC] += fbytes(i, 1);
-        if (s.frame_fused[i]) {                               // residuals inside the k_plf launches
-            const double b = s.frame_res_bytes[i] + fbytes(i, 0);
-            s.alg_bytes[K_RESID] -= b;
-            s.alg_bytes[K_PLF] += b;
-        }
-    }
+    const uint32_t *gv = sm + 1, *ko = sm + 1 + s.n_gidx;
+    summary_bytes(s, s.alg_base);
     const uint32_t H = s.host_lists;
     const int nph = (int) s.dph.size();
     for (int g = 0; g < s.ngroups; g++)
@@ -1926,132 +1883,35 @@ static int plan_dev(vp9hip_ctx *c)
                         if (P.lf[j].second) push(K_LF, P.lf[j].first, P.lf[j].second, 0, PART_LF, (int) j);
                 continue;
             }
-            // fused: launch t = intra diagonal t + LF diagonal t - PLF_LAG + residuals of t + 1
-            const int np = P.np, nres = P.fused ? P.nseg : 0, nlf = P.nlf;
-            const int nt = std::max(std::max(np, nlf ? nlf + PLF_LAG : 0), nres - 1);
-            for (int t = -1; t < nt; t++) {
-                const std::pair<uint32_t, uint32_t> pv = t >= 0 && t < np ? step(t) : std::make_pair(0u, 0u);
-                const int j = t - PLF_LAG;
-                const std::pair<uint32_t, uint32_t> lv = j >= 0 && j < nlf ? P.lf[j] : std::make_pair(0u, 0u);
-                bool res = false;
-                for (int k = 0; t + 1 < nres && k < 5; k++) res |= rr(t + 1, k).second > 0;
-                if (!pv.second && !res) {
-                    if (lv.second) push(K_LF, lv.first, lv.second, 0, PART_LF, j);
-                    continue;
-                }
-                Launch L = { K_PLF, pv.first, pv.second, 0, g, ph, PART_RECON, t };
-                L.off2 = lv.first;
-                L.n2 = lv.second;
-                if (pv.second && t < (int) P.pred_bytes.size()) {
-                    s.alg_bytes[K_PRED] -= P.pred_bytes[t];
-                    s.alg_bytes[K_PLF] += P.pred_bytes[t];
-                }
-                if (lv.second) {
-                    s.alg_bytes[K_LF] -= P.lf_bytes[j];
-                    s.alg_bytes[K_PLF] += P.lf_bytes[j];
-                }
-                for (int k = 0; res && k < 5; k++) { L.roff[k] = rr(t + 1, k).first; L.rn[k] = rr(t + 1, k).second; }
-                s.launches.push_back(L);
-            }
+            sched_fused_phase(P.np, P.nlf, P.fused ? P.nseg : 0, step, [&](int j) { return P.lf[j]; }, rr,
+                              [&](int fused, int t, SchedRange a, SchedRange b, const SchedRange *r5) {
+                                  push_fused(s, P, s.alg_bytes, g, ph, fused, t, a, b, r5);
+                              });
             lfr();
         }
     s.planned = true;
     return 0;
 }
 
-static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bufs, const int *ref_bufs /*n*3 or null*/,
-                 int tile_lo = 0, int tile_hi = 64, int max_groups = 0, bool tiled = false)
-{
-    // fused intra + LF launches need the LF of a phase in the same launch sequence as its
-    // reconstruction (not for tile-sharded batches: recon, exchange, then LF)
-    const bool fuse = c->fuse_plf && !tiled;
-    // the loop filter of a phase as one row-pipelined k_lfr launch (after the phase's
-    // reconstruction) instead of x + 2y diagonal launches
-    const bool lfr_any = c->lf_rows > 0 && !tiled;
-    // VP9HIP_STAGE_TRACE=1: host time of the staging steps on stderr
-    const bool stage_trace = c->stage_trace;
-    double st_ms[6] = { 0, 0, 0, 0, 0, 0 };
-    auto st_t0 = std::chrono::steady_clock::now();
-#define STAGE_T(k) do { auto t_ = std::chrono::steady_clock::now(); \
-        st_ms[k] = std::chrono::duration<double, std::milli>(t_ - st_t0).count(); st_t0 = t_; } while (0)
-    if (!c || !pkts || n <= 0 || !out_bufs) return VP9HIP_EINVAL;
-    if (c->bufs.empty()) return VP9HIP_EINVAL;
-    hipSetDevice(c->dev);
-    // this slot's previous batch may still read the arena (the other slot's work may go on)
-    if (c->stg.done_ev) HIPCHK(hipEventSynchronize(c->stg.done_ev));
-    if (c->stg.up_ev) HIPCHK(hipEventSynchronize(c->stg.up_ev));
-    Staged &s = c->stg;
-    if (s.graph) { hipGraphExecDestroy(s.graph); s.graph = nullptr; }
-    s.frames.clear(); s.sbs.clear(); s.pjobs.clear(); s.passes.clear(); s.lfs.clear(); s.mcs.clear();
-    s.wgs.clear(); s.sbh.clear(); s.sbjobs.clear(); s.jdep0.clear(); s.jdeps.clear();
-    s.rjobs.clear(); s.resid16 = 0;
-    s.rbucket.clear();
-    s.lists.clear(); s.launches.clear(); s.coefs.clear(); s.n_ctr = 0; s.lfr_ctr.clear();
-    s.frame_phase.assign(n, 0); s.frame_log2.assign(n, 0);
-    s.tile_lo = tile_lo; s.tile_hi = tile_hi;
-    s.stat = false;
-    s.summary_pending = false;
-    s.status = 0;
-    s.fstat.assign(n, 0);
-    for (int k = 0; k < K_N; k++) s.alg_bytes[k] = 0;
-    s.ready = false;
+// VP9HIP_STAGE_TRACE=1: host time of the staging steps
+struct StageClock {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double ms[6] = { 0, 0, 0, 0, 0, 0 };
+    void lap(int k)
+    {
+        const auto t = std::chrono::steady_clock::now();
+        ms[k] = std::chrono::duration<double, std::milli>(t - t0).count();
+        t0 = t;
+    }
+};
 
+// Staging, per frame (sequential, cheap): validation against the context, frame descriptor, reference
+// scaling, FrameBuild and header-derived algorithmic bytes; then the intra frames' edge columns.
+static int stage_frames(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bufs, const int *ref_bufs,
+                        const SchedPhases &bp, std::vector<FrameBuild> &fbs)
+{
+    Staged &s = c->stg;
     const int csz = c->hb ? 4 : 2;
-    init_nz();
-    // Frame dependencies inside the batch: an inter frame follows the frames whose output
-    // it references, and a frame overwriting a buffer follows every earlier frame that
-    // reads or writes that buffer. Dependent frames form chains; chains are spread over G
-    // stream groups, and within a group frames of equal chain position ("phase") are
-    // interleaved in every launch (a keyframe batch is one phase per group).
-    std::vector<int> pos(n, 0), comp(n);
-    for (int i = 0; i < n; i++) comp[i] = i;
-    std::function<int(int)> find = [&](int x) { return comp[x] == x ? x : comp[x] = find(comp[x]); };
-    for (int i = 0; i < n; i++) {
-        const vp9h_frame *f = &pkts[i];
-        const bool inter = !(f->keyframe || f->intraonly);
-        if (inter && !ref_bufs) return VP9HIP_EINVAL;
-        for (int j = 0; j < i; j++) {
-            bool dep = out_bufs[j] == out_bufs[i];
-            for (int r = 0; r < 3 && !dep; r++) {
-                if (inter && ref_bufs[i * 3 + r] == out_bufs[j]) dep = true;
-                const bool jinter = !(pkts[j].keyframe || pkts[j].intraonly);
-                if (jinter && ref_bufs[j * 3 + r] == out_bufs[i]) dep = true;
-            }
-            if (dep) { pos[i] = std::max(pos[i], pos[j] + 1); comp[find(i)] = find(j); }
-        }
-    }
-    std::vector<int> roots;
-    for (int i = 0; i < n; i++) if (find(i) == i) roots.push_back(i);
-    // G groups: as many as allowed, but chains split evenly (unless there are many: 4 GOP
-    // chains over 3 streams run 2/1/1 and the pair sets the time)
-    const int nroots = (int) roots.size();
-    int G = std::max(1, std::min<int>(max_groups > 0 ? max_groups : c->max_groups, nroots));
-    while (G > 1 && nroots % G && nroots < 16 * G) G--;
-    s.ngroups = G;
-    std::vector<int> grp(n);
-    for (int i = 0; i < n; i++)
-        grp[i] = (int) (std::lower_bound(roots.begin(), roots.end(), find(i)) - roots.begin()) % G;
-    int maxpos = 0;
-    for (int i = 0; i < n; i++) maxpos = std::max(maxpos, pos[i]);
-    const int NP = G * (maxpos + 1);                   // phase id = g * (maxpos + 1) + pos
-    s.nphases = NP;
-    // residuals fused into the wavefront launches: per phase (RES_FUSE_MAX_FRAMES)
-    std::vector<int> phase_n(NP, 0);
-    for (int i = 0; i < n; i++) phase_n[grp[i] * (maxpos + 1) + pos[i]]++;
-    std::vector<char> res_fused(NP);
-    for (int ph = 0; ph < NP; ph++) res_fused[ph] = fuse && phase_n[ph] < RES_FUSE_MAX_FRAMES;
-    // level-scheduled phases (inter frames of k_lfr phases): MC, all residuals, the intra
-    // SBs by dependency level (k_pred), then the whole loop filter as one k_lfr launch
-    std::vector<char> lvl_ph(NP, 0);
-    if (lfr_any && c->level_sched) {
-        for (int ph = 0; ph < NP; ph++) lvl_ph[ph] = c->lf_rows > 1 || phase_n[ph] < LFR_MAX_FRAMES;
-        for (int i = 0; i < n; i++)
-            if (pkts[i].keyframe || pkts[i].intraonly) lvl_ph[grp[i] * (maxpos + 1) + pos[i]] = 0;
-        for (int ph = 0; ph < NP; ph++) if (lvl_ph[ph]) res_fused[ph] = false;
-    }
-    // per frame: validate, frame descriptor, reference scaling (sequential, cheap)
-    std::vector<FrameBuild> fbs(n);
-    std::vector<size_t> coef_off(n + 1, 0);
     uint64_t coef_base = 0;
     uint64_t edge_sbs = 0;                  // SBs of the batch's intra frames (FrameDesc.edge)
     for (int i = 0; i < n; i++) {
@@ -2121,13 +1981,12 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
         fb.ss_h = c->ss_h; fb.ss_v = c->ss_v; fb.coef_size = csz;
         fb.pitch[0] = c->pitch[0]; fb.pitch[1] = c->pitch[1];
         fb.coef_base = coef_base;
-        fb.phase = grp[i] * (maxpos + 1) + pos[i];
-        fb.tile_lo = tile_lo; fb.tile_hi = tile_hi;
-        fb.by_diag = res_fused[fb.phase];
-        fb.levels = lvl_ph[fb.phase];
+        fb.phase = bp.phase(i);
+        fb.tile_lo = s.tile_lo; fb.tile_hi = s.tile_hi;
+        fb.by_diag = bp.res_fused[fb.phase];
+        fb.levels = bp.lvl_ph[fb.phase];
         s.frame_phase[i] = fb.phase;
         s.frame_log2[i] = f->log2_tile_cols;
-        coef_off[i + 1] = coef_off[i] + (size_t) f->ncoefs * csz;
         coef_base += f->ncoefs;
         if (coef_base > 0xffffffffull) return VP9HIP_ENOMEM;
         // algorithmic bytes: reconstruction reads C and writes P (k_resid
@@ -2140,94 +1999,57 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
     }
     // the intra frames' SB right columns: written by each SB's intra workgroup, read by the
     // SB to its right in place of a column of one-pixel frame rows (128 scattered lines)
-    {
-        const size_t eb = (size_t) edge_sbs * EDGE_PIX * c->bypp + 256;
-        // only the 4:2:0 tile loader reads the edge columns (the other chroma formats load
-        // their left column from frame rows): no buffer written and never read for those
-        const bool edge_off = !c->edge || !(c->ss_h && c->ss_v);
-        if (edge_sbs && !edge_off && eb > s.edge_cap) {
-            if (s.edge) hipFree(s.edge);
-            s.edge = nullptr;
-            s.edge_cap = 0;
-            if (hipMalloc(&s.edge, eb) != hipSuccess) return VP9HIP_ENOMEM;
-            s.edge_cap = eb;
-        }
-        for (FrameDesc &fd : s.frames)
-            fd.edge = fd.edge && !edge_off ? (uint64_t) (s.edge + (size_t) (fd.edge - 1) * EDGE_PIX * c->bypp) : 0;
-    }
+    // only the 4:2:0 tile loader reads the edge columns (the other chroma formats load
+    // their left column from frame rows): no buffer written and never read for those
+    const bool edge_off = !c->edge || !(c->ss_h && c->ss_v);
+    if (edge_sbs && !edge_off && grow(s.edge, s.edge_cap, (size_t) edge_sbs * EDGE_PIX * c->bypp + 256)) return VP9HIP_ENOMEM;
+    for (FrameDesc &fd : s.frames)
+        fd.edge = fd.edge && !edge_off ? (uint64_t) (s.edge + (size_t) (fd.edge - 1) * EDGE_PIX * c->bypp) : 0;
+    return 0;
+}
 
-    STAGE_T(0);
-    // the buffers this batch writes and reads, and which other slots' batches touch them
+// Staging: the buffers this batch writes and reads, and which other slots' batches touch them.
+static void slot_deps(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bufs, const int *ref_bufs)
+{
+    Staged &s = c->stg;
     s.wr.assign(out_bufs, out_bufs + n);
     s.rd.clear();
     for (int i = 0; i < n && ref_bufs; i++)
         if (!(pkts[i].keyframe || pkts[i].intraonly))
             for (int r = 0; r < 3; r++) s.rd.push_back(ref_bufs[i * 3 + r]);
     for (auto *v : { &s.wr, &s.rd }) { std::sort(v->begin(), v->end()); v->erase(std::unique(v->begin(), v->end()), v->end()); }
-    {
-        auto meet = [](const std::vector<int> &a, const std::vector<int> &b) {
-            for (size_t i = 0, j = 0; i < a.size() && j < b.size();) {
-                if (a[i] == b[j]) return true;
-                if (a[i] < b[j]) i++; else j++;
-            }
-            return false;
-        };
-        s.dep_mask = 0;
-        for (int k = 0; k < MAX_SLOTS; k++) {
-            if (k == c->slot) continue;
-            const Staged &o = c->sl[k];
-            if (o.ready && (meet(s.wr, o.wr) || meet(s.wr, o.rd) || meet(s.rd, o.wr))) s.dep_mask |= 1u << k;
+    auto meet = [](const std::vector<int> &a, const std::vector<int> &b) {
+        for (size_t i = 0, j = 0; i < a.size() && j < b.size();) {
+            if (a[i] == b[j]) return true;
+            if (a[i] < b[j]) i++; else j++;
         }
+        return false;
+    };
+    s.dep_mask = 0;
+    for (int k = 0; k < MAX_SLOTS; k++) {
+        if (k == c->slot) continue;
+        const Staged &o = c->sl[k];
+        if (o.ready && (meet(s.wr, o.wr) || meet(s.wr, o.rd) || meet(s.rd, o.wr))) s.dep_mask |= 1u << k;
     }
-    s.dev = false;
-    s.motion = false;
-    s.residual = false;
-    if (!c->host_plan) {
-        DevIn in;
-        in.pkts = pkts; in.n = n; in.G = G; in.maxpos = maxpos; in.NP = NP; in.csz = csz;
-        in.fbs = &fbs; in.res_fused = &res_fused; in.lvl_ph = &lvl_ph;
-        in.fuse = fuse; in.lfr_any = lfr_any;
-        in.out_bufs = out_bufs;
-        in.motion = (c->export_flags & VP9HIP_EXPORT_MOTION) && !tiled;
-        // the buffers' fields: the frames' grids once the batch ran; none for a sharded batch
-        for (int i = 0; i < n && !c->mot_gwh.empty(); i++) c->mot_gwh[out_bufs[i]] = { 0, 0 };
-        in.residual = (c->export_flags & VP9HIP_EXPORT_RESIDUAL) && !tiled;
-        for (int i = 0; i < n && !c->res_wh.empty(); i++) c->res_wh[out_bufs[i]] = { 0, 0 };
-        const int r = stage_dev(c, in);
-        if (r) return r;
-        s.mot_buf.clear(); s.mot_grid.clear();
-        for (int i = 0; i < n && in.motion; i++) {      // in frame order: a buffer's last writer wins
-            s.mot_buf.push_back(out_bufs[i]);
-            s.mot_grid.push_back({ 2 * fbs[i].cols, 2 * fbs[i].rows });
-            c->mot_gwh[out_bufs[i]] = s.mot_grid.back();
-        }
-        s.res_buf.clear(); s.res_size.clear();
-        for (int i = 0; i < n && in.residual; i++) {
-            s.res_buf.push_back(out_bufs[i]);
-            s.res_size.push_back({ pkts[i].width, pkts[i].height });
-            c->res_wh[out_bufs[i]] = s.res_size.back();
-        }
-        STAGE_T(1);
-        if (stage_trace) fprintf(stderr, "vp9hip stage (device plan): %d frames: setup %.1f upload %.1f ms\n", n, st_ms[0], st_ms[1]);
-        return 0;
-    }
+}
+
+// Host-planned batches (VP9HIP_HOST_PLAN=1, beside stage_dev): every frame's work planned on
+// host threads, merged into one arena image with the launch list, and uploaded.
+static int stage_host(vp9hip_ctx *c, const StageIn &in, StageClock &clk)
+{
+    Staged &s = c->stg;
+    const vp9h_frame *pkts = in.pkts;
+    const int n = in.n, csz = in.csz, G = in.ph->G, maxpos = in.ph->maxpos, NP = in.ph->NP;
+    const std::vector<FrameBuild> &fbs = *in.fbs;
+    const std::vector<char> &res_fused = in.ph->res_fused, &lvl_ph = in.ph->lvl_ph;
+    const bool fuse = in.fuse, lfr_any = in.lfr_any;
+    std::vector<size_t> coef_off(n + 1, 0);               // byte offsets of the frames' coefficients
+    for (int i = 0; i < n; i++) coef_off[i + 1] = coef_off[i] + (size_t) pkts[i].ncoefs * csz;
     // work planning of every frame (independent), on host threads: jobs, dependency
     // levels and pass packing, LF programs, MC units, coefficient copy
     std::vector<FramePlan> plans(n);
-    {
-        std::atomic<int> next(0);
-        auto worker = [&]() {
-            for (int i; (i = next.fetch_add(1)) < n;) {
-                plans[i].err = plan_frame(fbs[i], plans[i]);
-            }
-        };
-        const int nt = std::min(n, c->host_threads);
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nt; t++) pool.emplace_back(worker);
-        worker();
-        for (auto &t : pool) t.join();
-    }
-    STAGE_T(1);
+    for_frames(c, n, [&](int i) { plans[i].err = plan_frame(fbs[i], plans[i]); });
+    clk.lap(1);
     // merge: batch offsets of every frame's records (prefix sums in frame order; residual
     // jobs in launch order: group, phase, tx code, txtp, frame). The records themselves
     // are written, with their index fixups, straight into the pinned arena image below.
@@ -2294,7 +2116,7 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
         for (size_t d = 0; d < fp.lsteps.size(); d++)
             for (uint32_t li : fp.lsteps[d]) lsteps[ph][d].push_back(li + off[i].lf);
     }
-    STAGE_T(2);
+    clk.lap(2);
     // launch schedule per group, phases in chain order: MC, residuals by (tx code, txtp),
     // the intra SB wavefront, the LF wavefront; inter residual pixels are algorithmic
     // reads + writes of k_resid
@@ -2314,60 +2136,34 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
             };
             const std::vector<std::vector<uint32_t>> &wls = wsteps[ph];   // one workgroup per SB
             const bool lfr = lfr_any && (c->lf_rows > 1 || (int) phase_frames[ph].size() < LFR_MAX_FRAMES);
-            // k_lfr task table of the phase: one task per (frame, SB row), rows-major, each
-            // naming the task of the row above (dep) and its SBs' LF records left to right
-            // j0: LF diagonals x + 2y < j0 ran in earlier (fused) launches
+            // k_lfr launch of the phase over the LF diagonals x + 2y >= j0 (the others ran in
+            // earlier, fused launches): its task table in the lists; a frame's LF records must
+            // cover its SB grid
             auto add_lfr = [&](int j0) {
-                std::vector<std::vector<std::vector<uint32_t>>> grid;      // per frame: [row][col]
-                int maxr = 0;
+                std::vector<std::pair<int, int>> dims;                     // per filtered frame: rows, columns
+                std::vector<std::vector<uint32_t>> grid;                   // its LF record of [row * columns + col]
                 for (int i : phase_frames[ph]) {
                     const std::vector<LFRec> &lf = plans[i].s.lfs;
                     if (lf.empty()) continue;
                     int nr = 0, nc = 0;
                     for (const LFRec &r : lf) { nr = std::max(nr, r.sby + 1); nc = std::max(nc, r.sbx + 1); }
-                    std::vector<std::vector<uint32_t>> gr(nr, std::vector<uint32_t>(nc, ~0u));
-                    for (size_t k = 0; k < lf.size(); k++) gr[lf[k].sby][lf[k].sbx] = off[i].lf + (uint32_t) k;
-                    for (auto &row : gr)
-                        for (uint32_t v : row)
-                            if (v == ~0u) return VP9HIP_EINVALIDDATA;
+                    std::vector<uint32_t> gr((size_t) nr * nc, ~0u);
+                    for (size_t k = 0; k < lf.size(); k++) gr[(size_t) lf[k].sby * nc + lf[k].sbx] = off[i].lf + (uint32_t) k;
+                    if (std::find(gr.begin(), gr.end(), ~0u) != gr.end()) return VP9HIP_EINVALIDDATA;
+                    dims.push_back({ nr, nc });
                     grid.push_back(std::move(gr));
-                    maxr = std::max(maxr, nr);
                 }
-                if (grid.empty()) return 0;
-                std::vector<std::vector<uint32_t>> tid(grid.size());   // task of (frame, row) or ~0u
-                std::vector<uint32_t> recs;
-                std::vector<uint32_t> offs;
-                auto start = [&](int r) { return std::max(0, j0 - 2 * r); };
-                for (int r = 0; r < maxr; r++)
-                    for (size_t f = 0; f < grid.size(); f++) {
-                        if (r >= (int) grid[f].size()) continue;
-                        const int nc = (int) grid[f][r].size(), c0 = start(r);
-                        if (c0 >= nc) { tid[f].push_back(~0u); continue; }
-                        tid[f].push_back((uint32_t) offs.size());
-                        offs.push_back((uint32_t) recs.size());
-                        const uint32_t dep = r ? tid[f][r - 1] : ~0u;
-                        recs.push_back(dep);
-                        recs.push_back((uint32_t) nc);
-                        recs.push_back((uint32_t) c0);
-                        recs.push_back(dep != ~0u ? (uint32_t) std::max(0, start(r - 1) - 1) : 0u);
-                        recs.insert(recs.end(), grid[f][r].begin() + c0, grid[f][r].end());
-                    }
-                if (offs.empty()) return 0;
-                const uint32_t nt = (uint32_t) offs.size();
-                Launch L = { K_LFR, (uint32_t) s.lists.size(), nt, (int) s.n_ctr, g, ph, PART_LF, 0 };
-                for (uint32_t &o : offs) o += nt;
-                s.lists.insert(s.lists.end(), offs.begin(), offs.end());
-                s.lists.insert(s.lists.end(), recs.begin(), recs.end());
+                Launch L = { K_LFR, (uint32_t) s.lists.size(), 0, (int) s.n_ctr, g, ph, PART_LF, 0 };
+                L.n = sched_lfr_tasks(dims, j0, [&](int f, int r, int x) {
+                    const uint32_t li = grid[f][(size_t) r * dims[f].second + x];
+                    s.alg_bytes[K_LF] -= lf_bytes[li];
+                    s.alg_bytes[K_LFR] += lf_bytes[li];
+                    return li;
+                }, s.lists);
+                if (!L.n) return 0;
                 s.lfr_ctr.push_back(s.n_ctr);
-                s.n_ctr += 4 + 2 * nt;     // ticket, done, timeouts, spin; progress and row-done per task
+                s.n_ctr += 4 + 2 * L.n;    // ticket, done, timeouts, spin; two words per task (k_lfr uses one: progress)
                 s.launches.push_back(L);
-                for (int i : phase_frames[ph])
-                    for (size_t k = 0; k < plans[i].s.lfs.size(); k++) {
-                        const LFRec &r = plans[i].s.lfs[k];
-                        if (r.sbx + 2 * r.sby < j0) continue;
-                        s.alg_bytes[K_LF] -= lf_bytes[off[i].lf + k];
-                        s.alg_bytes[K_LFR] += lf_bytes[off[i].lf + k];
-                    }
                 return 0;
             };
             if (!fuse || lvl_ph[ph]) {
@@ -2379,56 +2175,36 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
                 }
                 continue;
             }
-            // Fused schedule: launch t runs intra diagonal t and LF diagonal t - PLF_LAG.
-            // LF of SB (x, y) (diagonal x + 2y = j) rewrites pre-LF pixels of SBs
-            // (x - 1 .. x, y - 1 .. y) that the intra blocks of SBs (x - 1 .. x + 1, y .. y + 1)
-            // read; those are on intra diagonals <= x_in_tile + y + 2 <= j + 2, i.e. in earlier
-            // launches. Conversely the intra diagonal t reads SBs on diagonals t - 1, t - 2,
-            // whose pixels no LF SB of diagonal t - 3 touches (that needs x - x_in_tile + y < 0).
-            // This is the ordering the reference gets from its pre-LF intra_pred_data row
-            // (vp9.c:1404-1416), without a second copy.
-            // The residuals of intra diagonal t + 1 (inverse transforms, incl. inter
-            // residuals added onto the MC prediction) run in launch t too, so no separate
-            // residual pass precedes the wavefront: launch -1 holds diagonal 0's alone.
+            // fused: the step lists go into s.lists as the schedule asks for them (a launch's
+            // intra list, then its LF list)
             const int np = (int) wls.size();
             const int nres = res_fused[ph] ? (int) rj_range[ph].size() : 0;
-            // with k_lfr, LF diagonals fuse into the launches the intra wavefront needs anyway
-            // and k_lfr filters the rest
-            const int jlfr = std::max(0, std::max(np, nres - 1) - PLF_LAG);
-            const int nlf = lfr ? std::min(jlfr, (int) lsteps[ph].size()) : (int) lsteps[ph].size();
-            const int nt = std::max(std::max(np, nlf ? nlf + PLF_LAG : 0), nres - 1);
-            for (int t = -1; t < nt; t++) {
-                const std::vector<uint32_t> *pv = t >= 0 && t < np && !wls[t].empty() ? &wls[t] : nullptr;
-                const int j = t - PLF_LAG;
-                const std::vector<uint32_t> *lv = j >= 0 && j < nlf && !lsteps[ph][j].empty() ? &lsteps[ph][j] : nullptr;
-                const std::array<std::pair<uint32_t, uint32_t>, 5> *rr = t + 1 < nres ? &rj_range[ph][t + 1] : nullptr;
-                bool res = false;
-                for (int k = 0; rr && k < 5; k++) res |= (*rr)[k].second > 0;
-                if (!pv && !res) {
-                    if (lv) add_list(K_LF, *lv, j);
-                    continue;
+            const int nlf = sched_fused_nlf(np, nres, (int) lsteps[ph].size(), lfr);
+            auto append = [&](const std::vector<uint32_t> &v) {
+                s.lists.insert(s.lists.end(), v.begin(), v.end());
+                return SchedRange((uint32_t) (s.lists.size() - v.size()), (uint32_t) v.size());
+            };
+            sched_fused_phase(np, nlf, nres, [&](int t) { return append(wls[t]); }, [&](int j) { return append(lsteps[ph][j]); },
+                              [&](int d, int tc) { return rj_range[ph][d][tc]; },
+                              [&](int fused, int step, SchedRange a, SchedRange b, const SchedRange *rr) {
+                s.launches.push_back(fused_launch(g, ph, fused, step, a, b, rr));
+                for (uint32_t k = 0; fused && k < a.second; k++) {
+                    const double wb = wg_bytes[s.lists[a.first + k]];
+                    s.alg_bytes[K_PRED] -= wb;
+                    s.alg_bytes[K_PLF] += wb;
                 }
-                Launch L = { K_PLF, (uint32_t) s.lists.size(), 0, 0, g, ph, PART_RECON, t };
-                if (pv) {
-                    L.n = (uint32_t) pv->size();
-                    s.lists.insert(s.lists.end(), pv->begin(), pv->end());
-                    for (uint32_t w : *pv) { s.alg_bytes[K_PRED] -= wg_bytes[w]; s.alg_bytes[K_PLF] += wg_bytes[w]; }
+                for (uint32_t k = 0; k < b.second; k++) {
+                    const double lb = lf_bytes[s.lists[b.first + k]];
+                    s.alg_bytes[K_LF] -= lb;
+                    s.alg_bytes[K_PLF] += lb;
                 }
-                L.off2 = (uint32_t) s.lists.size();
-                if (lv) {
-                    L.n2 = (uint32_t) lv->size();
-                    s.lists.insert(s.lists.end(), lv->begin(), lv->end());
-                    for (uint32_t li : *lv) { s.alg_bytes[K_LF] -= lf_bytes[li]; s.alg_bytes[K_PLF] += lf_bytes[li]; }
-                }
-                for (int k = 0; res && k < 5; k++) { L.roff[k] = (*rr)[k].first; L.rn[k] = (*rr)[k].second; }
-                s.launches.push_back(L);
-            }
+            });
             if (lfr)
                 if (int e = add_lfr(nlf)) return e;
         }
     if (s.resid16 > 0xffffffffull) return VP9HIP_ENOMEM;
 
-    STAGE_T(3);
+    clk.lap(3);
     // upload: one arena; its host image is built in pinned memory (every frame writes its
     // records there with the batch index fixups, in parallel) and copied with one DMA
     auto al = [](size_t x) { return (x + 255) & ~(size_t) 255; };
@@ -2446,82 +2222,53 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
     s.o_coefs = o; o = al(o + coef_off[n] + VP9HIP_COEF_PAD);
     s.n_sbs = tot.sb; s.n_pjobs = tot.job; s.n_passes = tot.pass; s.n_wgs = tot.wg; s.n_rjobs = tot_rj;
     s.n_lfs = tot.lf; s.n_mcs = tot.mc;
-    if (o > s.arena_cap) {
-        if (s.arena) hipFree(s.arena);
-        s.arena = nullptr;
-        s.arena_cap = 0;
-        if (hipMalloc(&s.arena, o) != hipSuccess) return VP9HIP_ENOMEM;
-        s.arena_cap = o;
-    }
-    if (o > s.pinned_cap) {
-        if (s.pinned) hipHostFree(s.pinned);
-        s.pinned = nullptr;
-        s.pinned_cap = 0;
-        if (hipHostMalloc((void **) &s.pinned, o, hipHostMallocDefault) != hipSuccess) return VP9HIP_ENOMEM;
-        s.pinned_cap = o;
-    }
-    const size_t rbytes = (size_t) s.resid16 * 32 + 256;
-    if (rbytes > s.resid_cap) {
-        if (s.resid) hipFree(s.resid);
-        s.resid = nullptr;
-        s.resid_cap = 0;
-        if (hipMalloc(&s.resid, rbytes) != hipSuccess) return VP9HIP_ENOMEM;
-        s.resid_cap = rbytes;
-    }
+    if (grow(s.arena, s.arena_cap, o) || grow(s.pinned, s.pinned_cap, o, true) ||
+        grow(s.resid, s.resid_cap, (size_t) s.resid16 * 32 + 256))
+        return VP9HIP_ENOMEM;
     uint8_t *img = s.pinned;
     memcpy(img + s.o_frames, s.frames.data(), s.frames.size() * sizeof(FrameDesc));
     if (!s.lists.empty()) memcpy(img + s.o_lists, s.lists.data(), s.lists.size() * sizeof(uint32_t));
     init_lfr_ctr(c, s, (uint32_t *) (img + s.o_ctr));
     std::vector<double> inplace_bytes(n, 0.0);
-    {
-        std::atomic<int> next(0);
-        auto worker = [&]() {
-            for (int i; (i = next.fetch_add(1)) < n;) {
-                const Staged &l = plans[i].s;
-                const Off &q = off[i];
-                const uint32_t res = (uint32_t) q.res;
-                if (!l.sbs.empty()) memcpy((SBRec *) (img + s.o_sbs) + q.sb, l.sbs.data(), l.sbs.size() * sizeof(SBRec));
-                PJob *pj = (PJob *) (img + s.o_pjobs) + q.job;
-                for (size_t k = 0; k < l.pjobs.size(); k++) {
-                    PJob j = l.pjobs[k];
-                    if (PJ_RES(j)) j.roff += res;
-                    pj[k] = j;
-                }
-                if (!l.passes.empty())
-                    memcpy((uint32_t *) (img + s.o_passes) + q.pass, l.passes.data(), l.passes.size() * sizeof(uint32_t));
-                WGRec *wg = (WGRec *) (img + s.o_wgs) + q.wg;
-                for (size_t k = 0; k < l.wgs.size(); k++) {
-                    WGRec w = l.wgs[k];
-                    w.job0 += q.job; w.pass0 += q.pass; w.sb[0] += q.sb;
-                    wg[k] = w;
-                }
-                if (!l.lfs.empty()) memcpy((LFRec *) (img + s.o_lfs) + q.lf, l.lfs.data(), l.lfs.size() * sizeof(LFRec));
-                if (!l.mcs.empty()) memcpy((McUnit *) (img + s.o_mcs) + q.mc, l.mcs.data(), l.mcs.size() * sizeof(McUnit));
-                double ib = 0;
-                for (size_t d = 0; d < l.rbucket.size(); d++)
-                for (int t = 0; t < 5; t++)
-                    for (int tp = 0; tp < 4; tp++) {
-                        const std::vector<RJob> &bk = l.rbucket[d][t][tp];
-                        RJob *dst = (RJob *) (img + s.o_rjobs) + rj_off[i][d][t][tp];
-                        for (size_t k = 0; k < bk.size(); k++) {
-                            RJob r = bk[k];
-                            if (!(r.ptx & 32)) r.dst += res;          // intra: residual scratch offset
-                            else ib += 2.0 * (16 << (2 * (t & 3))) * c->bypp;   // inter: pixels read + written
-                            dst[k] = r;
-                        }
+    for_frames(c, n, [&](int i) {
+        const Staged &l = plans[i].s;
+        const Off &q = off[i];
+        const uint32_t res = (uint32_t) q.res;
+        if (!l.sbs.empty()) memcpy((SBRec *) (img + s.o_sbs) + q.sb, l.sbs.data(), l.sbs.size() * sizeof(SBRec));
+        PJob *pj = (PJob *) (img + s.o_pjobs) + q.job;
+        for (size_t k = 0; k < l.pjobs.size(); k++) {
+            PJob j = l.pjobs[k];
+            if (PJ_RES(j)) j.roff += res;
+            pj[k] = j;
+        }
+        if (!l.passes.empty())
+            memcpy((uint32_t *) (img + s.o_passes) + q.pass, l.passes.data(), l.passes.size() * sizeof(uint32_t));
+        WGRec *wg = (WGRec *) (img + s.o_wgs) + q.wg;
+        for (size_t k = 0; k < l.wgs.size(); k++) {
+            WGRec w = l.wgs[k];
+            w.job0 += q.job; w.pass0 += q.pass; w.sb[0] += q.sb;
+            wg[k] = w;
+        }
+        if (!l.lfs.empty()) memcpy((LFRec *) (img + s.o_lfs) + q.lf, l.lfs.data(), l.lfs.size() * sizeof(LFRec));
+        if (!l.mcs.empty()) memcpy((McUnit *) (img + s.o_mcs) + q.mc, l.mcs.data(), l.mcs.size() * sizeof(McUnit));
+        double ib = 0;
+        for (size_t d = 0; d < l.rbucket.size(); d++)
+            for (int t = 0; t < 5; t++)
+                for (int tp = 0; tp < 4; tp++) {
+                    const std::vector<RJob> &bk = l.rbucket[d][t][tp];
+                    RJob *dst = (RJob *) (img + s.o_rjobs) + rj_off[i][d][t][tp];
+                    for (size_t k = 0; k < bk.size(); k++) {
+                        RJob r = bk[k];
+                        if (!(r.ptx & 32)) r.dst += res;          // intra: residual scratch offset
+                        else ib += 2.0 * (16 << (2 * (t & 3))) * c->bypp;   // inter: pixels read + written
+                        dst[k] = r;
                     }
-                inplace_bytes[i] = ib;
-                if (coef_off[i + 1] > coef_off[i])
-                    memcpy(img + s.o_coefs + coef_off[i], pkts[i].coefs, coef_off[i + 1] - coef_off[i]);
-                plans[i] = FramePlan();                  // release the frame's host images
-            }
-        };
-        const int nt = std::min(n, c->host_threads);
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nt; t++) pool.emplace_back(worker);
-        worker();
-        for (auto &t : pool) t.join();
-    }
+                }
+        inplace_bytes[i] = ib;
+        if (coef_off[i + 1] > coef_off[i])
+            memcpy(img + s.o_coefs + coef_off[i], pkts[i].coefs, coef_off[i + 1] - coef_off[i]);
+        plans[i] = FramePlan();                  // release the frame's host images
+    });
     for (int i = 0; i < n; i++) s.alg_bytes[K_RESID] += inplace_bytes[i];
     for (int i = 0; i < n; i++)                  // residuals that run inside the k_plf launches
         if (res_fused[fbs[i].phase]) {
@@ -2530,13 +2277,88 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
             s.alg_bytes[K_PLF] += b;
         }
     HIPCHK(hipMemcpyAsync(s.arena, img, o, hipMemcpyHostToDevice, c->st));
-    STAGE_T(4);
+    clk.lap(4);
     HIPCHK(hipStreamSynchronize(c->st));
-    STAGE_T(5);
-    if (stage_trace)
+    clk.lap(5);
+    if (c->stage_trace)
         fprintf(stderr, "vp9hip stage: %d frames: setup %.1f plan %.1f merge %.1f schedule %.1f upload %.1f sync %.1f ms\n",
-                n, st_ms[0], st_ms[1], st_ms[2], st_ms[3], st_ms[4], st_ms[5]);
+                n, clk.ms[0], clk.ms[1], clk.ms[2], clk.ms[3], clk.ms[4], clk.ms[5]);
     s.ready = true;
+    return 0;
+}
+
+// Stage a batch into the current slot: its phases (sched_batch_phases), the per-frame step,
+// the slot dependencies, then the device-planned hand-off (stage_dev) or the host planner.
+static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bufs, const int *ref_bufs /*n*3 or null*/,
+                 int tile_lo = 0, int tile_hi = 64, int max_groups = 0, bool tiled = false)
+{
+    if (!c || !pkts || n <= 0 || !out_bufs) return VP9HIP_EINVAL;
+    if (c->bufs.empty()) return VP9HIP_EINVAL;
+    StageClock clk;
+    hipSetDevice(c->dev);
+    // this slot's previous batch may still read the arena (the other slot's work may go on)
+    if (c->stg.done_ev) HIPCHK(hipEventSynchronize(c->stg.done_ev));
+    if (c->stg.up_ev) HIPCHK(hipEventSynchronize(c->stg.up_ev));
+    Staged &s = c->stg;
+    if (s.graph) { hipGraphExecDestroy(s.graph); s.graph = nullptr; }
+    s.frames.clear(); s.sbs.clear(); s.pjobs.clear(); s.passes.clear(); s.lfs.clear(); s.mcs.clear();
+    s.wgs.clear(); s.sbh.clear(); s.sbjobs.clear(); s.jdep0.clear(); s.jdeps.clear();
+    s.rjobs.clear(); s.resid16 = 0;
+    s.rbucket.clear();
+    s.lists.clear(); s.launches.clear(); s.coefs.clear(); s.n_ctr = 0; s.lfr_ctr.clear();
+    s.frame_phase.assign(n, 0); s.frame_log2.assign(n, 0);
+    s.tile_lo = tile_lo; s.tile_hi = tile_hi;
+    s.stat = false;
+    s.summary_pending = false;
+    s.status = 0;
+    s.fstat.assign(n, 0);
+    for (int k = 0; k < K_N; k++) s.alg_bytes[k] = 0;
+    s.ready = false;
+    init_nz();
+
+    StageIn in = {};
+    in.pkts = pkts; in.n = n; in.csz = c->hb ? 4 : 2; in.out_bufs = out_bufs;
+    // fused intra + LF launches need the LF of a phase in the same launch sequence as its
+    // reconstruction (not for tile-sharded batches: recon, exchange, then LF)
+    in.fuse = c->fuse_plf && !tiled;
+    // the loop filter of a phase as one row-pipelined k_lfr launch (after the phase's
+    // reconstruction) instead of x + 2y diagonal launches
+    in.lfr_any = c->lf_rows > 0 && !tiled;
+    std::vector<char> intra(n);
+    for (int i = 0; i < n; i++) intra[i] = pkts[i].keyframe || pkts[i].intraonly;
+    SchedPhases bp;
+    if (!sched_batch_phases(n, intra.data(), out_bufs, ref_bufs,
+                            { max_groups > 0 ? max_groups : c->max_groups, in.fuse, in.lfr_any, c->level_sched, c->lf_rows }, bp))
+        return VP9HIP_EINVAL;
+    s.ngroups = bp.G; s.nphases = bp.NP;
+    std::vector<FrameBuild> fbs(n);
+    if (const int r = stage_frames(c, pkts, n, out_bufs, ref_bufs, bp, fbs)) return r;
+    in.fbs = &fbs; in.ph = &bp;
+    clk.lap(0);
+    slot_deps(c, pkts, n, out_bufs, ref_bufs);
+    s.dev = s.motion = s.residual = false;
+    if (c->host_plan) return stage_host(c, in, clk);
+    in.motion = (c->export_flags & VP9HIP_EXPORT_MOTION) && !tiled;
+    // the buffers' fields: the frames' grids once the batch ran; none for a sharded batch
+    for (int i = 0; i < n && !c->mot_gwh.empty(); i++) c->mot_gwh[out_bufs[i]] = { 0, 0 };
+    in.residual = (c->export_flags & VP9HIP_EXPORT_RESIDUAL) && !tiled;
+    for (int i = 0; i < n && !c->res_wh.empty(); i++) c->res_wh[out_bufs[i]] = { 0, 0 };
+    if (const int r = stage_dev(c, in)) return r;
+    s.mot_buf.clear(); s.mot_grid.clear();
+    for (int i = 0; i < n && in.motion; i++) {      // in frame order: a buffer's last writer wins
+        s.mot_buf.push_back(out_bufs[i]);
+        s.mot_grid.push_back({ 2 * fbs[i].cols, 2 * fbs[i].rows });
+        c->mot_gwh[out_bufs[i]] = s.mot_grid.back();
+    }
+    s.res_buf.clear(); s.res_size.clear();
+    for (int i = 0; i < n && in.residual; i++) {
+        s.res_buf.push_back(out_bufs[i]);
+        s.res_size.push_back({ pkts[i].width, pkts[i].height });
+        c->res_wh[out_bufs[i]] = s.res_size.back();
+    }
+    clk.lap(1);
+    if (c->stage_trace)
+        fprintf(stderr, "vp9hip stage (device plan): %d frames: setup %.1f upload %.1f ms\n", n, clk.ms[0], clk.ms[1]);
     return 0;
 }
 
@@ -2670,13 +2492,13 @@ static int launch_one(vp9hip_ctx *c, const Launch &L, hipStream_t st)
                                    s.arena + s.o_coefs, s.resid);
     case K_PRED:
         if (L.flow >= 0)
-            return vp9hip_launch_predd(c->hb | c->ss_h << 1 | c->ss_v << 2, st, (int) L.n, c->pred_df_wgs, lists + L.off,
+            return vp9hip_launch_predd(fmt_word(c), st, (int) L.n, c->pred_df_wgs, lists + L.off,
                                        (const uint32_t *) (s.arena + s.o_sbinfo), (const WGRec *) (s.arena + s.o_wgs),
                                        (const SBRec *) (s.arena + s.o_sbs), (const PJob *) (s.arena + s.o_pjobs),
                                        (const uint32_t *) (s.arena + s.o_passes), fr, s.resid, c->ptab,
                                        (uint32_t *) (s.arena + s.o_ctr) + L.flow, (uint32_t *) (s.arena + s.o_ctr) + s.pdone,
                                        c->dbg);
-        return vp9hip_launch_pred(c->hb | c->ss_h << 1 | c->ss_v << 2, st, (int) L.n, lists + L.off, (const WGRec *) (s.arena + s.o_wgs),
+        return vp9hip_launch_pred(fmt_word(c), st, (int) L.n, lists + L.off, (const WGRec *) (s.arena + s.o_wgs),
                                   (const SBRec *) (s.arena + s.o_sbs), (const PJob *) (s.arena + s.o_pjobs),
                                   (const uint32_t *) (s.arena + s.o_passes), fr, s.resid, c->ptab, c->dbg);
     case K_LFR:
@@ -2698,17 +2520,17 @@ static int launch_one(vp9hip_ctx *c, const Launch &L, hipStream_t st)
                                                (uint32_t) std::max(1, c->pred_df_wgs / LFRI_WAVES));
             li.dbg = c->dbg;
         }
-        return vp9hip_launch_lfr(c->hb | c->ss_h << 1 | c->ss_v << 2, st, (int) L.n, lists + L.off,
+        return vp9hip_launch_lfr(fmt_word(c), st, (int) L.n, lists + L.off,
                                  (const LFRec *) (s.arena + s.o_lfs), fr, (uint32_t *) (s.arena + s.o_ctr) + L.arg,
                                  &c->kcfg, &li);
     }
     case K_LF:
-        return vp9hip_launch_lf(c->hb | c->ss_h << 1 | c->ss_v << 2, st, (int) L.n, lists + L.off, (const LFRec *) (s.arena + s.o_lfs), fr, c->dbg >> 16);
+        return vp9hip_launch_lf(fmt_word(c), st, (int) L.n, lists + L.off, (const LFRec *) (s.arena + s.o_lfs), fr, c->dbg >> 16);
     case K_PLF: {
         PlfLaunch pl;
         pl.npred = L.n; pl.nlf = L.n2;
         for (int k = 0; k < 5; k++) { pl.roff[k] = L.roff[k]; pl.rn[k] = L.rn[k]; }
-        return vp9hip_launch_plf(c->hb | c->ss_h << 1 | c->ss_v << 2, st, &pl, lists + L.off, lists + L.off2,
+        return vp9hip_launch_plf(fmt_word(c), st, &pl, lists + L.off, lists + L.off2,
                                  (const WGRec *) (s.arena + s.o_wgs), (const SBRec *) (s.arena + s.o_sbs),
                                  (const PJob *) (s.arena + s.o_pjobs), (const uint32_t *) (s.arena + s.o_passes),
                                  (const LFRec *) (s.arena + s.o_lfs), (const RJob *) (s.arena + s.o_rjobs), fr,
