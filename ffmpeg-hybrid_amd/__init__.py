@@ -156,7 +156,8 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9h_stream_set_color", "vp9hip_out_layout", "vp9hip_out_coefs", "vp9hip_convert_frames",
                "vp9hip_decoder_convert", "vp9hip_convert_frames_scaled", "vp9hip_decoder_convert_scaled",
                "vp9hip_convert_frames_resampled", "vp9hip_decoder_convert_resampled", "vp9hip_resample_weights",
-               "vp9hip_convert_frames_bicubic", "vp9hip_decoder_convert_bicubic", "vp9hip_bicubic_weights"]
+               "vp9hip_convert_frames_bicubic", "vp9hip_decoder_convert_bicubic", "vp9hip_bicubic_weights",
+               "vp9hip_frame_metrics", "vp9hip_frame_metrics_host", "vp9hip_decoder_metrics"]
 
 
 def lib():
@@ -325,6 +326,13 @@ def lib():
                                        ctypes.POINTER(ctypes.c_int * 3)]
     L.vp9hip_residual_relaunch.argtypes = [vp, ctypes.c_void_p]
     L.vp9hip_decoder_frame_residual.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), vp3, i64p3]
+    # frame metrics
+    L.vp9hip_frame_metrics.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_frame_metrics_host.argtypes = [vp3, ctypes.POINTER(ctypes.c_ssize_t * 3), vp3, ctypes.POINTER(ctypes.c_ssize_t * 3)] + \
+                                           [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_decoder_metrics.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(DecodedFrameInfo), ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     _lib_handle = L
     return L
 
@@ -833,6 +841,68 @@ def _residual_views(ptrs, pitch, width, height, ss_h, ss_v, device):
     return out
 
 
+METRIC_FIELDS = ("sum_a", "sum_b", "sumsq_a", "sad", "sse", "ndiff", "maxdiff", "first")   # VP9HIP_METRIC_*
+METRIC_CELL = 16               # VP9HIP_METRIC_CELL
+
+
+def _metric_map_shape(width, height):
+    return (int(height) + METRIC_CELL - 1) // METRIC_CELL, (int(width) + METRIC_CELL - 1) // METRIC_CELL
+
+
+def frame_metrics_host(planes_a, planes_b, width, height, bpp, ss_h=1, ss_v=1, cells=False):
+    """The metrics of one pair of host frames, vp9hip_frame_metrics_host, the C statement of the
+    definition in include/vp9hip.h: an int64 (3, 8) array, plane by METRIC_FIELDS, over the
+    top-left width x height luma samples and the chroma they cover; with cells=True
+    (metrics, map), map the int32 (MH, MW) luma SAD of every 16x16 cell. planes_* are three 2-D
+    arrays each, uint8 at 8 bits, else uint16 (rows may be strided; the codes are not masked to
+    the depth); planes_b=None gives the statistics of a alone."""
+    dt = np.uint8 if bpp == 8 else np.uint16
+    sane = 1 <= width <= 16384 and 1 <= height <= 16384 and ss_h in (0, 1) and ss_v in (0, 1)
+
+    def prep(planes):
+        out = []
+        for p, a in enumerate(planes):
+            a = np.asarray(a)
+            if a.ndim != 2 or a.dtype != dt:
+                raise ValueError("frame_metrics_host: planes must be 2-D %s arrays" % np.dtype(dt).name)
+            if a.strides[1] != a.itemsize or a.strides[0] < 0:
+                a = np.ascontiguousarray(a)
+            if sane:                                  # what the library refuses it does not read
+                pw, ph = (width, height) if p == 0 else ((width + ss_h) >> ss_h, (height + ss_v) >> ss_v)
+                if a.shape[0] < ph or a.shape[1] < pw:
+                    raise ValueError("frame_metrics_host: plane %d is smaller than %d x %d" % (p, pw, ph))
+            out.append(a)
+        if len(out) != 3:
+            raise ValueError("frame_metrics_host: three planes a frame")
+        return out
+    pa = prep(planes_a)
+    pb = prep(planes_b) if planes_b is not None else None
+    out = np.full((3, len(METRIC_FIELDS)), -0x5a5a, np.int64)
+    cmap = np.full(_metric_map_shape(width, height) if sane else (1, 1), -0x5a5a, np.int32) if cells else None
+    ap, als = _plane_ptrs(pa)
+    bp, bls = _plane_ptrs(pb) if pb is not None else (None, None)
+    _check("vp9hip_frame_metrics_host",
+           lib().vp9hip_frame_metrics_host(ctypes.byref(ap), ctypes.byref(als), ctypes.byref(bp) if pb is not None else None,
+                                           ctypes.byref(bls) if pb is not None else None, int(width), int(height), int(bpp),
+                                           int(ss_h), int(ss_v), out.ctypes.data, cmap.ctypes.data if cells else None))
+    return (out, cmap) if cells else out
+
+
+def psnr(metrics, bpp, width, height, ss_h=1, ss_v=1):
+    """PSNR in dB of each plane from metrics records (a host array (..., 3, 8), e.g.
+    Device.metrics(...).cpu()): float64 (..., 3), 10 log10((2^bpp - 1)^2 count / sse) with count
+    the plane's visible samples; inf where sse is 0."""
+    m = np.asarray(metrics)
+    if m.shape[-2:] != (3, len(METRIC_FIELDS)):
+        raise ValueError("psnr: metrics must be (..., 3, %d)" % len(METRIC_FIELDS))
+    cw, ch = (width + ss_h) >> ss_h, (height + ss_v) >> ss_v
+    count = np.array([width * height, cw * ch, cw * ch], np.float64)
+    sse = m[..., METRIC_FIELDS.index("sse")].astype(np.float64)
+    peak = float((1 << bpp) - 1) ** 2
+    with np.errstate(divide="ignore"):
+        return np.where(sse == 0, np.inf, 10.0 * np.log10(peak * count / np.where(sse == 0, 1.0, sse)))
+
+
 def alloc_planes(width, height, bpp, ss_h=1, ss_v=1, pad=64):
     """Host planes padded to 64 luma pixels (the layout the oracle expects)."""
     dt = np.uint8 if bpp == 8 else np.uint16
@@ -1217,6 +1287,61 @@ class Device:
 
     letterbox_rect = staticmethod(letterbox_rect)
 
+    @staticmethod
+    def _metrics_out(n, w, h, cells, out):
+        """The destinations of a metrics call: ((N, 3, 8) int64 view, (N, MH, MW) int32 map or
+        None). `out` is a contiguous int64 cuda tensor of at least N * 24 elements, or None."""
+        import torch
+        need = max(n, 0) * 3 * len(METRIC_FIELDS)
+        if out is None:
+            out = torch.empty(max(need, 1), dtype=torch.int64, device="cuda")
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous()
+                  and out.numel() >= need):
+            raise ValueError("metrics: out must be a contiguous int64 cuda tensor of at least %d elements" % need)
+        res = out.view(-1)[:need].view(max(n, 0), 3, len(METRIC_FIELDS))
+        cmap = None
+        if cells:
+            mh, mw = _metric_map_shape(w, h) if 1 <= w <= 16384 and 1 <= h <= 16384 else (1, 1)
+            cmap = torch.empty((max(n, 1), mh, mw), dtype=torch.int32, device="cuda")[:max(n, 0)]
+        return res, cmap
+
+    def metrics(self, bufs_a, bufs_b=None, size=None, cells=False, out=None, stream=None):
+        """The exact frame metrics of the pairs (bufs_a[i], bufs_b[i]) of device buffers on the GPU
+        (vp9hip_frame_metrics, the definition in include/vp9hip.h): an (N, 3, 8) int64 cuda
+        tensor, pair by plane by METRIC_FIELDS, over the top-left `size` = (width, height) luma
+        samples (default: the configured size) and the chroma they cover; with cells=True
+        (metrics, map), map the (N, MH, MW) int32 luma SAD of every 16x16 cell (its cells sum to
+        the pair's luma "sad"). Any buffers in any order, repeats and a == b allowed;
+        bufs_b=None gives the statistics of a alone ("sum_a", "sumsq_a"; "first" is -1). `out` is
+        a contiguous int64 cuda tensor to write the N * 24 values into (else one is allocated).
+        Runs in the order of torch's current stream (or on `stream`, a hipStream_t handle; see
+        _enqueue_for_torch) and does not wait: order it after the frames' producer (sync(), or
+        vp9hip_slot_stream_wait), as for convert. Needs torch imported before the library was
+        loaded (see _torch_first)."""
+        if not _torch_first:
+            raise Vp9HipUnavailable("metrics: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        bufs_a = [int(b) for b in bufs_a]
+        n = len(bufs_a)
+        if bufs_b is not None:
+            bufs_b = [int(b) for b in bufs_b]
+            if len(bufs_b) != n:
+                raise ValueError("metrics: bufs_a and bufs_b differ in length")
+        w, h = (int(x) for x in size) if size is not None else (self.w, self.h)
+        res, cmap = self._metrics_out(n, w, h, cells, out)
+        aa = (ctypes.c_int * max(n, 1))(*bufs_a)
+        ab = (ctypes.c_int * max(n, 1))(*bufs_b) if bufs_b is not None else None
+        call = lambda st: lib().vp9hip_frame_metrics(self._c, aa, ab, n, w, h, res.data_ptr(),
+                                                     cmap.data_ptr() if cells else None, st)
+        main = ctypes.c_void_p()
+        # an unconfigured context has no buffer to ask for its stream: the library refuses the call itself
+        if lib().vp9hip_frame_device(self._c, 0, (ctypes.c_void_p * 3)(), (ctypes.c_ssize_t * 3)(), None, None,
+                                     ctypes.byref(main)):
+            _check("vp9hip_frame_metrics", call(stream))
+        else:
+            _check("vp9hip_frame_metrics", _enqueue_for_torch(main.value, stream, call))
+        return (res, cmap) if cells else res
+
     def upload(self, buf, planes):
         planes = [np.ascontiguousarray(p) for p in planes]
         ptrs, ls = self._plane_args(planes)
@@ -1410,6 +1535,40 @@ class Decoder:
         for i in infos:
             self.release(i.buf)
         return res
+
+    def metrics(self, infos_a, infos_b=None, cells=False):
+        """The exact frame metrics of the pairs (infos_a[i], infos_b[i]) of frames of
+        receive_frame(download=False) (their DecodedFrameInfos, all of one size, depth and
+        subsampling, all still held), as Device.metrics returns them: an (N, 3, 8) int64 cuda
+        tensor, or (metrics, map) with cells=True (vp9hip_decoder_metrics). infos_b=None gives
+        the statistics of the frames alone. Runs on torch's current stream and waits for it.
+        Unlike Decoder.convert it releases nothing: the scene-cut use, metrics(infos[1:],
+        infos[:-1]), needs every frame twice, so the caller releases the buffers when it is done
+        with them."""
+        if not _torch_first:
+            raise Vp9HipUnavailable("metrics: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        import torch
+        infos_a = list(infos_a)
+        n = len(infos_a)
+        if infos_b is not None:
+            infos_b = list(infos_b)
+            if len(infos_b) != n:
+                raise ValueError("metrics: infos_a and infos_b differ in length")
+        if not n:
+            raise Vp9HipError("vp9hip_decoder_metrics", EINVAL)
+        f = infos_a[0]
+        res, cmap = Device._metrics_out(n, f.width, f.height, cells, None)
+        aa = (DecodedFrameInfo * n)(*infos_a)
+        ab = (DecodedFrameInfo * n)(*infos_b) if infos_b is not None else None
+        main = ctypes.c_void_p()
+        _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
+                                                                (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
+        call = lambda st: lib().vp9hip_decoder_metrics(self._d, aa, ab, n, res.data_ptr(),
+                                                       cmap.data_ptr() if cells else None, st)
+        _check("vp9hip_decoder_metrics", _enqueue_for_torch(main.value, None, call))
+        torch.cuda.current_stream().synchronize()
+        return (res, cmap) if cells else res
 
     def flush(self):
         _check("vp9hip_decoder_flush", lib().vp9hip_decoder_flush(self._d))

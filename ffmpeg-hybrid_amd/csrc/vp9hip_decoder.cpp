@@ -435,6 +435,27 @@ extern "C" int vp9hip_decoder_convert_bicubic(vp9hip_decoder *d, const vp9hip_de
     return decoder_convert(d, frames, n, format, false, 0, 0, dst_dev, pitch, frame_stride, stream, rs, true);
 }
 
+// The metrics of pairs of received frames (vp9hip_frame_metrics). The frames are complete and
+// stay the caller's: nothing is ordered and nothing released here.
+extern "C" int vp9hip_decoder_metrics(vp9hip_decoder *d, const vp9hip_decoded_frame *frames_a,
+                                      const vp9hip_decoded_frame *frames_b, int n, int64_t *out_dev, int32_t *cells_dev,
+                                      void *stream)
+{
+    if (!d || !frames_a || n <= 0 || !d->configured) return VP9HIP_EINVAL;
+    std::vector<int> ba(n), bb(frames_b ? n : 0);
+    const vp9hip_decoded_frame &f0 = frames_a[0];
+    for (int s = 0; s < (frames_b ? 2 : 1); s++)
+        for (int i = 0; i < n; i++) {
+            const vp9hip_decoded_frame &f = s ? frames_b[i] : frames_a[i];
+            if (f.buf < 0 || f.buf >= d->nbufs || d->pins[f.buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+            if (f.width != f0.width || f.height != f0.height || f.bpp != f0.bpp || f.ss_h != f0.ss_h || f.ss_v != f0.ss_v)
+                return VP9HIP_EINVAL;
+            (s ? bb : ba)[i] = f.buf;
+        }
+    return vp9hip_frame_metrics(d->ctx, ba.data(), frames_b ? bb.data() : nullptr, n, f0.width, f0.height, out_dev,
+                                cells_dev, stream);
+}
+
 // Motion export: the flags go to the context before it is configured (the first keyframe).
 extern "C" int vp9hip_decoder_set_export(vp9hip_decoder *d, int flags)
 {

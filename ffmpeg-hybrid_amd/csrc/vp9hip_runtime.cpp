@@ -45,6 +45,7 @@
 #include "vp9hip_convert.h"
 #include "vp9hip_motion.h"
 #include "vp9hip_residual.h"
+#include "vp9hip_metrics.h"
 #include "vp9hip_residn.h"
 
 extern "C" {
@@ -3032,6 +3033,51 @@ extern "C" int vp9hip_convert_frames(vp9hip_ctx *c, const int *bufs, int n, cons
         HIPCHK(vp9hip_convert_launch(a, d->format, c->hb, c->ss_h, c->ss_v, k, st));
         return 0;
     });
+}
+
+// Frame metrics (include/vp9hip.h "frame metrics"; k_metrics in vp9hip_metrics.hip): the pairs
+// (bufs_a[i], bufs_b[i]) into out_dev / cells_dev, enqueued on `stream` (NULL: the current
+// slot's main stream). Everything is validated before the first launch, so a refused call writes
+// nothing. The planes are those vp9hip_frame_device reports; the buffers' pointers travel as
+// kernel arguments, MET_MAX_PAIRS per launch, like the conversion's.
+extern "C" int vp9hip_frame_metrics(vp9hip_ctx *c, const int *bufs_a, const int *bufs_b, int n, int width, int height,
+                                    int64_t *out_dev, int32_t *cells_dev, void *stream)
+{
+    if (!c || c->bufs.empty() || !bufs_a || n <= 0 || !out_dev) return VP9HIP_EINVAL;
+    if (width < 1 || height < 1 || width > c->w || height > c->h) return VP9HIP_EINVAL;
+    if (((uintptr_t) out_dev & 7) || ((uintptr_t) cells_dev & 3) || (cells_dev && !bufs_b)) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++) {
+        if (bufs_a[i] < 0 || bufs_a[i] >= (int) c->bufs.size()) return VP9HIP_EINVAL;
+        if (bufs_b && (bufs_b[i] < 0 || bufs_b[i] >= (int) c->bufs.size())) return VP9HIP_EINVAL;
+    }
+    MetArgs a;
+    memset(&a, 0, sizeof(a));
+    void *pl[3];
+    ptrdiff_t ls[3];
+    if (const int r = vp9hip_frame_device(c, bufs_a[0], pl, ls, nullptr, nullptr, nullptr)) return r;
+    for (int p = 0; p < 3; p++) a.off[p] = (int64_t) ((uint8_t *) pl[p] - (uint8_t *) pl[0]);
+    a.pitch[0] = (int32_t) ls[0]; a.pitch[1] = (int32_t) ls[1];
+    a.w = width; a.h = height;
+    a.cw = (width + c->ss_h) >> c->ss_h; a.ch = (height + c->ss_v) >> c->ss_v;
+    a.ss_h = c->ss_h; a.ss_v = c->ss_v;
+    a.mw = (width + VP9HIP_METRIC_CELL - 1) / VP9HIP_METRIC_CELL;
+    a.mh = (height + VP9HIP_METRIC_CELL - 1) / VP9HIP_METRIC_CELL;
+    a.has_b = bufs_b != nullptr;
+    hipSetDevice(c->dev);
+    hipStream_t st = stream ? (hipStream_t) stream : c->st;
+    for (int i0 = 0; i0 < n; i0 += MET_MAX_PAIRS) {
+        const int k = std::min(n - i0, MET_MAX_PAIRS);
+        for (int i = 0; i < k; i++) {
+            vp9hip_frame_device(c, bufs_a[i0 + i], pl, ls, nullptr, nullptr, nullptr);
+            a.a[i] = (const uint8_t *) pl[0];
+            if (bufs_b) vp9hip_frame_device(c, bufs_b[i0 + i], pl, ls, nullptr, nullptr, nullptr);
+            a.b[i] = (const uint8_t *) pl[0];
+        }
+        a.out = (unsigned long long *) out_dev + (size_t) i0 * 3 * VP9HIP_METRIC_FIELDS;
+        a.cells = cells_dev ? cells_dev + (size_t) i0 * a.mh * a.mw : nullptr;
+        HIPCHK(vp9hip_metrics_launch(a, c->hb, k, st));
+    }
+    return 0;
 }
 
 // The same with the box-filter resize to out_width x out_height fused in (k_convert_scale).

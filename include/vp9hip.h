@@ -618,6 +618,61 @@ int  vp9hip_download_residual(vp9hip_ctx *ctx, int buf, int16_t *const planes[3]
  * NULL arguments, a packet without a size or format, or planes smaller than the coded area. */
 int  vp9hip_residual_host(const vp9h_frame *pkt, int16_t *const planes[3], const ptrdiff_t pitch[3], const int rows[3]);
 
+/* ---- frame metrics: exact sums over two device frames ---------------------------------
+ * What a consumer needs to decide which frames are worth converting: near-duplicate and scene
+ * cut detection (FFmpeg's scene score is the mean luma SAD of consecutive frames), PSNR against
+ * a reference in another buffer, a coarse "what changed" map. One launch reads n pairs of
+ * device frames once; everything is an integer sum with one right answer.
+ *
+ * A frame pair is (a, b): two buffers of one configured context, so of one depth and
+ * subsampling. width x height is the visible luma size compared, the top-left crop as in
+ * vp9hip_out_desc; the chroma planes are ((width + ss_h) >> ss_h) x ((height + ss_v) >> ss_v).
+ * A sample is the stored code, uint8_t at 8 bits, else uint16_t; it is not masked to the depth.
+ *
+ * For each plane p (Y, U, V) of each pair, over the plane's visible samples, VP9HIP_METRIC_FIELDS
+ * int64_t values in the order of the enum below. All fit: the largest is
+ * sum a^2 <= 65535^2 * 2^28 < 2^61; FIRST <= 2^28. With bufs_b == NULL (statistics only)
+ * SUM_B, SAD, SSE, NDIFF and MAXDIFF are 0 and FIRST is -1. The result of n pairs is a tight
+ * (n, 3, VP9HIP_METRIC_FIELDS) int64 array, 192 bytes a pair, plane-major.
+ *
+ * The cell map (optional, luma only, needs b): MW = (width + 15) >> 4, MH = (height + 15) >> 4,
+ * cells[i][cy][cx] = sum |a - b| over the visible luma samples of the 16 x 16 cell (a partial
+ * cell sums what is visible), int32_t (at most 256 * 65535 < 2^24), tight (n, MH, MW). The
+ * cells of a pair sum to its plane 0 SAD. Not offered: other cell sizes (pool the map), chroma
+ * maps, rectangles other than the top-left crop, SSIM / VMAF, histograms. */
+enum { VP9HIP_METRIC_SUM_A,    /* sum a                                                   */
+       VP9HIP_METRIC_SUM_B,    /* sum b                                                   */
+       VP9HIP_METRIC_SUMSQ_A,  /* sum a^2                                                 */
+       VP9HIP_METRIC_SAD,      /* sum |a - b|                                             */
+       VP9HIP_METRIC_SSE,      /* sum (a - b)^2                                           */
+       VP9HIP_METRIC_NDIFF,    /* samples with a != b                                     */
+       VP9HIP_METRIC_MAXDIFF,  /* max |a - b| (0 if none differ)                          */
+       VP9HIP_METRIC_FIRST,    /* min (y * plane_width + x) over samples with a != b, -1 if none */
+       VP9HIP_METRIC_FIELDS };
+#define VP9HIP_METRIC_CELL 16
+/* The metrics of the pairs (bufs_a[i], bufs_b[i]), i < n, into out_dev (device memory, n * 192
+ * bytes) and, if cells_dev is not NULL, their cell maps into cells_dev (device memory,
+ * n * MH * MW * 4 bytes). Any buffers in any order, repeats allowed, a == b allowed; bufs_b may
+ * be NULL (statistics only). n above 32 is split into launches of at most 32 pairs. Enqueues on
+ * `stream` (NULL: the current slot's main stream) and returns without waiting; it orders
+ * nothing itself, exactly as vp9hip_convert_frames. No host wait, no allocation and no host
+ * read of device memory, so it can sit in a captured stream. The results do not depend on what
+ * out_dev / cells_dev held before; only those bytes are written. Everything is checked before
+ * the first launch: a refused call writes nothing. VP9HIP_EINVAL: an unconfigured context, a
+ * buffer index out of range, n <= 0, NULL bufs_a or out_dev, width / height outside
+ * 1 .. the configured size, out_dev not 8-byte aligned, cells_dev not 4-byte aligned, cells_dev
+ * without bufs_b. */
+int  vp9hip_frame_metrics(vp9hip_ctx *ctx, const int *bufs_a, const int *bufs_b, int n,
+                          int width, int height, int64_t *out_dev, int32_t *cells_dev, void *stream);
+/* Host only, no device: the C statement of the definition above for one pair of host frames
+ * (linesize in bytes; b may be NULL, cells may be NULL): out[3][8], cells[MH][MW].
+ * VP9HIP_EINVAL: NULL a, linesize_a or out, sizes outside 1..16384, bpp not 8 / 10 / 12, ss not
+ * 0 / 1, b without linesize_b, cells without b. */
+int  vp9hip_frame_metrics_host(const void *const a[3], const ptrdiff_t linesize_a[3],
+                               const void *const b[3], const ptrdiff_t linesize_b[3],
+                               int width, int height, int bpp, int ss_h, int ss_v,
+                               int64_t out[24], int32_t *cells);
+
 /* Upload host planes into device buffer `buf` (test hook for reference frames). */
 int  vp9hip_upload_frame(vp9hip_ctx *ctx, int buf, const uint8_t *const planes[3],
                          const ptrdiff_t linesize[3]);
@@ -1003,6 +1058,14 @@ int  vp9hip_decoder_frame_motion(vp9hip_decoder *d, const vp9hip_decoded_frame *
  * a frame the caller does not hold. */
 int  vp9hip_decoder_frame_residual(vp9hip_decoder *d, const vp9hip_decoded_frame *frame, void *planes[3],
                                    int64_t pitch[3]);
+/* The metrics of the pairs (frames_a[i], frames_b[i]) of received frames through
+ * vp9hip_frame_metrics, under the rules of vp9hip_decoder_convert: every frame of both arrays
+ * must be of one size, depth and subsampling and held by the caller, else VP9HIP_EINVAL; the size
+ * compared is the frames' own; frames_b may be NULL; it only enqueues. It releases nothing:
+ * consecutive-frame use needs the same frame as b of one pair and a of the next. */
+int  vp9hip_decoder_metrics(vp9hip_decoder *d, const vp9hip_decoded_frame *frames_a,
+                            const vp9hip_decoded_frame *frames_b, int n,
+                            int64_t *out_dev, int32_t *cells_dev, void *stream);
 /* avcodec_flush_buffers: drop queued frames and reference state (seek). */
 int  vp9hip_decoder_flush(vp9hip_decoder *d);
 
