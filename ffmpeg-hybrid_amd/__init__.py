@@ -317,6 +317,18 @@ def lib():
     L.vp9hip_decoder_frame_motion.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(ctypes.c_void_p),
                                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int),
                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)]
+    # accumulated motion
+    u32p, ip = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)
+    L.vp9hip_frame_motion_acc.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ip, ip,
+                                          ctypes.POINTER(ctypes.c_int64), u32p, ctypes.POINTER(ctypes.c_void_p)]
+    L.vp9hip_download_motion_acc.argtypes = [vp, ctypes.c_int, ctypes.c_void_p, u32p]
+    L.vp9hip_motion_acc_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
+                                         ctypes.POINTER(ctypes.c_void_p * 3), ctypes.POINTER(ctypes.c_int * 3),
+                                         ctypes.c_void_p]
+    L.vp9hip_mvacc_launch_dev.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_void_p, ip, ctypes.c_int, ctypes.c_void_p]
+    L.vp9hip_decoder_frame_motion_acc.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(ctypes.c_void_p),
+                                                  ip, ip, ctypes.POINTER(ctypes.c_int64), u32p]
     # residual export
     i64p3, vp3 = ctypes.POINTER(ctypes.c_int64 * 3), ctypes.POINTER(ctypes.c_void_p * 3)
     L.vp9hip_frame_residual.argtypes = [vp, ctypes.c_int, vp3, i64p3, ctypes.POINTER(ctypes.c_int),
@@ -790,6 +802,54 @@ def _motion_views(mv, info, gw, gh, pitch, device):
     return torch.as_tensor(_Mv(), device=device or "cuda"), torch.as_tensor(_Info(), device=device or "cuda")
 
 
+EXPORT_MOTION_ACC = 4          # VP9HIP_EXPORT_MOTION_ACC
+ACC_END_INTRA, ACC_END_NOFIELD, ACC_END_SCALED = 0, 1, 2   # VP9HIP_ACC_END_*
+# vp9hip_acc_cell
+ACC_CELL = np.dtype([("dx", "<i4"), ("dy", "<i4"), ("root", "<u4"), ("hops", "<u2"), ("end", "u1"), ("pad", "u1")])
+
+
+def motion_acc_host(mv, info, serial, parents=(None, None, None), parent_end=(ACC_END_NOFIELD,) * 3):
+    """One frame of the accumulated-motion recurrence on the host (vp9hip_motion_acc_host, the C
+    statement of the definition in include/vp9hip.h): mv int16 (GH, GW, 2, 2) and info uint8
+    (GH, GW, 4) as motion_host gives them, the frame's serial, per reference name the parent's
+    ACC_CELL array (GH, GW) or None with parent_end[k] (ACC_END_NOFIELD / ACC_END_SCALED) saying
+    why. Returns the frame's ACC_CELL array (GH, GW)."""
+    mv, info = np.ascontiguousarray(mv, np.int16), np.ascontiguousarray(info, np.uint8)
+    gh, gw = info.shape[:2]
+    if mv.shape != (gh, gw, 2, 2) or info.shape != (gh, gw, 4):
+        raise Vp9HipError("vp9hip_motion_acc_host", EINVAL)
+    par = [None if q is None else np.ascontiguousarray(q, ACC_CELL) for q in parents]
+    if any(q is not None and q.shape != (gh, gw) for q in par):
+        raise Vp9HipError("vp9hip_motion_acc_host", EINVAL)
+    ptrs = (ctypes.c_void_p * 3)(*[None if q is None else q.ctypes.data for q in par])
+    ends = (ctypes.c_int * 3)(*[int(e) for e in parent_end])
+    out = np.empty((gh, gw), ACC_CELL)
+    _check("vp9hip_motion_acc_host", lib().vp9hip_motion_acc_host(mv.ctypes.data, info.ctypes.data, gw, gh, serial,
+                                                                  ctypes.byref(ptrs), ctypes.byref(ends), out.ctypes.data))
+    return out
+
+
+def acc_fields(t):
+    """The five fields (dx, dy, root, hops, end) of an accumulated-motion view (Device.motion_acc:
+    int32 (GH, GW, 4) with columns dx, dy, root, hops | end << 16), torch or numpy. root is the
+    serial's 32 bits in an int32."""
+    w = t[..., 3]
+    return t[..., 0], t[..., 1], t[..., 2], w & 0xffff, (w >> 16) & 0xff
+
+
+def _acc_view(acc, gw, gh, pitch, device):
+    """Zero-copy torch int32 view (GH, GW, 4) of a field's device plane, strided over the pitch."""
+    if not _torch_first:
+        raise Vp9HipUnavailable("motion_acc: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+    import torch
+
+    class _Acc:
+        __cuda_array_interface__ = {"shape": (gh, gw, 4), "typestr": "<i4", "data": (acc, False),
+                                    "strides": (pitch * 16, 16, 4), "version": 2}
+    return torch.as_tensor(_Acc(), device=device or "cuda")
+
+
 EXPORT_RESIDUAL = 2            # VP9HIP_EXPORT_RESIDUAL
 
 
@@ -979,12 +1039,39 @@ class Device:
         _check("vp9hip_configure", lib().vp9hip_configure(self._c, width, height, bpp, ss_h, ss_v, nbufs))
         self.w, self.h, self.bpp, self.ss_h, self.ss_v = width, height, bpp, ss_h, ss_v
 
-    def set_export(self, motion=True, residual=False):
+    def set_export(self, motion=True, residual=False, motion_acc=False):
         """Motion and / or residual export on / off for the next configure (vp9hip_set_export):
         every batch then leaves each frame's motion field (motion / download_motion) and / or
-        residual field (residual / download_residual) beside its pixels."""
+        residual field (residual / download_residual) beside its pixels; motion_acc (only with
+        motion) adds the accumulated motion field (motion_acc / download_motion_acc)."""
         _check("vp9hip_set_export", lib().vp9hip_set_export(self._c, (EXPORT_MOTION if motion else 0) |
-                                                            (EXPORT_RESIDUAL if residual else 0)))
+                                                            (EXPORT_RESIDUAL if residual else 0) |
+                                                            (EXPORT_MOTION_ACC if motion_acc else 0)))
+
+    def frame_motion_acc(self, buf):
+        """The accumulated field of buffer `buf` in place (vp9hip_frame_motion_acc): (pointer,
+        (GW, GH), pitch in cells, serial, hipStream_t handle)."""
+        acc, st = ctypes.c_void_p(), ctypes.c_void_p()
+        gw, gh, pitch, ser = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_uint32()
+        _check("vp9hip_frame_motion_acc", lib().vp9hip_frame_motion_acc(self._c, buf, ctypes.byref(acc), ctypes.byref(gw),
+                                                                        ctypes.byref(gh), ctypes.byref(pitch),
+                                                                        ctypes.byref(ser), ctypes.byref(st)))
+        return acc.value, (gw.value, gh.value), pitch.value, ser.value, st.value
+
+    def motion_acc(self, buf, device=None):
+        """Zero-copy torch int32 view (GH, GW, 4) of buffer `buf`'s accumulated motion field,
+        strided over the plane's pitch: columns dx, dy, root, hops | end << 16 (acc_fields splits
+        them). Call sync() first (or order consumers after the slot that wrote the frame)."""
+        acc, (gw, gh), pitch, _, _ = self.frame_motion_acc(buf)
+        return _acc_view(acc, gw, gh, pitch, device)
+
+    def download_motion_acc(self, buf):
+        """Buffer `buf`'s accumulated motion field as a numpy ACC_CELL array (GH, GW), and its
+        serial (vp9hip_download_motion_acc; waits for the batches writing the buffer)."""
+        _, (gw, gh), _, _, _ = self.frame_motion_acc(buf)
+        cells, ser = np.empty((gh, gw), ACC_CELL), ctypes.c_uint32()
+        _check("vp9hip_download_motion_acc", lib().vp9hip_download_motion_acc(self._c, buf, cells.ctypes.data, ctypes.byref(ser)))
+        return cells, ser.value
 
     def frame_residual(self, buf):
         """The residual field of buffer `buf` in place (vp9hip_frame_residual): ([ptr] * 3,
@@ -1401,7 +1488,7 @@ class Decoder:
     """
 
     def __init__(self, device=0, max_batch=16, extra_bufs=4, max_width=0, max_height=0, parse_threads=None,
-                 export_motion=False, export_residual=False):
+                 export_motion=False, export_residual=False, export_motion_acc=False):
         self.params = DecoderParams()
         lib().vp9hip_decoder_defaults(ctypes.byref(self.params))
         self.params.device, self.params.max_batch, self.params.extra_bufs = device, max_batch, extra_bufs
@@ -1411,10 +1498,11 @@ class Decoder:
         self._d = ctypes.c_void_p()
         _check("vp9hip_decoder_open", lib().vp9hip_decoder_open(ctypes.byref(self.params), ctypes.byref(self._d)))
         self.eof = False
-        if export_motion or export_residual:
+        if export_motion or export_residual or export_motion_acc:   # accumulated motion turns motion on
             _check("vp9hip_decoder_set_export",
-                   lib().vp9hip_decoder_set_export(self._d, (EXPORT_MOTION if export_motion else 0) |
-                                                   (EXPORT_RESIDUAL if export_residual else 0)))
+                   lib().vp9hip_decoder_set_export(self._d, (EXPORT_MOTION if export_motion or export_motion_acc else 0) |
+                                                   (EXPORT_RESIDUAL if export_residual else 0) |
+                                                   (EXPORT_MOTION_ACC if export_motion_acc else 0)))
 
     def close(self):
         if self._d:
@@ -1477,6 +1565,24 @@ class Decoder:
         m, i = np.empty((gh.value, gw.value, 2, 2), np.int16), np.empty((gh.value, gw.value, 4), np.uint8)
         _check("vp9hip_download_motion", lib().vp9hip_download_motion(self.context(), info.buf, m.ctypes.data, i.ctypes.data))
         return m, i
+
+    def motion_acc(self, info, download=False, device=None):
+        """The accumulated motion field of a frame of receive_frame(download=False), valid until
+        release(info.buf) (vp9hip_decoder_frame_motion_acc; needs export_motion_acc=True):
+        (cells, serial) with cells the zero-copy torch int32 view Device.motion_acc returns, or
+        a numpy ACC_CELL array with download=True. A show_existing_frame output has the field and
+        serial of the frame it shows."""
+        acc, ser = ctypes.c_void_p(), ctypes.c_uint32()
+        gw, gh, pitch = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        _check("vp9hip_decoder_frame_motion_acc",
+               lib().vp9hip_decoder_frame_motion_acc(self._d, ctypes.byref(info), ctypes.byref(acc), ctypes.byref(gw),
+                                                     ctypes.byref(gh), ctypes.byref(pitch), ctypes.byref(ser)))
+        if not download:
+            return _acc_view(acc.value, gw.value, gh.value, pitch.value, device), ser.value
+        cells = np.empty((gh.value, gw.value), ACC_CELL)
+        _check("vp9hip_download_motion_acc",
+               lib().vp9hip_download_motion_acc(self.context(), info.buf, cells.ctypes.data, None))
+        return cells, ser.value
 
     def residual(self, info, download=False, device=None):
         """The residual field of a frame of receive_frame(download=False), valid until

@@ -476,6 +476,14 @@ extern "C" int vp9hip_decoder_frame_motion(vp9hip_decoder *d, const vp9hip_decod
     return vp9hip_frame_motion(d->ctx, f->buf, mv, info, gw, gh, pitch_cells, nullptr);
 }
 
+extern "C" int vp9hip_decoder_frame_motion_acc(vp9hip_decoder *d, const vp9hip_decoded_frame *f, void **acc_dev,
+                                               int *gw, int *gh, int64_t *pitch_cells, uint32_t *serial)
+{
+    if (!d || !f || !d->configured || !(d->export_flags & VP9HIP_EXPORT_MOTION_ACC)) return VP9HIP_EINVAL;
+    if (f->buf < 0 || f->buf >= d->nbufs || d->pins[f->buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+    return vp9hip_frame_motion_acc(d->ctx, f->buf, acc_dev, gw, gh, pitch_cells, serial, nullptr);
+}
+
 extern "C" int vp9hip_decoder_frame_residual(vp9hip_decoder *d, const vp9hip_decoded_frame *f, void *planes[3],
                                              int64_t pitch[3])
 {

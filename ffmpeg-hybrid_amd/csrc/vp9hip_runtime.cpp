@@ -44,6 +44,7 @@
 #include "vp9hip_plan.h"
 #include "vp9hip_convert.h"
 #include "vp9hip_motion.h"
+#include "vp9hip_mvacc.h"
 #include "vp9hip_residual.h"
 #include "vp9hip_metrics.h"
 #include "vp9hip_residn.h"
@@ -211,6 +212,14 @@ struct Staged {
     size_t o_mot = 0;
     std::vector<int> mot_buf;                        // per frame: its output buffer
     std::vector<std::pair<int, int>> mot_grid;       // per frame: GW, GH
+    // accumulated motion (VP9HIP_EXPORT_MOTION_ACC): every run launches k_mvacc after k_motion,
+    // from the AccFrame records uploaded with the batch (o_acc); the fields live and die with
+    // the motion fields (mot_buf, mot_grid)
+    bool acc = false;
+    size_t o_acc = 0;
+    int acc_gw = 0, acc_gh = 0;                      // the largest grid of the batch
+    std::vector<uint32_t> acc_ser;                   // per frame: its serial
+    std::vector<int> acc_level_n;                    // exporting frames per chain position (one launch each)
     // residual export: every run launches k_residual over the batch's SB slots, from the
     // ResidFrame records uploaded with the batch (o_res) and the planner's tx records
     bool residual = false;
@@ -323,6 +332,12 @@ struct vp9hip_ctx {
     std::vector<uint8_t *> mot;
     std::vector<std::pair<int, int>> mot_gwh;
     int mot_pitch = 0, mot_rows = 0;
+    // accumulated motion: per frame buffer one plane of 16-byte records at the motion planes'
+    // pitch and rows; a buffer holds an accumulated field exactly when it holds a motion field
+    // (mot_gwh), acc_serial is that field's frame; acc_next: the next staged frame's serial
+    std::vector<uint8_t *> acc;
+    std::vector<uint32_t> acc_serial;
+    uint32_t acc_next = 1;
     // residual export: per frame buffer one allocation with three int16 planes of the pixel
     // planes' padded geometry (pitch[] elements a row, plane_off[] / bypp elements apart);
     // res_wh: the visible size of the frame whose field a buffer holds, { 0, 0 } when none
@@ -557,6 +572,9 @@ static void free_bufs(vp9hip_ctx *c)
     for (auto *b : c->mot) hipFree(b);
     c->mot.clear();
     c->mot_gwh.clear();
+    for (auto *b : c->acc) hipFree(b);
+    c->acc.clear();
+    c->acc_serial.clear();
     for (auto *b : c->res) hipFree(b);
     c->res.clear();
     c->res_wh.clear();
@@ -737,6 +755,11 @@ extern "C" int vp9hip_configure(vp9hip_ctx *c, int width, int height, int bpp, i
     if (c->export_flags & VP9HIP_EXPORT_MOTION) {
         c->mot_pitch = 2 * c->cols; c->mot_rows = 2 * c->rows;
         if (!alloc(c->mot, c->mot_gwh, { 0, 0 }, (size_t) c->mot_pitch * c->mot_rows * 12)) return VP9HIP_ENOMEM;
+    }
+    if (c->export_flags & VP9HIP_EXPORT_MOTION_ACC) {
+        std::vector<std::pair<int, int>> unused;
+        if (!alloc(c->acc, unused, { 0, 0 }, (size_t) c->mot_pitch * c->mot_rows * sizeof(vp9hip_acc_cell))) return VP9HIP_ENOMEM;
+        c->acc_serial.assign(nbufs, 0);
     }
     if ((c->export_flags & VP9HIP_EXPORT_RESIDUAL) && !alloc(c->res, c->res_wh, { 0, 0 }, c->buf_bytes / c->bypp * 2))
         return VP9HIP_ENOMEM;
@@ -1175,6 +1198,9 @@ struct StageIn {
     bool fuse, lfr_any;
     const int *out_bufs;
     bool motion;                 // the batch exports its frames' motion fields
+    bool acc;                    // and their accumulated motion, with serials from serial0
+    uint32_t serial0;
+    const int *ref_bufs;         // n * 3, or null (a batch of intra frames)
     bool residual;               // the batch exports its frames' residual fields
 };
 
@@ -1481,6 +1507,8 @@ static int stage_dev(vp9hip_ctx *c, const StageIn &in)
     s.o_mot = o; o = al(o + (s.motion ? (size_t) n * sizeof(MotionFrame) : 0));
     s.residual = in.residual;
     s.o_res = o; o = al(o + (s.residual ? (size_t) n * sizeof(ResidFrame) : 0));
+    s.acc = in.acc;
+    s.o_acc = o; o = al(o + (s.acc ? (size_t) n * (sizeof(AccFrame) + 4) : 0));   // the records, then the launch order
     s.o_blocks = o; o = al(o + nb * sizeof(vp9h_block));
     s.o_eobs = o; o = al(o + ne * 2);
     s.o_coefs = o; o = al(o + nc * in.csz + VP9HIP_COEF_PAD);
@@ -1551,6 +1579,65 @@ static int stage_dev(vp9hip_ctx *c, const StageIn &in)
             mf[i].info = (uint64_t) (mp + (size_t) c->mot_pitch * c->mot_rows * 8);
             mf[i].pitch = (uint32_t) c->mot_pitch;
             mf[i].pad = 0;
+        }
+    }
+    s.acc_gw = s.acc_gh = 0;
+    if (s.acc) {
+        // the parents of include/vp9hip.h ("accumulated motion"): a frame of the batch when it is
+        // the last writer of the reference's buffer, the buffer's finished field when no frame of
+        // the batch writes it, else none
+        AccFrame *af = (AccFrame *) (img + s.o_acc);
+        const int *ob = in.out_bufs;
+        for (int i = 0; i < n; i++) {
+            AccFrame &A = af[i];
+            memset(&A, 0, sizeof(A));
+            uint8_t *mp = c->mot[ob[i]];
+            A.mv = (uint64_t) mp;
+            A.info = (uint64_t) (mp + (size_t) c->mot_pitch * c->mot_rows * 8);
+            A.acc = (uint64_t) c->acc[ob[i]];
+            const int gw = 2 * fbs[i].cols, gh = 2 * fbs[i].rows;
+            A.gw = last_writer(ob, n, i) ? (uint32_t) gw : 0;     // as for motion: only the last writer exports
+            A.gh = (uint32_t) gh;
+            A.pitch = (uint32_t) c->mot_pitch;
+            A.serial = in.serial0 + (uint32_t) i;
+            const bool intra = pkts[i].keyframe || pkts[i].intraonly;
+            for (int k = 0; k < 3; k++) {
+                A.par[k] = ACC_PAR_NONE(VP9HIP_ACC_END_NOFIELD);
+                if (intra || !in.ref_bufs) continue;
+                const int B = in.ref_bufs[3 * i + k];
+                int j = i - 1;
+                while (j >= 0 && ob[j] != B) j--;
+                std::pair<int, int> pg = { 0, 0 };                // the parent's grid, { 0, 0 }: none
+                if (j >= 0) {
+                    if (last_writer(ob, n, j)) pg = { 2 * fbs[j].cols, 2 * fbs[j].rows };
+                } else if (std::find(ob + i, ob + n, B) == ob + n) {
+                    pg = c->mot_gwh[B];
+                }
+                if (!pg.first) continue;
+                if (pg != std::make_pair(gw, gh)) { A.par[k] = ACC_PAR_NONE(VP9HIP_ACC_END_SCALED); continue; }
+                if (j >= 0) {
+                    A.par[k] = j;
+                    A.level = std::max(A.level, af[j].level + 1);
+                } else {
+                    A.par[k] = ACC_PAR_EXT;
+                    A.ext[k] = (uint64_t) c->acc[B];
+                }
+            }
+            s.acc_gw = std::max(s.acc_gw, (int) A.gw);
+            if (A.gw) s.acc_gh = std::max(s.acc_gh, gh);
+        }
+        // the exporting frames by chain position: one launch each, parents before children
+        uint32_t *order = (uint32_t *) (af + n), no = 0;
+        s.acc_level_n.clear();
+        for (uint32_t l = 0; no < (uint32_t) n; l++) {
+            int cnt = 0, later = 0;
+            for (int i = 0; i < n; i++) {
+                if (af[i].level == l && af[i].gw) { order[no + cnt] = (uint32_t) i; cnt++; }
+                later += af[i].level > l;
+            }
+            s.acc_level_n.push_back(cnt);
+            no += cnt;
+            if (!later) break;
         }
     }
     s.res_max_sb = 0;
@@ -2337,12 +2424,16 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
     in.fbs = &fbs; in.ph = &bp;
     clk.lap(0);
     slot_deps(c, pkts, n, out_bufs, ref_bufs);
-    s.dev = s.motion = s.residual = false;
+    s.dev = s.motion = s.residual = s.acc = false;
     if (c->host_plan) return stage_host(c, in, clk);
     in.motion = (c->export_flags & VP9HIP_EXPORT_MOTION) && !tiled;
     // the buffers' fields: the frames' grids once the batch ran; none for a sharded batch
     for (int i = 0; i < n && !c->mot_gwh.empty(); i++) c->mot_gwh[out_bufs[i]] = { 0, 0 };
     in.residual = (c->export_flags & VP9HIP_EXPORT_RESIDUAL) && !tiled;
+    in.acc = in.motion && (c->export_flags & VP9HIP_EXPORT_MOTION_ACC);
+    in.ref_bufs = ref_bufs;
+    in.serial0 = c->acc_next;
+    if (in.acc) c->acc_next += (uint32_t) n;        // one serial per staged frame, restagings included
     for (int i = 0; i < n && !c->res_wh.empty(); i++) c->res_wh[out_bufs[i]] = { 0, 0 };
     if (const int r = stage_dev(c, in)) return r;
     s.mot_buf.clear(); s.mot_grid.clear();
@@ -2350,6 +2441,11 @@ static int stage(vp9hip_ctx *c, const vp9h_frame *pkts, int n, const int *out_bu
         s.mot_buf.push_back(out_bufs[i]);
         s.mot_grid.push_back({ 2 * fbs[i].cols, 2 * fbs[i].rows });
         c->mot_gwh[out_bufs[i]] = s.mot_grid.back();
+    }
+    s.acc_ser.clear();
+    for (int i = 0; i < n && in.acc; i++) {
+        s.acc_ser.push_back(in.serial0 + (uint32_t) i);
+        c->acc_serial[out_bufs[i]] = s.acc_ser.back();
     }
     s.res_buf.clear(); s.res_size.clear();
     for (int i = 0; i < n && in.residual; i++) {
@@ -2431,6 +2527,16 @@ extern "C" int vp9hip_run_batch(vp9hip_ctx *c)
                                     (const vp9h_block *) (s.arena + s.o_blocks), 0, c->st));
         // (again) the fields of this run: a refused earlier run or a fill in between cleared them
         for (size_t i = 0; i < s.mot_buf.size(); i++) c->mot_gwh[s.mot_buf[i]] = s.mot_grid[i];
+    }
+    // accumulated motion: directly after k_motion, whose planes it reads in stream order, one
+    // launch per chain position of the batch; the waits above cover the external parents' records
+    // (another slot's k_mvacc comes before that slot's done_ev). Outside the graph for k_motion's
+    // reason.
+    if (s.dev && s.acc) {
+        const AccFrame *af = (const AccFrame *) (s.arena + s.o_acc);
+        HIPCHK(vp9hip_mvacc_launch(af, s.nframes, s.acc_gw, s.acc_gh, 0, (const uint32_t *) (af + s.nframes),
+                                   s.acc_level_n.data(), (int) s.acc_level_n.size(), c->st));
+        for (size_t i = 0; i < s.acc_ser.size(); i++) c->acc_serial[s.mot_buf[i]] = s.acc_ser[i];
     }
     // residual export: one launch over the batch's SB slots, after the planner's records (the
     // waits above, or plan_dev's host synchronise) and outside the graph like k_motion. It reads
@@ -2865,7 +2971,8 @@ extern "C" int vp9hip_frame_device(vp9hip_ctx *c, int buf, void *planes[3], ptrd
 // ---- motion export (include/vp9hip.h "motion export"; k_motion in vp9hip_motion.hip) ----
 extern "C" int vp9hip_set_export(vp9hip_ctx *c, int flags)
 {
-    if (!c || (flags & ~(VP9HIP_EXPORT_MOTION | VP9HIP_EXPORT_RESIDUAL))) return VP9HIP_EINVAL;
+    if (!c || (flags & ~(VP9HIP_EXPORT_MOTION | VP9HIP_EXPORT_RESIDUAL | VP9HIP_EXPORT_MOTION_ACC))) return VP9HIP_EINVAL;
+    if ((flags & VP9HIP_EXPORT_MOTION_ACC) && !(flags & VP9HIP_EXPORT_MOTION)) return VP9HIP_EINVAL;
     if (flags && c->host_plan) return VP9HIP_ENOSYS;      // host-planned batches do not upload the blocks
     if (!c->bufs.empty() && flags != c->export_flags) return VP9HIP_EINVAL;
     c->export_flags = flags;
@@ -2899,6 +3006,56 @@ extern "C" int vp9hip_download_motion(vp9hip_ctx *c, int buf, int16_t *mv, uint8
     if (info) HIPCHK(hipMemcpy2DAsync(info, (size_t) gw * 4, infod, (size_t) pitch * 4, (size_t) gw * 4, gh, hipMemcpyDeviceToHost, c->dst_dl));
     HIPCHK(hipStreamSynchronize(c->dst_dl));
     return 0;
+}
+
+// ---- accumulated motion (include/vp9hip.h "accumulated motion"; k_mvacc in vp9hip_mvacc.hip) ----
+extern "C" int vp9hip_frame_motion_acc(vp9hip_ctx *c, int buf, void **acc_dev, int *gw, int *gh, int64_t *pitch_cells,
+                                       uint32_t *serial, void **stream)
+{
+    if (!c || c->acc.empty() || buf < 0 || buf >= (int) c->acc.size()) return VP9HIP_EINVAL;
+    if (!c->mot_gwh[buf].first) return VP9HIP_EAGAIN;
+    if (acc_dev) *acc_dev = c->acc[buf];
+    if (gw) *gw = c->mot_gwh[buf].first;
+    if (gh) *gh = c->mot_gwh[buf].second;
+    if (pitch_cells) *pitch_cells = c->mot_pitch;
+    if (serial) *serial = c->acc_serial[buf];
+    if (stream) *stream = (void *) c->st;
+    return 0;
+}
+
+extern "C" int vp9hip_download_motion_acc(vp9hip_ctx *c, int buf, vp9hip_acc_cell *acc, uint32_t *serial)
+{
+    void *accd = nullptr;
+    int gw = 0, gh = 0;
+    int64_t pitch = 0;
+    if (const int r = vp9hip_frame_motion_acc(c, buf, &accd, &gw, &gh, &pitch, serial, nullptr)) return r;
+    hipSetDevice(c->dev);
+    if (const int r = wait_writers(c, buf)) return r;
+    if (!c->dst_dl) HIPCHK(hipStreamCreateWithFlags(&c->dst_dl, hipStreamNonBlocking));
+    if (acc) HIPCHK(hipMemcpy2DAsync(acc, (size_t) gw * 16, accd, (size_t) pitch * 16, (size_t) gw * 16, gh, hipMemcpyDeviceToHost, c->dst_dl));
+    HIPCHK(hipStreamSynchronize(c->dst_dl));
+    return 0;
+}
+
+// Diagnostics (tools/mvacc_bench.py): k_mvacc over caller-built AccFrame records in device memory,
+// on `stream`; shape 0 is the launch per chain position (order_dev: the frames by level,
+// level_n[l]: the frames at level l), shape 1 the one-launch walk.
+extern "C" int vp9hip_mvacc_launch_dev(const void *frames_dev, int nframes, int max_gw, int max_gh, int shape,
+                                       const void *order_dev, const int *level_n, int nlevels, void *stream)
+{
+    if (!frames_dev || nframes <= 0 || nframes > 65535 || max_gw <= 0 || max_gh <= 0 || max_gw > 4096 || max_gh > 4096 ||
+        ((uintptr_t) frames_dev & 7))
+        return VP9HIP_EINVAL;
+    if (shape != 1) {
+        if (!order_dev || !level_n || nlevels <= 0) return VP9HIP_EINVAL;
+        int tot = 0;
+        for (int l = 0; l < nlevels; l++) {
+            if (level_n[l] < 0 || level_n[l] > nframes - tot) return VP9HIP_EINVAL;
+            tot += level_n[l];
+        }
+    }
+    return vp9hip_mvacc_launch((const AccFrame *) frames_dev, nframes, max_gw, max_gh, shape, (const uint32_t *) order_dev,
+                               level_n, nlevels, (hipStream_t) stream) == hipSuccess ? 0 : VP9HIP_EEXTERNAL;
 }
 
 // ---- residual export (include/vp9hip.h "residual export"; k_residual in vp9hip_residual.hip) ----

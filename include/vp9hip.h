@@ -48,7 +48,9 @@ extern "C" {
  * vp9hip_bicubic_weights) likewise: a new macro and new symbols, the filter enum and
  * vp9hip_resample unchanged. The residual export (VP9HIP_EXPORT_RESIDUAL, vp9hip_frame_residual,
  * vp9hip_download_residual, vp9hip_residual_host, vp9hip_decoder_frame_residual) likewise: new
- * symbols only. */
+ * symbols only. Accumulated motion (VP9HIP_EXPORT_MOTION_ACC, vp9hip_acc_cell,
+ * vp9hip_frame_motion_acc, vp9hip_download_motion_acc, vp9hip_motion_acc_host,
+ * vp9hip_decoder_frame_motion_acc) likewise: a new macro, a new struct and new symbols. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -519,7 +521,8 @@ int  vp9hip_bicubic_weights(int n_src, int n_out, int o, int *first, int32_t *we
  * vectors. */
 #define VP9HIP_EXPORT_MOTION 1
 /* Export flags (0, VP9HIP_EXPORT_MOTION, and / or VP9HIP_EXPORT_RESIDUAL, "residual export"
- * below) of the next vp9hip_configure, which then allocates
+ * below, and / or VP9HIP_EXPORT_MOTION_ACC, "accumulated motion" below, which is VP9HIP_EINVAL
+ * without VP9HIP_EXPORT_MOTION) of the next vp9hip_configure, which then allocates
  * two side planes per frame buffer, freed with the buffers: mv (8 bytes per cell) and info (4
  * bytes per cell), of the fixed cell pitch 2 ((cfg_width + 7) >> 3) and 2 ((cfg_height + 7) >> 3)
  * rows; a smaller frame in a larger context uses the top-left of its planes. VP9HIP_EINVAL:
@@ -554,6 +557,77 @@ int  vp9hip_download_motion(vp9hip_ctx *ctx, int buf, int16_t *mv, uint8_t *info
  * (a cell two blocks cover counts twice), or VP9HIP_EINVAL for a NULL argument or a packet
  * without a size. */
 int  vp9hip_motion_host(const vp9h_frame *pkt, int16_t *mv, uint8_t *info);
+
+/* ---- accumulated motion: every cell's displacement to the frame its content came from ----
+ * The motion field above is relative to each frame's own references. Temporal propagation of
+ * labels or features and CoViAR-style models want the vectors followed back through the GOP
+ * until an intra cell or a keyframe. With VP9HIP_EXPORT_MOTION_ACC (only together with
+ * VP9HIP_EXPORT_MOTION) one more kernel (k_mvacc) per batch does that on the device, where the
+ * fields are resident and the runtime knows every frame's three reference buffers. Off by
+ * default; with it off nothing is allocated and nothing is launched.
+ *
+ * With the flag vp9hip_configure allocates one more side plane per frame buffer, freed with the
+ * buffers: 16 bytes (one vp9hip_acc_cell) per cell, at the motion planes' cell pitch and rows.
+ *
+ * Serials. Every frame staged by vp9hip_stage_batch / _refs on a context with the flag gets a
+ * serial from a per-context uint32_t counter that starts at 1 and advances one per frame in
+ * staging order; restagings count, a re-run of a staged batch keeps its serials. The serial lives
+ * with the buffer's field, as the grid does.
+ *
+ * Parent of frame i of a batch for reference name k (0 LAST, 1 GOLDEN, 2 ALTREF). Let B =
+ * ref_bufs[3 i + k]. If an earlier frame of the batch writes B, the parent is the latest such
+ * frame j < i, provided j is the last writer of B in the batch; otherwise there is none
+ * (NOFIELD). If no frame of the batch writes B and B holds an accumulated field (host-side
+ * state, set and cleared exactly as the motion field's), the parent is that field, with its grid
+ * and serial. In every other case there is none (NOFIELD): a buffer without a field, an external
+ * buffer that a later frame of the batch overwrites. A parent whose grid (GW, GH) differs from
+ * the frame's is none with SCALED.
+ *
+ * Record of cell (r, c) of frame t, with info, mv, GW and GH as the motion export defines them
+ * and i0 = info[r][c][0]:
+ *   i0 == 255 (an intra cell, hence every cell of a keyframe): { 0, 0, serial_t, 0, INTRA, 0 }.
+ *   Otherwise let (mx, my) = mv[r][c][0]: only the first reference is followed, a compound
+ *   block's second vector is ignored.
+ *   i0 > 2, or no parent for name i0: { mx, my, 0, 1, NOFIELD or SCALED, 0 }.
+ *   Else the parent cell is
+ *     c' = clamp((32 c + 16 + mx) >> 5, 0, GW - 1)
+ *     r' = clamp((32 r + 16 + my) >> 5, 0, GH - 1)
+ *   (an arithmetic shift, so the division floors: the cell centre is displaced by the vector and
+ *   snapped to the cell it lands in), q is the parent's record at (r', c'), and the record is
+ *     { mx + q.dx, my + q.dy, q.root, min(q.hops + 1, 65535), q.end, 0 }.
+ *   The two sums wrap modulo 2^32 (unsigned adds); they cannot wrap before hops saturates, since
+ *   |mv| <= 2^15.
+ * Every cell of the GW x GH grid is written, and nothing else. The field of a frame the planner
+ * rejects, and of anything chained through it, is unspecified. A buffer written by several frames
+ * of a batch keeps the last writer's field. A refused run, vp9hip_upload_frame,
+ * vp9hip_fill_buffers and sharded batches leave the buffers they touch without a field. */
+#define VP9HIP_EXPORT_MOTION_ACC 4
+typedef struct vp9hip_acc_cell {   /* 16 bytes */
+    int32_t  dx, dy;   /* sum of the coded vectors along the chain, 1/8 luma pel */
+    uint32_t root;     /* serial of the frame where the chain ended, 0: unknown  */
+    uint16_t hops;     /* frames stepped through, saturating at 65535            */
+    uint8_t  end;      /* VP9HIP_ACC_END_*                                       */
+    uint8_t  pad;      /* 0                                                      */
+} vp9hip_acc_cell;
+enum { VP9HIP_ACC_END_INTRA, VP9HIP_ACC_END_NOFIELD, VP9HIP_ACC_END_SCALED };
+/* The accumulated field of device buffer `buf`, in place, in the style of vp9hip_frame_motion:
+ * the device pointer of the plane (vp9hip_acc_cell [gh][pitch_cells]), the grid and serial of the
+ * frame last exported into the buffer, the pitch in cells, and the current slot's main
+ * hipStream_t; any output pointer may be NULL. VP9HIP_EINVAL without the flag or for a bad buf;
+ * VP9HIP_EAGAIN if the buffer holds no field. */
+int  vp9hip_frame_motion_acc(vp9hip_ctx *ctx, int buf, void **acc_dev, int *gw, int *gh,
+                             int64_t *pitch_cells, uint32_t *serial, void **stream);
+/* Copy the field of `buf` into a tight host array acc[gh][gw] (may be NULL). Waits for the
+ * batches writing the buffer, like vp9hip_download_motion. Errors as vp9hip_frame_motion_acc. */
+int  vp9hip_download_motion_acc(vp9hip_ctx *ctx, int buf, vp9hip_acc_cell *acc, uint32_t *serial);
+/* Host only, no device: one frame of the recurrence above over tight arrays of one grid:
+ * mv[gh][gw][2][2], info[gh][gw][4], out[gh][gw], and per reference name the parent's records
+ * parent[k][gh][gw], or NULL for no parent, when parent_end[k] (VP9HIP_ACC_END_NOFIELD or
+ * _SCALED) says why. VP9HIP_EINVAL for a NULL argument, a grid outside 1..4096 or a NULL parent
+ * with another end code. */
+int  vp9hip_motion_acc_host(const int16_t *mv, const uint8_t *info, int gw, int gh, uint32_t serial,
+                            const vp9hip_acc_cell *const parent[3], const int parent_end[3],
+                            vp9hip_acc_cell *out);
 
 /* ---- residual export: what the transforms add to the prediction, as device tensors ----
  * The third input of compressed-domain models besides I-frame pixels and motion vectors. The
@@ -1051,6 +1125,14 @@ int  vp9hip_decoder_set_export(vp9hip_decoder *d, int flags);
  * for a frame the caller does not hold. */
 int  vp9hip_decoder_frame_motion(vp9hip_decoder *d, const vp9hip_decoded_frame *frame, void **mv, void **info,
                                  int *gw, int *gh, int64_t *pitch_cells);
+/* The accumulated motion field of a received frame, in place (as vp9hip_frame_motion_acc), under
+ * the rules of vp9hip_decoder_frame_motion: valid while the frame is un-released (the decoder
+ * keeps a reference buffer, and with it the parent's plane, while a pending frame reads it), a
+ * show_existing_frame output carries the shown buffer's field and serial. Needs
+ * VP9HIP_EXPORT_MOTION | VP9HIP_EXPORT_MOTION_ACC in vp9hip_decoder_set_export's flags;
+ * VP9HIP_EINVAL without them or for a frame the caller does not hold. */
+int  vp9hip_decoder_frame_motion_acc(vp9hip_decoder *d, const vp9hip_decoded_frame *frame, void **acc_dev,
+                                     int *gw, int *gh, int64_t *pitch_cells, uint32_t *serial);
 /* The residual field of a received frame, in place (as vp9hip_frame_residual), under the rules
  * of vp9hip_decoder_frame_motion: valid while the frame is un-released, a show_existing_frame
  * output returns the field of the frame it shows, hidden frames export too. Needs
