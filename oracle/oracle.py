@@ -50,6 +50,10 @@ def lib():
         _L.vp9o_set_intra_trace.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
         _L.vp9o_set_intra_trace.restype = None
         _L.vp9o_intra_trace_count.restype = ctypes.c_size_t
+        _L.vp9o_set_lf_census.argtypes = [ctypes.c_void_p]
+        _L.vp9o_set_lf_census.restype = None
+        _L.vp9o_lf_limits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int * 3)]
+        _L.vp9o_lf_limits.restype = None
         _L.vp9o_scan.argtypes = [ctypes.c_int, ctypes.c_int]
         _L.vp9o_scan.restype = ctypes.POINTER(ctypes.c_int16)
     return _L
@@ -100,6 +104,36 @@ def intra_trace(pkt, out_planes, ref_planes=None, cap=1 << 16):
     if n > cap:
         raise RuntimeError("intra trace: %d calls, room for %d" % (n, cap))
     return buf[:n]
+
+
+LF_ARMS = ("off", "n4", "h4", "f8", "f16")
+LF_TIGHT = ("I", "I+1", "E", "E+1", "Fin", "Fin+1", "Fout", "Fout+1", "H", "H+1")
+
+
+class LfCensus:
+    """vp9o_set_lf_census for the calls made inside the `with` block (single-threaded only):
+    count and moved are [plane class: luma, chroma][direction: column edge, row edge]
+    [coded width: 4, 8, 16][arm: LF_ARMS], tight is [plane class][LF_TIGHT] (vp9_oracle.h)."""
+
+    def __init__(self):
+        self.buf = np.zeros(140, np.int64)
+        self.count = self.buf[:60].reshape(2, 2, 3, 5)
+        self.moved = self.buf[60:120].reshape(2, 2, 3, 5)
+        self.tight = self.buf[120:].reshape(2, 10)
+
+    def __enter__(self):
+        lib().vp9o_set_lf_census(self.buf.ctypes.data)
+        return self
+
+    def __exit__(self, *exc):
+        lib().vp9o_set_lf_census(None)
+
+
+def lf_limits(level, sharpness):
+    """(E, I, H) of a level as the frame path derives them, before the bit-depth shift."""
+    out = (ctypes.c_int * 3)()
+    lib().vp9o_lf_limits(level, sharpness, ctypes.byref(out))
+    return tuple(out)
 
 
 def scan(tx, txtp):

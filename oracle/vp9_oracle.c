@@ -18,6 +18,12 @@
 #include "vp9_oracle.h"
 #include "../ffmpeg-hybrid_amd/csrc/vp9_tables.h"
 
+/* vp9o_set_lf_census (vp9_oracle.h): NULL while off, when a line costs this one test. The
+ * plane class * 2 + direction of the lines that follow is set by filter_plane_cols / rows
+ * (and by vp9o_loop_filter: luma, its dir) only while a buffer is set. */
+static int64_t *lf_census;
+static int lf_census_pd;
+
 #define OB 8
 #include "vp9o_dsp_tmpl.h"
 #undef OB
@@ -67,6 +73,7 @@ void vp9o_intra_pred(int bpp, void *dst, ptrdiff_t stride, const void *left, con
 void vp9o_loop_filter(int bpp, void *dst, ptrdiff_t stride, int kind, int wd1, int wd2, int dir,
                       int E, int I, int H)
 {
+    if (lf_census) lf_census_pd = !!dir;
     if (bpp == 8) {
         if (kind == 0) lf8_8(dst, stride, wd1, dir, E, I, H, 8);
         else if (kind == 1) lf16_8(dst, stride, dir, E, I, H, 8);
@@ -152,6 +159,26 @@ static int32_t *intra_trace;
 static size_t intra_trace_cap, intra_trace_n;
 void vp9o_set_intra_trace(int32_t *buf, size_t cap) { intra_trace = buf; intra_trace_cap = buf ? cap : 0; intra_trace_n = 0; }
 size_t vp9o_intra_trace_count(void) { return intra_trace_n; }
+
+void vp9o_set_lf_census(int64_t *buf) { lf_census = buf; lf_census_pd = 0; }
+
+/* lim (I) of a level, vp9.c:673-686 */
+static int lf_lim(int level, int sharp)
+{
+    int limit = level;
+    if (sharp > 0) {
+        limit >>= (sharp + 3) >> 2;
+        limit = MIN(limit, 9 - sharp);
+    }
+    return MAX(limit, 1);
+}
+
+void vp9o_lf_limits(int level, int sharpness, int out[3])
+{
+    out[1] = lf_lim(level, sharpness);
+    out[0] = 2 * (level + 2) + out[1];      /* mblim_lut, vp9.c:685 */
+    out[2] = level >> 4;                    /* vp9lpf.c:49 */
+}
 
 /* check_intra_mode, vp9recon.c:37-221. Byte-addressed like the reference. */
 static int check_intra_mode(OCtx *c, int mode, uint8_t **a, uint8_t *dst_edge, ptrdiff_t stride_edge,
@@ -832,10 +859,11 @@ static void lfmix(OCtx *c, uint8_t *p, ptrdiff_t ls, int w1, int w2, int dir, in
 }
 
 /* filter_plane_cols, vp9lpf.c:31-104 */
-static void filter_plane_cols(OCtx *c, int col, int ss_h, int ss_v, uint8_t *lvl, uint8_t (*mask)[4],
+static void filter_plane_cols(OCtx *c, int uv, int col, int ss_h, int ss_v, uint8_t *lvl, uint8_t (*mask)[4],
                               uint8_t *dst, ptrdiff_t ls)
 {
     int y, x, bypp = c->bypp;
+    if (lf_census) lf_census_pd = uv * 2;
     for (y = 0; y < 8; y += 2 << ss_v, dst += 16 * ls, lvl += 16 << ss_v) {
         uint8_t *ptr = dst, *l = lvl, *hmask1 = mask[y], *hmask2 = mask[y + 1 + ss_v];
         unsigned hm1 = hmask1[0] | hmask1[1] | hmask1[2], hm13 = hmask1[3];
@@ -891,10 +919,11 @@ static void filter_plane_cols(OCtx *c, int col, int ss_h, int ss_v, uint8_t *lvl
 }
 
 /* filter_plane_rows, vp9lpf.c:106-181 */
-static void filter_plane_rows(OCtx *c, int row, int ss_h, int ss_v, uint8_t *lvl, uint8_t (*mask)[4],
+static void filter_plane_rows(OCtx *c, int uv, int row, int ss_h, int ss_v, uint8_t *lvl, uint8_t (*mask)[4],
                               uint8_t *dst, ptrdiff_t ls)
 {
     int y, x, bypp = c->bypp;
+    if (lf_census) lf_census_pd = uv * 2 + 1;
     for (y = 0; y < 8; y++, dst += 8 * ls >> ss_v) {
         uint8_t *ptr = dst, *l = lvl, *vmask = mask[y];
         unsigned vm = vmask[0] | vmask[1] | vmask[2], vm3 = vmask[3];
@@ -956,12 +985,12 @@ static void loopfilter_sb(OCtx *c, VP9Filter *lflvl, int row, int col)
     uint8_t *dst = c->plane[0] + row * 8 * c->ls[0] + col * 8 * bypp;
     uint8_t (*uv_masks)[8][4] = lflvl->mask[c->ss_h | c->ss_v];
     int p;
-    filter_plane_cols(c, col, 0, 0, lflvl->level, lflvl->mask[0][0], dst, c->ls[0]);
-    filter_plane_rows(c, row, 0, 0, lflvl->level, lflvl->mask[0][1], dst, c->ls[0]);
+    filter_plane_cols(c, 0, col, 0, 0, lflvl->level, lflvl->mask[0][0], dst, c->ls[0]);
+    filter_plane_rows(c, 0, row, 0, 0, lflvl->level, lflvl->mask[0][1], dst, c->ls[0]);
     for (p = 0; p < 2; p++) {
         dst = c->plane[1 + p] + row * (8 >> c->ss_v) * c->ls[1] + col * (8 >> c->ss_h) * bypp;
-        filter_plane_cols(c, col, c->ss_h, c->ss_v, lflvl->level, uv_masks[0], dst, c->ls[1]);
-        filter_plane_rows(c, row, c->ss_h, c->ss_v, lflvl->level, uv_masks[1], dst, c->ls[1]);
+        filter_plane_cols(c, 1, col, c->ss_h, c->ss_v, lflvl->level, uv_masks[0], dst, c->ls[1]);
+        filter_plane_rows(c, 1, row, c->ss_h, c->ss_v, lflvl->level, uv_masks[1], dst, c->ls[1]);
     }
 }
 
@@ -1090,12 +1119,7 @@ static int frame_init(OCtx *c, const vp9h_frame *f, vp9o_planes *cur, const vp9o
     }
     /* lim/mblim LUT, vp9.c:673-686 */
     for (i = 1; i <= 63; i++) {
-        int limit = i;
-        if (sharp > 0) {
-            limit >>= (sharp + 3) >> 2;
-            limit = MIN(limit, 9 - sharp);
-        }
-        limit = MAX(limit, 1);
+        int limit = lf_lim(i, sharp);
         c->lim_lut[i] = limit;
         c->mblim_lut[i] = 2 * (i + 2) + limit;
     }

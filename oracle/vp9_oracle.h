@@ -45,6 +45,29 @@ int vp9o_decode_frame_tiles(const vp9h_frame *f, vp9o_planes *cur, const vp9o_pl
 void vp9o_set_intra_trace(int32_t *buf, size_t cap);
 size_t vp9o_intra_trace_count(void);
 
+/* Optional census of the loop filter's line routine (loop_filter, vp9dsp_template.c:1780-1889).
+ * While buf is set, every line it processes, from vp9o_decode_frame or vp9o_loop_filter, adds
+ * to buf, VP9O_LF_CENSUS_N int64 the caller zeroed:
+ *   count[plane class: luma, chroma][direction: column edge, row edge][coded width: 4, 8, 16]
+ *        [arm: off (fm false), n4 (4-wide without hev), h4 (4-wide with hev), f8 (7-tap),
+ *         f16 (15-tap)]                                                        60 cells
+ *   moved, same shape: the lines of the cell whose output differs from their input  60 cells
+ *   tight[plane class][10]: per comparison the lines where the deciding quantity equals its
+ *        threshold, then those where it is one above: the largest neighbour difference against
+ *        I (E's test passing), 2|p0-q0| + (|p1-q1|>>1) against E (I's test passing), the inner
+ *        flat maximum against F (filtered lines of width 8 and 16), the outer flat maximum
+ *        against F (width 16, inner flat), max(|p1-p0|, |q1-q0|) against H (lines that take the
+ *        4-wide arms)                                                          20 cells
+ * Plane class and direction are those of the frame path's filter_plane_cols / rows;
+ * vp9o_loop_filter counts as luma with its dir. The arm is decided a second time, from the
+ * pixels before the filter; pixels do not change. NULL ends it; off, a line costs one pointer
+ * test. Not for vp9o_decode_frame_tiles (one buffer, no lock). */
+#define VP9O_LF_CENSUS_N 140
+void vp9o_set_lf_census(int64_t *buf);
+/* E (mblim), I (lim), H (hev threshold) of a level as the frame path derives them (vp9.c:673-686,
+ * vp9lpf.c:49), before the shift to the bit depth. Level 0 is never filtered. */
+void vp9o_lf_limits(int level, int sharpness, int out[3]);
+
 /* DSP entry points for unit tests (stride in pixels). */
 void vp9o_itxfm_add(int bpp, void *dst, ptrdiff_t stride, void *coef, int eob, int tx, int txtp);
 void vp9o_intra_pred(int bpp, void *dst, ptrdiff_t stride, const void *left, const void *top,

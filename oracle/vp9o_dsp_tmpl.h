@@ -587,68 +587,116 @@ static void F(ipred)(PIX *dst, ptrdiff_t stride, const PIX *left, const PIX *top
 static inline int F(iabs)(int v) { return v < 0 ? -v : v; }
 static inline int F(clip_intp2)(int v, int p) { int lo = -(1 << p), hi = (1 << p) - 1; return v < lo ? lo : v > hi ? hi : v; }
 
+/* one line of loop_filter; E, I, H already shifted to the bit depth */
+static inline void F(lf_line)(PIX *dst, int E, int I, int H, ptrdiff_t strideb, int wd, int bd)
+{
+    const int Fl = 1 << (bd - 8);
+    int p7 = 0, p6 = 0, p5 = 0, p4 = 0, q4 = 0, q5 = 0, q6 = 0, q7 = 0;
+    int p3 = dst[strideb * -4], p2 = dst[strideb * -3], p1 = dst[strideb * -2], p0 = dst[strideb * -1];
+    int q0 = dst[strideb * +0], q1 = dst[strideb * +1], q2 = dst[strideb * +2], q3 = dst[strideb * +3];
+    int fm = F(iabs)(p3 - p2) <= I && F(iabs)(p2 - p1) <= I && F(iabs)(p1 - p0) <= I &&
+             F(iabs)(q1 - q0) <= I && F(iabs)(q2 - q1) <= I && F(iabs)(q3 - q2) <= I &&
+             F(iabs)(p0 - q0) * 2 + (F(iabs)(p1 - q1) >> 1) <= E;
+    int flat8out = 0, flat8in = 0;
+    if (!fm) return;
+    if (wd >= 16) {
+        p7 = dst[strideb * -8]; p6 = dst[strideb * -7]; p5 = dst[strideb * -6]; p4 = dst[strideb * -5];
+        q4 = dst[strideb * +4]; q5 = dst[strideb * +5]; q6 = dst[strideb * +6]; q7 = dst[strideb * +7];
+        flat8out = F(iabs)(p7 - p0) <= Fl && F(iabs)(p6 - p0) <= Fl && F(iabs)(p5 - p0) <= Fl &&
+                   F(iabs)(p4 - p0) <= Fl && F(iabs)(q4 - q0) <= Fl && F(iabs)(q5 - q0) <= Fl &&
+                   F(iabs)(q6 - q0) <= Fl && F(iabs)(q7 - q0) <= Fl;
+    }
+    if (wd >= 8)
+        flat8in = F(iabs)(p3 - p0) <= Fl && F(iabs)(p2 - p0) <= Fl && F(iabs)(p1 - p0) <= Fl &&
+                  F(iabs)(q1 - q0) <= Fl && F(iabs)(q2 - q0) <= Fl && F(iabs)(q3 - q0) <= Fl;
+    if (wd >= 16 && flat8out && flat8in) {
+        /* 15-tap smoothing: out[k] = (sum of the 16-tap window around k + 8) >> 4 */
+        int px[16] = { p7, p6, p5, p4, p3, p2, p1, p0, q0, q1, q2, q3, q4, q5, q6, q7 };
+        int k;
+        for (k = 1; k < 15; k++) {
+            int acc = 8, t;
+            for (t = k - 7; t <= k + 7; t++) acc += px[t < 0 ? 0 : t > 15 ? 15 : t];
+            acc += px[k];
+            dst[strideb * (k - 8)] = acc >> 4;
+        }
+    } else if (wd >= 8 && flat8in) {
+        dst[strideb * -3] = (p3 + p3 + p3 + 2 * p2 + p1 + p0 + q0 + 4) >> 3;
+        dst[strideb * -2] = (p3 + p3 + p2 + 2 * p1 + p0 + q0 + q1 + 4) >> 3;
+        dst[strideb * -1] = (p3 + p2 + p1 + 2 * p0 + q0 + q1 + q2 + 4) >> 3;
+        dst[strideb * +0] = (p2 + p1 + p0 + 2 * q0 + q1 + q2 + q3 + 4) >> 3;
+        dst[strideb * +1] = (p1 + p0 + q0 + 2 * q1 + q2 + q3 + q3 + 4) >> 3;
+        dst[strideb * +2] = (p0 + q0 + q1 + 2 * q2 + q3 + q3 + q3 + 4) >> 3;
+    } else {
+        int hev = F(iabs)(p1 - p0) > H || F(iabs)(q1 - q0) > H;
+        int mx = (1 << (bd - 1)) - 1;
+        if (hev) {
+            int f = F(clip_intp2)(p1 - q1, bd - 1), f1, f2;
+            f = F(clip_intp2)(3 * (q0 - p0) + f, bd - 1);
+            f1 = (f + 4 < mx ? f + 4 : mx) >> 3;
+            f2 = (f + 3 < mx ? f + 3 : mx) >> 3;
+            dst[strideb * -1] = F(clip_px)(p0 + f2, bd);
+            dst[strideb * +0] = F(clip_px)(q0 - f1, bd);
+        } else {
+            int f = F(clip_intp2)(3 * (q0 - p0), bd - 1), f1, f2;
+            f1 = (f + 4 < mx ? f + 4 : mx) >> 3;
+            f2 = (f + 3 < mx ? f + 3 : mx) >> 3;
+            dst[strideb * -1] = F(clip_px)(p0 + f2, bd);
+            dst[strideb * +0] = F(clip_px)(q0 - f1, bd);
+            f = (f1 + 1) >> 1;
+            dst[strideb * -2] = F(clip_px)(p1 + f, bd);
+            dst[strideb * +1] = F(clip_px)(q1 - f, bd);
+        }
+    }
+}
+
+/* vp9o_set_lf_census (vp9_oracle.h): the line's arm, decided here a second time from the
+ * pixels before the filter, whether the filter changed it, and the comparisons that sat at
+ * their threshold or one above it. Layout: count[2][2][3][5], moved[2][2][3][5], tight[2][10]. */
+static void F(lf_census_line)(PIX *dst, int E, int I, int H, ptrdiff_t strideb, int wd, int bd)
+{
+    const int Fl = 1 << (bd - 8), n = wd >= 16 ? 8 : 4;
+    int v[16] = { 0 }, k, mi = 0, fin = 0, fout = 0, ev, hv, fm, f8, f16, arm, cell, moved = 0;
+    int64_t *t = lf_census + 120 + 10 * (lf_census_pd >> 1);
+    for (k = -n; k < n; k++) v[8 + k] = dst[strideb * k];
+    for (k = 0; k < 3; k++) {
+        int a = F(iabs)(v[4 + k] - v[5 + k]), b = F(iabs)(v[8 + k] - v[9 + k]);
+        int c = F(iabs)(v[4 + k] - v[7]), d = F(iabs)(v[9 + k] - v[8]);
+        if (a > mi) mi = a;
+        if (b > mi) mi = b;
+        if (c > fin) fin = c;
+        if (d > fin) fin = d;
+    }
+    for (k = 0; k < 4 && wd >= 16; k++) {
+        int c = F(iabs)(v[k] - v[7]), d = F(iabs)(v[12 + k] - v[8]);
+        if (c > fout) fout = c;
+        if (d > fout) fout = d;
+    }
+    ev = F(iabs)(v[7] - v[8]) * 2 + (F(iabs)(v[6] - v[9]) >> 1);
+    hv = F(iabs)(v[6] - v[7]) > F(iabs)(v[9] - v[8]) ? F(iabs)(v[6] - v[7]) : F(iabs)(v[9] - v[8]);
+    fm = mi <= I && ev <= E;
+    f8 = fm && wd >= 8 && fin <= Fl;
+    f16 = f8 && wd >= 16 && fout <= Fl;
+    arm = !fm ? 0 : f16 ? 4 : f8 ? 3 : hv > H ? 2 : 1;
+    F(lf_line)(dst, E, I, H, strideb, wd, bd);
+    for (k = -n; k < n; k++) moved |= dst[strideb * k] != v[8 + k];
+    cell = (lf_census_pd * 3 + (wd >> 3)) * 5 + arm;
+    lf_census[cell]++;
+    lf_census[60 + cell] += moved;
+    if (ev <= E) { t[0] += mi == I; t[1] += mi == I + 1; }
+    if (mi <= I) { t[2] += ev == E; t[3] += ev == E + 1; }
+    if (fm && wd >= 8) { t[4] += fin == Fl; t[5] += fin == Fl + 1; }
+    if (f8 && wd >= 16) { t[6] += fout == Fl; t[7] += fout == Fl + 1; }
+    if (fm && !f8) { t[8] += hv == H; t[9] += hv == H + 1; }
+}
+
 static void F(loop_filter)(PIX *dst, int E, int I, int H, ptrdiff_t stridea, ptrdiff_t strideb,
                            int wd, int bd)
 {
-    int i, Fl = 1 << (bd - 8);
+    int i;
     E <<= (bd - 8); I <<= (bd - 8); H <<= (bd - 8);
     for (i = 0; i < 8; i++, dst += stridea) {
-        int p7 = 0, p6 = 0, p5 = 0, p4 = 0, q4 = 0, q5 = 0, q6 = 0, q7 = 0;
-        int p3 = dst[strideb * -4], p2 = dst[strideb * -3], p1 = dst[strideb * -2], p0 = dst[strideb * -1];
-        int q0 = dst[strideb * +0], q1 = dst[strideb * +1], q2 = dst[strideb * +2], q3 = dst[strideb * +3];
-        int fm = F(iabs)(p3 - p2) <= I && F(iabs)(p2 - p1) <= I && F(iabs)(p1 - p0) <= I &&
-                 F(iabs)(q1 - q0) <= I && F(iabs)(q2 - q1) <= I && F(iabs)(q3 - q2) <= I &&
-                 F(iabs)(p0 - q0) * 2 + (F(iabs)(p1 - q1) >> 1) <= E;
-        int flat8out = 0, flat8in = 0;
-        if (!fm) continue;
-        if (wd >= 16) {
-            p7 = dst[strideb * -8]; p6 = dst[strideb * -7]; p5 = dst[strideb * -6]; p4 = dst[strideb * -5];
-            q4 = dst[strideb * +4]; q5 = dst[strideb * +5]; q6 = dst[strideb * +6]; q7 = dst[strideb * +7];
-            flat8out = F(iabs)(p7 - p0) <= Fl && F(iabs)(p6 - p0) <= Fl && F(iabs)(p5 - p0) <= Fl &&
-                       F(iabs)(p4 - p0) <= Fl && F(iabs)(q4 - q0) <= Fl && F(iabs)(q5 - q0) <= Fl &&
-                       F(iabs)(q6 - q0) <= Fl && F(iabs)(q7 - q0) <= Fl;
-        }
-        if (wd >= 8)
-            flat8in = F(iabs)(p3 - p0) <= Fl && F(iabs)(p2 - p0) <= Fl && F(iabs)(p1 - p0) <= Fl &&
-                      F(iabs)(q1 - q0) <= Fl && F(iabs)(q2 - q0) <= Fl && F(iabs)(q3 - q0) <= Fl;
-        if (wd >= 16 && flat8out && flat8in) {
-            /* 15-tap smoothing: out[k] = (sum of the 16-tap window around k + 8) >> 4 */
-            int px[16] = { p7, p6, p5, p4, p3, p2, p1, p0, q0, q1, q2, q3, q4, q5, q6, q7 };
-            int k;
-            for (k = 1; k < 15; k++) {
-                int acc = 8, t;
-                for (t = k - 7; t <= k + 7; t++) acc += px[t < 0 ? 0 : t > 15 ? 15 : t];
-                acc += px[k];
-                dst[strideb * (k - 8)] = acc >> 4;
-            }
-        } else if (wd >= 8 && flat8in) {
-            dst[strideb * -3] = (p3 + p3 + p3 + 2 * p2 + p1 + p0 + q0 + 4) >> 3;
-            dst[strideb * -2] = (p3 + p3 + p2 + 2 * p1 + p0 + q0 + q1 + 4) >> 3;
-            dst[strideb * -1] = (p3 + p2 + p1 + 2 * p0 + q0 + q1 + q2 + 4) >> 3;
-            dst[strideb * +0] = (p2 + p1 + p0 + 2 * q0 + q1 + q2 + q3 + 4) >> 3;
-            dst[strideb * +1] = (p1 + p0 + q0 + 2 * q1 + q2 + q3 + q3 + 4) >> 3;
-            dst[strideb * +2] = (p0 + q0 + q1 + 2 * q2 + q3 + q3 + q3 + 4) >> 3;
-        } else {
-            int hev = F(iabs)(p1 - p0) > H || F(iabs)(q1 - q0) > H;
-            int mx = (1 << (bd - 1)) - 1;
-            if (hev) {
-                int f = F(clip_intp2)(p1 - q1, bd - 1), f1, f2;
-                f = F(clip_intp2)(3 * (q0 - p0) + f, bd - 1);
-                f1 = (f + 4 < mx ? f + 4 : mx) >> 3;
-                f2 = (f + 3 < mx ? f + 3 : mx) >> 3;
-                dst[strideb * -1] = F(clip_px)(p0 + f2, bd);
-                dst[strideb * +0] = F(clip_px)(q0 - f1, bd);
-            } else {
-                int f = F(clip_intp2)(3 * (q0 - p0), bd - 1), f1, f2;
-                f1 = (f + 4 < mx ? f + 4 : mx) >> 3;
-                f2 = (f + 3 < mx ? f + 3 : mx) >> 3;
-                dst[strideb * -1] = F(clip_px)(p0 + f2, bd);
-                dst[strideb * +0] = F(clip_px)(q0 - f1, bd);
-                f = (f1 + 1) >> 1;
-                dst[strideb * -2] = F(clip_px)(p1 + f, bd);
-                dst[strideb * +1] = F(clip_px)(q1 - f, bd);
-            }
-        }
+        if (lf_census) F(lf_census_line)(dst, E, I, H, strideb, wd, bd);
+        else F(lf_line)(dst, E, I, H, strideb, wd, bd);
     }
 }
 
