@@ -157,7 +157,9 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9hip_decoder_convert", "vp9hip_convert_frames_scaled", "vp9hip_decoder_convert_scaled",
                "vp9hip_convert_frames_resampled", "vp9hip_decoder_convert_resampled", "vp9hip_resample_weights",
                "vp9hip_convert_frames_bicubic", "vp9hip_decoder_convert_bicubic", "vp9hip_bicubic_weights",
-               "vp9hip_frame_metrics", "vp9hip_frame_metrics_host", "vp9hip_decoder_metrics"]
+               "vp9hip_frame_metrics", "vp9hip_frame_metrics_host", "vp9hip_decoder_metrics",
+               "vp9hip_resid_layout", "vp9hip_residual_frames_scaled", "vp9hip_residual_scaled_host",
+               "vp9hip_decoder_residual_scaled"]
 
 
 def lib():
@@ -338,6 +340,15 @@ def lib():
                                        ctypes.POINTER(ctypes.c_int * 3)]
     L.vp9hip_residual_relaunch.argtypes = [vp, ctypes.c_void_p]
     L.vp9hip_decoder_frame_residual.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), vp3, i64p3]
+    # residual tensors at model size
+    L.vp9hip_resid_layout.restype = ctypes.c_int64
+    L.vp9hip_resid_layout.argtypes = [ctypes.POINTER(ResidDesc), ctypes.POINTER(ctypes.c_int64)]
+    L.vp9hip_residual_frames_scaled.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ResidDesc),
+                                                ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_residual_scaled_host.argtypes = [vp3, ctypes.POINTER(ctypes.c_ssize_t * 3)] + [ctypes.c_int] * 5 + \
+                                             [ctypes.POINTER(ResidDesc), ctypes.c_void_p]
+    L.vp9hip_decoder_residual_scaled.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int,
+                                                 ctypes.POINTER(ResidDesc), ctypes.c_void_p, ctypes.c_void_p]
     # frame metrics
     L.vp9hip_frame_metrics.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -386,6 +397,13 @@ class OutDesc(ctypes.Structure):
                 ("frame_stride", ctypes.c_int64)]
 
 
+class ResidDesc(ctypes.Structure):
+    """vp9hip_resid_desc: the format and layout of residual tensors at model size."""
+    _fields_ = [("format", ctypes.c_int32), ("colorspace", ctypes.c_int32), ("full_range", ctypes.c_int32),
+                ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32), ("pitch", ctypes.c_int64),
+                ("frame_stride", ctypes.c_int64)]
+
+
 class Rect(ctypes.Structure):
     """vp9hip_rect: (x, y, w, h) in luma samples."""
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32)]
@@ -399,6 +417,8 @@ class Resample(ctypes.Structure):
 
 # VP9HIP_OUT_*: the names Device.convert / Decoder.convert take
 OUT_FORMATS = {"semiplanar": 0, "rgb24": 1, "rgbp_u8": 2, "rgbp_f16": 3}
+# VP9HIP_RESID_*: the names Device.residual_tensors / Decoder.residual_tensors take
+RESID_FORMATS = {"yuv_i16": 0, "yuv_f16": 1, "rgb_i16": 2, "rgb_f16": 3}
 # VP9HIP_FILTER_*: the names of their filter argument
 FILTERS = {"box": 0, "triangle": 1}
 # VP9HIP_FILTER_BICUBIC, filter="bicubic": entries of its own (vp9hip_convert_frames_bicubic)
@@ -901,6 +921,69 @@ def _residual_views(ptrs, pitch, width, height, ss_h, ss_v, device):
     return out
 
 
+def _resid_desc(fn, fmt, resize, size, colorspace, full_range, pitch, frame_stride):
+    """The ResidDesc of a residual_tensors call: resize=None is the field's own size."""
+    ow, oh = (int(x) for x in (resize if resize is not None else size))
+    return ResidDesc(RESID_FORMATS[fmt], int(colorspace), int(bool(full_range)), ow, oh, int(pitch), int(frame_stride))
+
+
+def residual_scaled_host(planes, width, height, ss_h, ss_v, bpp, fmt, resize, colorspace=2, full_range=False):
+    """The residual tensor of one frame on the host, vp9hip_residual_scaled_host, the C statement
+    of the definition in include/vp9hip.h ("residual tensors at model size"): planes are three
+    2-D int16 arrays (rows may be strided) holding at least the visible width x height luma and
+    the chroma samples they cover; the result is a (3, OH, OW) int16 or float16 array, fmt a key
+    of RESID_FORMATS, resize = (OW, OH) or None for the field's own size."""
+    pl = []
+    for a in planes:
+        a = np.asarray(a)
+        if a.ndim != 2 or a.dtype != np.int16:
+            raise ValueError("residual_scaled_host: planes must be 2-D int16 arrays")
+        if a.strides[1] != 2 or a.strides[0] < 0 or a.strides[0] % 2:
+            a = np.ascontiguousarray(a)
+        pl.append(a)
+    if len(pl) != 3:
+        raise ValueError("residual_scaled_host: three planes a frame")
+    d = _resid_desc("vp9hip_residual_scaled_host", fmt, resize, (width, height), colorspace, full_range, 0, 0)
+    sane = 1 <= width <= 16384 and 1 <= height <= 16384 and ss_h in (0, 1) and ss_v in (0, 1)
+    if sane:                                          # what the library refuses it does not read
+        for p, a in enumerate(pl):
+            pw, ph = (width, height) if p == 0 else ((width + ss_h) >> ss_h, (height + ss_v) >> ss_v)
+            if a.shape[0] < ph or a.shape[1] < pw:
+                raise ValueError("residual_scaled_host: plane %d is smaller than %d x %d" % (p, pw, ph))
+    ok = 1 <= d.out_width <= 16384 and 1 <= d.out_height <= 16384
+    out = np.full((3, d.out_height, d.out_width) if ok else (3, 1, 1), 0x5a5a, np.int16)
+    ptrs = (ctypes.c_void_p * 3)(*[a.ctypes.data for a in pl])
+    pitch = (ctypes.c_ssize_t * 3)(*[a.strides[0] // 2 for a in pl])
+    _check("vp9hip_residual_scaled_host",
+           lib().vp9hip_residual_scaled_host(ctypes.byref(ptrs), ctypes.byref(pitch), int(width), int(height), int(ss_h),
+                                             int(ss_v), int(bpp), ctypes.byref(d), out.ctypes.data))
+    return out.view(np.float16) if fmt.endswith("f16") else out
+
+
+def _resid_out(n, d, out):
+    """The destination of a residual_tensors call: (flat storage tensor, (N, 3, OH, OW) view of
+    it). The storage is allocated, or `out` itself: a contiguous int16 or float16 cuda tensor (by
+    the format) of at least the layout's elements. A descriptor the library refuses gets one
+    element to hand it, so the refusal is the library's."""
+    import torch
+    dt = torch.float16 if d.format & 1 else torch.int16
+    pitch = ctypes.c_int64()
+    nbytes = lib().vp9hip_resid_layout(ctypes.byref(d), ctypes.byref(pitch))
+    if nbytes < 0:
+        flat = out.view(-1) if out is not None else torch.empty(1, dtype=dt, device="cuda")
+        return flat, None
+    stride = d.frame_stride or nbytes
+    total = ((max(n, 1) - 1) * stride + nbytes) // 2
+    if out is None:
+        out = torch.empty(total, dtype=dt, device="cuda")
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == dt and out.is_contiguous()
+              and out.numel() >= total):
+        raise ValueError("residual_tensors: out must be a contiguous %s cuda tensor of at least %d elements" % (dt, total))
+    flat = out.view(-1)
+    return flat, flat.as_strided((max(n, 0), 3, d.out_height, d.out_width),
+                                 (stride // 2, pitch.value * d.out_height // 2, pitch.value // 2, 1))
+
+
 METRIC_FIELDS = ("sum_a", "sum_b", "sumsq_a", "sad", "sse", "ndiff", "maxdiff", "first")   # VP9HIP_METRIC_*
 METRIC_CELL = 16               # VP9HIP_METRIC_CELL
 
@@ -1098,6 +1181,46 @@ class Device:
         ptrs, ls = _plane_ptrs(planes)
         _check("vp9hip_download_residual", lib().vp9hip_download_residual(self._c, buf, ctypes.byref(ptrs), ctypes.byref(ls)))
         return planes
+
+    def residual_tensors(self, bufs, fmt, resize=None, colorspace=2, full_range=False, out=None, stream=None,
+                         pitch=0, frame_stride=0):
+        """The residual fields of device buffers `bufs` (any order, repeats allowed, all of one
+        visible size) as one (N, 3, OH, OW) cuda tensor at the model's size, made on the GPU in
+        one launch per 32 frames (vp9hip_residual_frames_scaled, the definition in
+        include/vp9hip.h "residual tensors at model size"): cropped to the visible size, all
+        three planes box-resampled to resize = (OW, OH) with the exact signed box filter (None:
+        the field's own size, the identity, through the same kernel), and by fmt "yuv_i16" the
+        planes y, u, v as int16, "rgb_i16" the RGB residual of the colour matrix `colorspace`
+        (the VP9 code, 1..5, 7 = RGB planes) / full_range clipped to [-m, m], m = 2^bpp - 1, or
+        "yuv_f16" / "rgb_f16" the same values times 1 / m as float16. `out` is a contiguous
+        int16 / float16 cuda tensor to write into (else one is allocated); pitch / frame_stride
+        in bytes as in vp9hip_resid_desc (0 = tight), the result then strided over them. Runs in
+        the order of torch's current stream (or on `stream`, a hipStream_t handle; see
+        _enqueue_for_torch) and does not wait: order it after the fields' producer (sync(), or
+        vp9hip_slot_stream_wait), as for convert. Needs torch imported before the library was
+        loaded (see _torch_first)."""
+        fn = "vp9hip_residual_frames_scaled"
+        if not _torch_first:
+            raise Vp9HipUnavailable("residual_tensors: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        bufs = [int(b) for b in bufs]
+        if not bufs:
+            raise Vp9HipError(fn, EINVAL)
+        size = (1, 1)
+        if resize is None:
+            size = self.frame_residual(bufs[0])[2]
+        d = _resid_desc(fn, fmt, resize, size, colorspace, full_range, pitch, frame_stride)
+        flat, res = _resid_out(len(bufs), d, out)
+        arr = (ctypes.c_int * len(bufs))(*bufs)
+        call = lambda st: lib().vp9hip_residual_frames_scaled(self._c, arr, len(bufs), ctypes.byref(d), flat.data_ptr(), st)
+        main = ctypes.c_void_p()
+        # an unconfigured context has no buffer to ask for its stream: the library refuses the call itself
+        if lib().vp9hip_frame_device(self._c, 0, (ctypes.c_void_p * 3)(), (ctypes.c_ssize_t * 3)(), None, None,
+                                     ctypes.byref(main)):
+            _check(fn, call(stream))
+        else:
+            _check(fn, _enqueue_for_torch(main.value, stream, call))
+        return res
 
     def frame_motion(self, buf):
         """The field of buffer `buf` in place (vp9hip_frame_motion): (mv pointer, info pointer,
@@ -1600,6 +1723,33 @@ class Decoder:
         _check("vp9hip_download_residual",
                lib().vp9hip_download_residual(self.context(), info.buf, ctypes.byref(hp), ctypes.byref(ls)))
         return planes
+
+    def residual_tensors(self, infos, fmt, resize=None, out=None):
+        """The residual fields of frames of receive_frame(download=False) (their
+        DecodedFrameInfos, all of one size, depth, subsampling, colour space and range, all still
+        held) as Device.residual_tensors returns them, with the frames' own colour description
+        (vp9hip_decoder_residual_scaled; needs export_residual=True), on torch's current stream;
+        waits for it. Unlike Decoder.convert it releases nothing: the pixels and the motion of
+        the same frames are usually wanted too."""
+        fn = "vp9hip_decoder_residual_scaled"
+        if not _torch_first:
+            raise Vp9HipUnavailable("residual_tensors: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        import torch
+        infos = list(infos)
+        if not infos:
+            raise Vp9HipError(fn, EINVAL)
+        f = infos[0]
+        d = _resid_desc(fn, fmt, resize, (f.width, f.height), -1, 0, 0, 0)
+        flat, res = _resid_out(len(infos), d, out)
+        arr = (DecodedFrameInfo * len(infos))(*infos)
+        main = ctypes.c_void_p()
+        _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
+                                                                (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
+        call = lambda st: lib().vp9hip_decoder_residual_scaled(self._d, arr, len(infos), ctypes.byref(d), flat.data_ptr(), st)
+        _check(fn, _enqueue_for_torch(main.value, None, call))
+        torch.cuda.current_stream().synchronize()
+        return res
 
     def convert(self, infos, fmt, out=None, resize=None, filter="box", src_rects=None, dst_rects=None, fill=None):
         """Convert the frames of receive_frame(download=False) (their DecodedFrameInfos, all of

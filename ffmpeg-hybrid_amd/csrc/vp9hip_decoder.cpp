@@ -492,6 +492,32 @@ extern "C" int vp9hip_decoder_frame_residual(vp9hip_decoder *d, const vp9hip_dec
     return vp9hip_frame_residual(d->ctx, f->buf, planes, pitch, nullptr, nullptr, nullptr);
 }
 
+// The residual tensors of received frames (vp9hip_residual_frames_scaled). The frames are
+// complete and stay the caller's: nothing is ordered and nothing released here. A
+// show_existing_frame output holds the buffer of the frame it shows, and with it that frame's field.
+extern "C" int vp9hip_decoder_residual_scaled(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n,
+                                              const vp9hip_resid_desc *desc, void *dst_dev, void *stream)
+{
+    if (!d || !frames || n <= 0 || !desc || !d->configured || !(d->export_flags & VP9HIP_EXPORT_RESIDUAL)) return VP9HIP_EINVAL;
+    std::vector<int> bufs(n);
+    const vp9hip_decoded_frame &f0 = frames[0];
+    const bool own = desc->colorspace < 0;
+    for (int i = 0; i < n; i++) {
+        const vp9hip_decoded_frame &f = frames[i];
+        if (f.buf < 0 || f.buf >= d->nbufs || d->pins[f.buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+        if (f.width != f0.width || f.height != f0.height || f.bpp != f0.bpp || f.ss_h != f0.ss_h || f.ss_v != f0.ss_v)
+            return VP9HIP_EINVAL;
+        if (own && (f.colorspace != f0.colorspace || f.full_range != f0.full_range)) return VP9HIP_EINVAL;
+        bufs[i] = f.buf;
+    }
+    vp9hip_resid_desc o = *desc;
+    if (own) {
+        o.colorspace = f0.colorspace == 0 || f0.colorspace == 6 ? 2 : f0.colorspace;   // unknown / reserved: BT.709
+        o.full_range = f0.full_range;
+    }
+    return vp9hip_residual_frames_scaled(d->ctx, bufs.data(), n, &o, dst_dev, stream);
+}
+
 // avcodec_flush_buffers (vp9.c:1865-1883): drop the decoder delay and the reference
 // state; frames already handed out stay valid until released.
 extern "C" int vp9hip_decoder_flush(vp9hip_decoder *d)

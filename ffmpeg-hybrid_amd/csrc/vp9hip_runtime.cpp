@@ -47,6 +47,7 @@
 #include "vp9hip_mvacc.h"
 #include "vp9hip_residual.h"
 #include "vp9hip_metrics.h"
+#include "vp9hip_residual_scale.h"
 #include "vp9hip_residn.h"
 
 extern "C" {
@@ -4041,6 +4042,55 @@ extern "C" int vp9hip_plan_stats(const vp9h_frame *f, double *out, int cap)
                 out[22] += (double) rows * lines * 128;
             }
         }
+    }
+    return 0;
+}
+
+// Residual tensors at model size (include/vp9hip.h "residual tensors at model size";
+// k_residual_scale in vp9hip_residual_scale.hip): the fields of bufs[0 .. n-1] into dst_dev,
+// enqueued on `stream` (NULL: the current slot's main stream). Everything is validated before
+// the first launch, so a refused call writes nothing. The fields' pointers travel as kernel
+// arguments, RSC_MAX_FRAMES per launch, like the conversion's: no device table, no copy,
+// nothing to free.
+extern "C" int vp9hip_residual_frames_scaled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_resid_desc *d,
+                                             void *dst_dev, void *stream)
+{
+    if (!c || c->res.empty() || !bufs || n <= 0 || !d || !dst_dev || ((uintptr_t) dst_dev & 1)) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (bufs[i] < 0 || bufs[i] >= (int) c->res.size()) return VP9HIP_EINVAL;
+    int64_t pitch = 0;
+    const int64_t bytes = vp9hip_resid_layout(d, &pitch);
+    if (bytes < 0) return VP9HIP_EINVAL;
+    ResidScaleArgs a;
+    memset(&a, 0, sizeof(a));
+    if (d->format == VP9HIP_RESID_RGB_I16 || d->format == VP9HIP_RESID_RGB_F16) {
+        if (vp9hip_out_coefs(d->colorspace, d->full_range, c->bpp, c->bpp, a.c, &a.shift) < 0) return VP9HIP_EINVAL;
+        a.rgb = d->colorspace == 7;
+        a.rnd = a.shift > 0 ? 1 << (a.shift - 1) : 0;
+    }
+    for (int i = 0; i < n; i++) {
+        if (!c->res_wh[bufs[i]].first) return VP9HIP_EAGAIN;
+        if (c->res_wh[bufs[i]] != c->res_wh[bufs[0]]) return VP9HIP_EINVAL;
+    }
+    const int64_t stride = d->frame_stride ? d->frame_stride : bytes;
+    a.frame_stride = stride; a.pitch = pitch; a.plane = pitch * d->out_height;
+    for (int p = 0; p < 3; p++) a.src_off[p] = (int64_t) (c->plane_off[p] / c->bypp * 2);
+    a.src_pitch[0] = c->pitch[0] * 2; a.src_pitch[1] = c->pitch[1] * 2;
+    a.w = c->res_wh[bufs[0]].first; a.h = c->res_wh[bufs[0]].second;
+    a.cw = (a.w + c->ss_h) >> c->ss_h; a.ch = (a.h + c->ss_v) >> c->ss_v;
+    a.ow = d->out_width; a.oh = d->out_height;
+    a.maxv = (1 << c->bpp) - 1;
+    a.fscale = (float) (1.0 / a.maxv);
+    a.rcp[0] = 1.0 / ((double) a.w * (double) a.h);
+    a.rcp[1] = 1.0 / ((double) a.cw * (double) a.ch);
+    a.rx = 1.0 / a.ow; a.ry = 1.0 / a.oh;
+    hipSetDevice(c->dev);
+    hipStream_t st = stream ? (hipStream_t) stream : c->st;
+    for (int i0 = 0; i0 < n; i0 += RSC_MAX_FRAMES) {
+        const int k = std::min(n - i0, RSC_MAX_FRAMES);
+        for (int i = 0; i < k; i++) a.src[i] = c->res[bufs[i0 + i]];
+        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
+        HIPCHK(vp9hip_residual_scale_launch(a, d->format, k, st));
     }
     return 0;
 }

@@ -50,7 +50,10 @@ extern "C" {
  * vp9hip_download_residual, vp9hip_residual_host, vp9hip_decoder_frame_residual) likewise: new
  * symbols only. Accumulated motion (VP9HIP_EXPORT_MOTION_ACC, vp9hip_acc_cell,
  * vp9hip_frame_motion_acc, vp9hip_download_motion_acc, vp9hip_motion_acc_host,
- * vp9hip_decoder_frame_motion_acc) likewise: a new macro, a new struct and new symbols. */
+ * vp9hip_decoder_frame_motion_acc) likewise: a new macro, a new struct and new symbols. The
+ * residual tensors at model size (VP9HIP_RESID_*, vp9hip_resid_desc,
+ * vp9hip_residual_frames_scaled, vp9hip_residual_scaled_host, vp9hip_decoder_residual_scaled)
+ * likewise: a new enum, a new struct and new symbols. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -692,6 +695,86 @@ int  vp9hip_download_residual(vp9hip_ctx *ctx, int buf, int16_t *const planes[3]
  * NULL arguments, a packet without a size or format, or planes smaller than the coded area. */
 int  vp9hip_residual_host(const vp9h_frame *pkt, int16_t *const planes[3], const ptrdiff_t pitch[3], const int rows[3]);
 
+/* ---- residual tensors at model size: signed box resize and the RGB matrix, fused ----
+ * What a CoViAR-style consumer reads is an (N, 3, OH, OW) residual tensor, usually RGB, at the
+ * model's size. One launch per 32 frames (k_residual_scale) makes it from the fields above:
+ * crop to the visible size, exact box resize, optionally the colour matrix, int16 or half.
+ *
+ * Definition, in integers.
+ * Source: the field of a buffer as vp9hip_frame_residual reports it: the visible w x h luma
+ * samples of the frame last exported into it and the cw x ch chroma samples,
+ * cw = (w + ss_h) >> ss_h, ch = (h + ss_v) >> ss_v. Samples are the stored int16 codes,
+ * whatever they are: the definition holds for every int16 value, so a consumer that wrote into
+ * the views gets a defined result. Samples of the coded area beyond the visible size, and of the
+ * padding, never enter a sum.
+ * Signed box: sbox(P, ow, oh) of a w x h plane uses the weights wx, wy of box ("Box-filter
+ * resize" above) unchanged:
+ *   A(ox, oy) = sum_sy wy(oy, sy) sum_sx wx(ox, sx) P[sy][sx]     exact, |A| <= 2^15 2^28
+ *   sbox      = floor((A + (w h >> 1)) / (w h))
+ * The division floors toward minus infinity, so negative means round half up as well:
+ * -2.5 -> -2, -2.25 -> -2. The weights of one output sample sum to w h, so
+ * sbox(P + c) = sbox(P) + c for every constant c, and sbox(P) = box(P + 32768) - 32768: with the
+ * sign bit of every stored sample flipped the source is a u16 plane for which the bounds of box
+ * hold as they stand (column sums below 2^30, quotient below 2^16). An implementation may use
+ * either form; both give the floor.
+ * Resampling: all three planes are resampled to OW x OH, as the RGB formats of the scaled
+ * conversion do: chroma covers the same picture area as luma. Call the results y, u, v.
+ * Formats:
+ *   VP9HIP_RESID_YUV_I16  the planes y, u, v.
+ *   VP9HIP_RESID_RGB_I16  with (CY, CRV, CGU, CGV, CBU), S of vp9hip_out_coefs(colorspace,
+ *     full_range, bpp, bpp) and m = 2^bpp - 1:
+ *       R = clip((CY y + CRV v + 2^(S-1)) >> S, -m, m)
+ *       G = clip((CY y - CGU u - CGV v + 2^(S-1)) >> S, -m, m)
+ *       B = clip((CY y + CBU u + 2^(S-1)) >> S, -m, m)
+ *     with arithmetic shifts and no offsets (the pixel's and its prediction's cancel).
+ *     colorspace 7 (RGB planes) is R = v, G = y, B = u, clipped alike; 0 and 6 are VP9HIP_EINVAL.
+ *     Every sum fits int32 for every int16 input: the largest CY + CBU (and CY + CGU + CGV) over
+ *     all matrices and depths is 54,367, and 54,367 x 32,768 + 2^13 < 2^31.
+ *   VP9HIP_RESID_YUV_F16, VP9HIP_RESID_RGB_F16  half(float(x) * float(1.0 / m)) of the integer
+ *     value: one float32 multiply and one round-to-nearest-even conversion, as VP9HIP_OUT_RGBP_F16.
+ *     RGB lies in [-1, 1]; YUV does for fields the decoder wrote. Other scalings are the caller's.
+ * What the RGB residual is: for a pixel and a prediction that both convert without clipping,
+ * RGB(pred + r) - RGB(pred) differs from the matrix of r by at most one code per channel (two
+ * floors of sums that differ by the linear part), at the same size with chroma at full
+ * resolution, for every matrix, range and depth.
+ * Not offered: the triangle and bicubic filters, source / destination rectangles, motion fields
+ * at model size, energy maps. */
+enum { VP9HIP_RESID_YUV_I16, VP9HIP_RESID_YUV_F16, VP9HIP_RESID_RGB_I16, VP9HIP_RESID_RGB_F16 };
+/* The output of n frames: planar (n, 3, OH, OW) 16-bit elements; plane p of frame i starts at
+ * dst + i frame_stride + p pitch OH. */
+typedef struct vp9hip_resid_desc {
+    int32_t format;            /* VP9HIP_RESID_* */
+    int32_t colorspace;        /* VP9 code; ignored by the YUV formats */
+    int32_t full_range;
+    int32_t out_width, out_height;   /* 1..16384 */
+    int64_t pitch;             /* bytes per output row, 0 = tight (2 OW); else a multiple of 16, >= 2 OW */
+    int64_t frame_stride;      /* bytes between frames, 0 = tight (3 pitch OH); else even, >= 3 pitch OH */
+} vp9hip_resid_desc;
+/* Bytes of one frame of d (3 pitch OH) and the pitch in effect, or VP9HIP_EINVAL for a format
+ * outside the enum, an output size outside 1..16384 or a pitch / frame stride the comments above
+ * exclude. Host only; the colour fields are not looked at. */
+int64_t vp9hip_resid_layout(const vp9hip_resid_desc *d, int64_t *pitch);
+/* The fields of bufs[0 .. n-1] (any order, repeats allowed) into dst_dev. Every buffer must hold
+ * a field and all fields must be of one visible size. Enqueues on `stream` (NULL: the current
+ * slot's main stream) and returns; it orders nothing itself, exactly as vp9hip_convert_frames.
+ * The buffers' pointers travel as kernel arguments, 32 frames per launch: no device table, no
+ * allocation, no host wait, so the call can sit in a captured stream. Only the OW x OH elements
+ * of each plane are written. Everything is checked before the first launch: a refused call
+ * writes nothing. VP9HIP_EINVAL: no residual flag, a buffer index out of range, n <= 0, NULL
+ * bufs or desc, fields of different sizes, a format outside the enum, colorspace 0, 6 or outside
+ * 1..7 with an RGB format, an output size outside 1..16384, a NULL or odd dst_dev, a pitch or
+ * frame stride the struct's comments exclude. VP9HIP_EAGAIN: a buffer without a field. */
+int  vp9hip_residual_frames_scaled(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip_resid_desc *d,
+                                   void *dst_dev, void *stream);
+/* Host only, no device: the C statement of the definition above for one frame, one output
+ * sample at a time in 64-bit integers. planes[p] are int16 planes of pitch[p] elements a row
+ * holding at least the visible width x height (chroma: cw x ch) samples, which are all it reads;
+ * dst is the frame's output in host memory, laid out by d (frame_stride is checked, not used).
+ * VP9HIP_EINVAL: NULL arguments, width / height outside 1..16384, ss not 0 / 1, bpp not 8 / 10 /
+ * 12, and what vp9hip_residual_frames_scaled refuses of d and dst; a refused call writes nothing. */
+int  vp9hip_residual_scaled_host(const int16_t *const planes[3], const ptrdiff_t pitch[3], int width, int height,
+                                 int ss_h, int ss_v, int bpp, const vp9hip_resid_desc *d, void *dst);
+
 /* ---- frame metrics: exact sums over two device frames ---------------------------------
  * What a consumer needs to decide which frames are worth converting: near-duplicate and scene
  * cut detection (FFmpeg's scene score is the mean luma SAD of consecutive frames), PSNR against
@@ -1140,6 +1223,15 @@ int  vp9hip_decoder_frame_motion_acc(vp9hip_decoder *d, const vp9hip_decoded_fra
  * a frame the caller does not hold. */
 int  vp9hip_decoder_frame_residual(vp9hip_decoder *d, const vp9hip_decoded_frame *frame, void *planes[3],
                                    int64_t pitch[3]);
+/* The residual tensors of received frames through vp9hip_residual_frames_scaled, under the
+ * rules of vp9hip_decoder_metrics: every frame must be of one size, depth and subsampling and
+ * held by the caller, else VP9HIP_EINVAL; it only enqueues and releases nothing. With
+ * desc->colorspace < 0 the colour space and range are the frames' own: all frames must then
+ * share them, and an unknown colour space (0, 6) is treated as BT.709. A show_existing_frame
+ * output uses the field of the frame it shows. Needs VP9HIP_EXPORT_RESIDUAL in
+ * vp9hip_decoder_set_export's flags. */
+int  vp9hip_decoder_residual_scaled(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n,
+                                    const vp9hip_resid_desc *desc, void *dst_dev, void *stream);
 /* The metrics of the pairs (frames_a[i], frames_b[i]) of received frames through
  * vp9hip_frame_metrics, under the rules of vp9hip_decoder_convert: every frame of both arrays
  * must be of one size, depth and subsampling and held by the caller, else VP9HIP_EINVAL; the size
