@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 
 #define VP9T_STORAGE static __constant__ constexpr
@@ -28,6 +29,7 @@
 #include "vp9hip_work.h"
 #include "vp9hip_resid4.h"
 #include "vp9hip_residn.h"
+#include "vp9hip_lfmap.h"
 
 // The Makefile compiles this file once per KPART (0..5), each object holding a subset of
 // the launchers below and so of the kernel instantiations (parallel builds); without KPART
@@ -683,27 +685,52 @@ struct Chunk16 {
         const uint32_t *s = (const uint32_t *) t;
         return make_uint4(s[0], s[1], s[2], s[3]);
     }
+    // between a chunk in the frame buffer and registers, as global (not flat) accesses: they
+    // count in vmcnt alone, so no LDS wait behind one waits for it
+    typedef uint32_t V4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) V4 G;
+    template <class P> static DEV T from_glb(P g) { const V4 v = *(const G *) g; return make_uint4(v.x, v.y, v.z, v.w); }
+    template <class P> static DEV void to_glb(T v, P g) { V4 w = { v.x, v.y, v.z, v.w }; *(G *) g = w; }
+};
+
+// A frame's plane pointers and pitches as wave-uniform values: copied out of the FrameDesc of a
+// uniform frame index once, before any loop, they are scalar loads; a lane then picks its plane's
+// pointer (a global, not a generic one) and pitch by selects, and no loop holds a per-lane load
+// from FrameDesc that its pixel access would have to wait for.
+struct FramePl {
+    uint64_t pl0, pl1, pl2;
+    int py, pc;
+    DEV explicit FramePl(const FrameDesc &fd) : pl0(fd.plane[0]), pl1(fd.plane[1]), pl2(fd.plane[2]), py(fd.pitch[0]), pc(fd.pitch[1]) {}
+    template <typename PIX> DEV __attribute__((address_space(1))) PIX *plane(int p) const
+    {
+        return (__attribute__((address_space(1))) PIX *) (p == 0 ? pl0 : p == 1 ? pl1 : pl2);
+    }
+    // pixel offset of (x, y) in plane p (< 2^32: a frame is at most 16384 x 16384, vp9hip_configure)
+    DEV uint32_t at(int p, int x, int y) const { return (uint32_t) y * (uint32_t) (p ? pc : py) + (uint32_t) x; }
 };
 
 // The SB interior (all planes) between HBM and the LDS tile in 16-byte chunks (16 px at
 // 8-bit, 8 at 16-bit): STORE = false loads (inter frames: MC prediction + inter residuals),
-// true stores the reconstructed SB. All loads of a lane are issued before its LDS writes.
+// true stores the reconstructed SB. The NB loads of a batch are issued before its LDS writes; a
+// lane's stores follow one another with no wait between them (the addresses come from the
+// scalar frame fields and the chunk number alone: chunks per row are powers of two).
 typedef __attribute__((address_space(1))) uint64_t gpx64;
 // SC (stores only): written through with sc1 (intra workers inside k_lfro: its loader on
 // another XCD reads them in the same launch)
 template <typename PIX, class G, bool STORE, bool SC = false>
-DEV void sb_interior(const FrameDesc &fd, int sbx, int sby, int lane, PIX *tile)
+DEV void sb_interior(const FramePl &fp, int sbx, int sby, int lane, PIX *tile)
 {
+    typedef __attribute__((address_space(1))) PIX gpix;
     constexpr int CPX = 16 / sizeof(PIX);
     constexpr int YK = 64 / CPX, CKX = G::CW / CPX;              // chunks per row
+    static_assert((YK & (YK - 1)) == 0 && (CKX & (CKX - 1)) == 0, "chunks per row: powers of two (no division in where)");
     constexpr int NY = 64 * YK, NC = G::CH * CKX, NT = NY + 2 * NC;
     constexpr int NB = 2;                                         // 16-byte loads in flight per lane (VGPR budget)
-    auto where = [&](int c, PIX *&g, PIX *&t) {
+    auto where = [&](int c, gpix *&g, PIX *&t) {
         int p, r, k;
-        if (c < NY) { p = 0; r = c / YK; k = c - r * YK; }
-        else { const int cc = c - NY; p = 1 + (cc >= NC); const int q = cc - (p - 1) * NC; r = q / CKX; k = q - r * CKX; }
-        g = (PIX *) fd.plane[p] + (size_t) ((p ? sby * G::CH : sby * 64) + r) * fd.pitch[p ? 1 : 0] +
-            (p ? sbx * G::CW : sbx * 64) + k * CPX;
+        if (c < NY) { p = 0; r = (unsigned) c / YK; k = c - r * YK; }
+        else { const int cc = c - NY; p = 1 + (cc >= NC); const int q = cc - (p - 1) * NC; r = (unsigned) q / CKX; k = q - r * CKX; }
+        g = fp.plane<PIX>(p) + fp.at(p, (p ? sbx * G::CW : sbx * 64) + k * CPX, (p ? sby * G::CH : sby * 64) + r);
         t = tile + (p == 0 ? 0 : p == 1 ? LT_SIZE : LT_SIZE + G::CT) + (r + 1) * (p ? G::CP : LP) + PX0 + k * CPX;
     };
 #pragma unroll 1
@@ -713,16 +740,17 @@ DEV void sb_interior(const FrameDesc &fd, int sbx, int sby, int lane, PIX *tile)
         for (int u = 0; u < NB; u++) {
             const int c = c0 + lane + 64 * u;
             if (c >= NT) break;
-            PIX *g, *t;
+            gpix *g;
+            PIX *t;
             where(c, g, t);
             if (STORE && SC) {
                 const uint4 w = Chunk16::from_lds(t);
                 __hip_atomic_store((gpx64 *) g, (uint64_t) w.x | (uint64_t) w.y << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store((gpx64 *) g + 1, (uint64_t) w.z | (uint64_t) w.w << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else if (STORE) {
-                *(uint4 *) g = Chunk16::from_lds(t);
+                Chunk16::to_glb(Chunk16::from_lds(t), g);
             } else {
-                v[u] = *(const uint4 *) g;
+                v[u] = Chunk16::from_glb(g);
             }
         }
         if (STORE) continue;
@@ -730,7 +758,8 @@ DEV void sb_interior(const FrameDesc &fd, int sbx, int sby, int lane, PIX *tile)
         for (int u = 0; u < NB; u++) {
             const int c = c0 + lane + 64 * u;
             if (c >= NT) break;
-            PIX *g, *t;
+            gpix *g;
+            PIX *t;
             where(c, g, t);
             Chunk16::to_lds(v[u], t);
         }
@@ -739,77 +768,84 @@ DEV void sb_interior(const FrameDesc &fd, int sbx, int sby, int lane, PIX *tile)
 
 // Pixel loads / stores of the intra hand-off inside one k_predd launch: sc1 (agent scope), so
 // a workgroup on another XCD reads what the producer wrote through, without an L2 write-back
-// or invalidate (the k_lfro row hand-off's protocol). SC = false: plain.
+// or invalidate (the k_lfro row hand-off's protocol). SC = false: plain. Both forms are global
+// accesses (the pointers are frame buffers or FrameDesc.edge), not flat ones.
 typedef __attribute__((address_space(1))) uint8_t gpx8;
 typedef __attribute__((address_space(1))) uint16_t gpx16;
 template <bool SC, typename PIX> DEV PIX ld_px(const PIX *p)
 {
-    if constexpr (!SC) return *p;
+    if constexpr (!SC) return *(const __attribute__((address_space(1))) PIX *) p;
     else if constexpr (sizeof(PIX) == 1) return __hip_atomic_load((gpx8 *) p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else return __hip_atomic_load((gpx16 *) p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 template <bool SC, typename PIX> DEV void st_px(PIX *p, PIX v)
 {
-    if constexpr (!SC) *p = v;
+    if constexpr (!SC) *(__attribute__((address_space(1))) PIX *) p = v;
     else if constexpr (sizeof(PIX) == 1) __hip_atomic_store((gpx8 *) p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else __hip_atomic_store((gpx16 *) p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// SC: the halo (the row above, the left column) with sc1 loads (k_predd; 4:2:0)
+// SC: the halo (the row above, the left column) with sc1 loads (k_predd; 4:2:0). Every frame
+// field is read here, ahead of the loads (one batch of scalar loads), so the halo loads of the row
+// above and of the left column go out as one batch of global loads.
 template <typename PIX, class G, bool SC = false>
 DEV void load_sb_tile(const FrameDesc &fd, int sbx, int sby, bool interior, int lane, PIX *tile)
 {
+    const FramePl fp(fd);
+    const uint64_t edge = fd.edge;
+    const int sb_cols = fd.sb_cols;
     if (G::SH != 1 || G::SV != 1) {
         // 4:2:2 / 4:4:0 / 4:4:4: plain loops (same tile layout, chroma CW x CH)
         const int lx = sbx * 64, ly = sby * 64, cx = sbx * G::CW, cy = sby * G::CH;
-        const int py = fd.pitch[0], pc = fd.pitch[1];
+        const int py = fp.py, pc = fp.pc;
         for (int p = 0; p < 3; p++) {
-            const PIX *g = (const PIX *) fd.plane[p];
+            const PIX *g = (const PIX *) (p == 0 ? fp.pl0 : p == 1 ? fp.pl1 : fp.pl2);
             const int pitch = p ? pc : py, x0 = p ? cx : lx, y0 = p ? cy : ly;
             const int w = p ? G::CW : 64, h = p ? G::CH : 64, tp = p ? G::CP : LP;
             PIX *t = tile + (p == 0 ? 0 : p == 1 ? LT_SIZE : LT_SIZE + G::CT);
             if (y0 > 0)
-                for (int i = lane; i <= w; i += 64) t[i + PX0 - 1] = x0 - 1 + i >= 0 ? g[(size_t) (y0 - 1) * pitch + x0 - 1 + i] : 0;
+                for (int i = lane; i <= w; i += 64) t[i + PX0 - 1] = x0 - 1 + i >= 0 ? ld_px<false>(g + (size_t) (y0 - 1) * pitch + x0 - 1 + i) : 0;
             if (x0 > 0)
-                for (int i = lane; i < h; i += 64) t[(i + 1) * tp + PX0 - 1] = g[(size_t) (y0 + i) * pitch + x0 - 1];
+                for (int i = lane; i < h; i += 64) t[(i + 1) * tp + PX0 - 1] = ld_px<false>(g + (size_t) (y0 + i) * pitch + x0 - 1);
         }
-        if (interior) sb_interior<PIX, G, false>(fd, sbx, sby, lane, tile);
+        if (interior) sb_interior<PIX, G, false>(fp, sbx, sby, lane, tile);
         return;
     }
     constexpr int CP = G::CP, CT_SIZE = G::CT;
-    const PIX *gy = (const PIX *) fd.plane[0], *gu = (const PIX *) fd.plane[1], *gv = (const PIX *) fd.plane[2];
-    const int py = fd.pitch[0], pc = fd.pitch[1];
+    const PIX *gy = (const PIX *) fp.pl0, *gu = (const PIX *) fp.pl1, *gv = (const PIX *) fp.pl2;
+    const int py = fp.py, pc = fp.pc;
     const int lx = sbx * 64, ly = sby * 64, cx = sbx * 32, cy = sby * 32;
     // lanes 0..32 read U top x = -1..31, lanes 33..63 V top x = -1..29, lanes 0..1 V x = 30..31
-    PIX v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0;
+    // All six loads are unconditional and go out back to back: a load under a condition left a
+    // wait for it at the end of its branch (the join copies the loaded register), so the left
+    // column waited for the row above. A pixel that does not exist (no row above, no column to
+    // the left, x = -1 of the first SB) is read at a clamped position inside the SB's own rows
+    // and columns and not used.
     const bool top = ly > 0, left = lx > 0;
     const PIX *gc = lane < 33 ? gu : gv;
     const int ci = lane < 33 ? lane : lane - 33;
-    if (top) {
-        if (lx - 1 + lane >= 0) v0 = ld_px<SC>(gy + (size_t) (ly - 1) * py + lx - 1 + lane);
-        if (lane == 0) v4 = ld_px<SC>(gy + (size_t) (ly - 1) * py + lx + 63);
-        if (cx - 1 + ci >= 0) v2 = ld_px<SC>(gc + (size_t) (cy - 1) * pc + cx - 1 + ci);
-        if (lane < 2) v5 = ld_px<SC>(gv + (size_t) (cy - 1) * pc + cx + 30 + lane);
-    }
-    if (left && fd.edge) {
-        // the left SB's right column as its intra workgroup saved it (FrameDesc.edge):
-        // two 64-pixel runs instead of 128 one-pixel frame rows
-        const PIX *e = (const PIX *) fd.edge + (size_t) (sby * fd.sb_cols + sbx - 1) * EDGE_PIX;
-        v1 = ld_px<SC>(e + lane);
-        v3 = ld_px<SC>(e + 64 + lane);
-    } else if (left) {
-        v1 = ld_px<SC>(gy + (size_t) (ly + lane) * py + lx - 1);
-        v3 = ld_px<SC>((lane < 32 ? gu : gv) + (size_t) (cy + (lane & 31)) * pc + cx - 1);
-    }
+    const bool in0 = lx - 1 + lane >= 0, in2 = cx - 1 + ci >= 0;
+    const size_t ty = (size_t) (top ? ly - 1 : 0) * py, tc = (size_t) (top ? cy - 1 : 0) * pc;
+    const PIX v0 = ld_px<SC>(gy + ty + (in0 ? lx - 1 + lane : lx));
+    const PIX v4 = ld_px<SC>(gy + ty + lx + 63);
+    const PIX v2 = ld_px<SC>(gc + tc + (in2 ? cx - 1 + ci : cx));
+    const PIX v5 = ld_px<SC>(gv + tc + cx + 30 + (lane & 1));
+    // the left SB's right column as its intra workgroup saved it (FrameDesc.edge): two 64-pixel
+    // runs instead of 128 one-pixel frame rows; without it, the frame's column
+    const bool sav = left && edge;
+    const PIX *e = (const PIX *) edge + (size_t) (sby * sb_cols + sbx - 1) * EDGE_PIX;
+    const PIX *a1 = sav ? e + lane : gy + (size_t) (ly + lane) * py + (left ? lx - 1 : lx);
+    const PIX *a3 = sav ? e + 64 + lane : (lane < 32 ? gu : gv) + (size_t) (cy + (lane & 31)) * pc + (left ? cx - 1 : cx);
+    const PIX v1 = ld_px<SC>(a1), v3 = ld_px<SC>(a3);
     PIX *tu = tile + LT_SIZE, *tv = tile + LT_SIZE + CT_SIZE;
     if (top) {
-        tile[PX0 - 1 + lane] = v0;
+        tile[PX0 - 1 + lane] = in0 ? v0 : (PIX) 0;
         if (lane == 0) tile[PX0 + 63] = v4;
-        (lane < 33 ? tu : tv)[PX0 - 1 + ci] = v2;
+        (lane < 33 ? tu : tv)[PX0 - 1 + ci] = in2 ? v2 : (PIX) 0;
         if (lane < 2) tv[PX0 + 30 + lane] = v5;
     }
     if (left) { tile[(lane + 1) * LP + PX0 - 1] = v1; (lane < 32 ? tu : tv)[((lane & 31) + 1) * CP + PX0 - 1] = v3; }
-    if (interior) sb_interior<PIX, G, false>(fd, sbx, sby, lane, tile);
+    if (interior) sb_interior<PIX, G, false>(fp, sbx, sby, lane, tile);
 }
 
 // one predictor pixel from its formula word and the three edge values it names
@@ -991,12 +1027,13 @@ template <typename PIX, class G, bool LISTS> struct PredLds {
 template <typename PIX>
 DEV void load_ltab(uint32_t *ltab, const uint32_t *__restrict__ ptab, int lane)
 {
+    // the contiguous image behind the table (PTAB_LTAB_WORDS, built with it once per context):
+    // 13 loads at lane + 64 u, no i / 80 and i % 80, none conditional (the image is padded)
+    static_assert(PTAB_LTAB_PAD == 13 * 64 && PTAB_LTAB_WORDS == 800, "load_ltab: 13 loads per lane");
+    glb_u32 *img = (glb_u32 *) (ptab + PTAB_SIZE);
     uint32_t t[13];
 #pragma unroll
-    for (int u = 0; u < 13; u++) {
-        const int i = lane + 64 * u;
-        t[u] = i < 800 ? ptab[(i / 80) * PTAB_SLOT + i % 80] : 0;
-    }
+    for (int u = 0; u < 13; u++) t[u] = img[lane + 64 * u];
 #pragma unroll
     for (int u = 0; u < 13; u++)
         if (lane + 64 * u < 800) ltab[lane + 64 * u] = t[u];
@@ -1029,8 +1066,12 @@ DEV void pred_wg(const WGRec *wgp, const SBRec *__restrict__ sbs, const PJob *__
 #endif
     typedef PredLists<G, LISTS> PL;
     const uint32_t wjob0 = wgp->job0, wpass0 = wgp->pass0;
-    const uint32_t wnjobs = PL::ON ? min((uint32_t) wgp->njobs, (uint32_t) PL::JL) : wgp->njobs;
-    const uint32_t wnpass = PL::ON ? min((uint32_t) wgp->npass, wnjobs) : wgp->npass;
+    // njobs | npass << 16 as one word: a scalar load with the record's other words (a 16-bit
+    // field is a vector load, waited for on its own)
+    static_assert(offsetof(WGRec, njobs) == 8 && offsetof(WGRec, npass) == 10, "WGRec: njobs, npass share word 2");
+    const uint32_t wnn = ((const uint32_t *) wgp)[2];
+    const uint32_t wnjobs = PL::ON ? min(wnn & 0xffffu, (uint32_t) PL::JL) : wnn & 0xffffu;
+    const uint32_t wnpass = PL::ON ? min(wnn >> 16, wnjobs) : wnn >> 16;
     const PJob *gj = jobs + wjob0;         // job records (global)
     const uint32_t *gp = passes + wpass0;  // pass words (global)
     const int bd = frames[sbs[wgp->sb[0]].frame].bd;
@@ -1053,7 +1094,9 @@ DEV void pred_wg(const WGRec *wgp, const SBRec *__restrict__ sbs, const PJob *__
         const uint32_t sbi = __builtin_amdgcn_readfirstlane(wgp->sb[k]);
         if (sbi != 0xffffffffu) {
             const SBRec sb = sbs[sbi];
-            if (!(dbg & 4)) load_sb_tile<PIX, G, HO != 0>(frames[sb.frame], sb.sbx, sb.sby, sb.flags & 1, lane, tile + k * G::TILE);
+            static_assert(offsetof(SBRec, flags) == 10 && sizeof(SBRec) == 12, "SBRec: tile_x0, flags share word 2");
+            const uint32_t sbflags = ((const uint32_t *) (sbs + sbi))[2] >> 16;     // a scalar load, as above
+            if (!(dbg & 4)) load_sb_tile<PIX, G, HO != 0>(frames[sb.frame], sb.sbx, sb.sby, sbflags & 1, lane, tile + k * G::TILE);
         }
     }
     if (PL::ON) {
@@ -1125,22 +1168,25 @@ DEV void pred_wg(const WGRec *wgp, const SBRec *__restrict__ sbs, const PJob *__
         if (sbi == 0xffffffffu) continue;
         const SBRec sb = sbs[sbi];
         const FrameDesc &fd = frames[sb.frame];
-        sb_interior<PIX, G, true, HO == 2>(fd, sb.sbx, sb.sby, lane, tile + k * G::TILE);
+        const FramePl fp(fd);
+        const uint64_t edge = fd.edge;     // with the planes: one batch of scalar loads
+        const int sb_cols = fd.sb_cols;
+        sb_interior<PIX, G, true, HO == 2>(fp, sb.sbx, sb.sby, lane, tile + k * G::TILE);
         if constexpr (HO == 1) {       // right column and bottom row again, written through
             static_assert(G::SH == 1 && G::SV == 1, "k_predd: 4:2:0");
             const PIX *t = tile + k * G::TILE;
-            PIX *gy = (PIX *) fd.plane[0];
+            PIX *gy = (PIX *) fp.pl0;
             const int p = 1 + (lane >> 5), x = lane & 31;
-            PIX *gc = (PIX *) fd.plane[p];
+            PIX *gc = (PIX *) (p == 1 ? fp.pl1 : fp.pl2);
             const PIX *tc = t + (p == 1 ? LT_SIZE : LT_SIZE + G::CT);
             const size_t ly = (size_t) sb.sby * 64, cy = (size_t) sb.sby * 32;
-            st_px<true>(gy + (ly + 63) * fd.pitch[0] + sb.sbx * 64 + lane, t[64 * LP + PX0 + lane]);
-            st_px<true>(gy + (ly + lane) * fd.pitch[0] + sb.sbx * 64 + 63, t[(lane + 1) * LP + PX0 + 63]);
-            st_px<true>(gc + (cy + 31) * fd.pitch[1] + sb.sbx * 32 + x, tc[32 * G::CP + PX0 + x]);
-            st_px<true>(gc + (cy + x) * fd.pitch[1] + sb.sbx * 32 + 31, tc[(x + 1) * G::CP + PX0 + 31]);
+            st_px<true>(gy + (ly + 63) * fp.py + sb.sbx * 64 + lane, t[64 * LP + PX0 + lane]);
+            st_px<true>(gy + (ly + lane) * fp.py + sb.sbx * 64 + 63, t[(lane + 1) * LP + PX0 + 63]);
+            st_px<true>(gc + (cy + 31) * fp.pc + sb.sbx * 32 + x, tc[32 * G::CP + PX0 + x]);
+            st_px<true>(gc + (cy + x) * fp.pc + sb.sbx * 32 + 31, tc[(x + 1) * G::CP + PX0 + 31]);
         }
-        if (fd.edge) {                 // the right column of each plane, for the SB to the right
-            PIX *e = (PIX *) fd.edge + (size_t) (sb.sby * fd.sb_cols + sb.sbx) * EDGE_PIX;
+        if (edge) {                    // the right column of each plane, for the SB to the right
+            PIX *e = (PIX *) edge + (size_t) (sb.sby * sb_cols + sb.sbx) * EDGE_PIX;
             const PIX *t = tile + k * G::TILE;
 #pragma unroll
             for (int i = lane; i < 64 + 2 * G::CH; i += 64) {
@@ -1191,13 +1237,14 @@ template <typename PIX, class G> struct LfP {
     static constexpr int PROG = LF_PROG_OF(G::SH, G::SV);
 };
 
-// chunk index -> (plane, tile row, chunk column): luma 72 rows x YK, then U, V CR x CK
-template <typename PIX, class G> DEV void lf_chunk(int ci, int &p, int &r, int &k)
-{
+// chunk index -> (plane, tile row, chunk column): LfMap (vp9hip_lfmap.h), which restates the
+// geometry above for the host check
+template <typename PIX, class G, int NT> struct LfM : LfMap<(int) sizeof(PIX), G::SH, G::SV, NT> {
+    typedef LfMap<(int) sizeof(PIX), G::SH, G::SV, NT> M;
     typedef LfP<PIX, G> L;
-    if (ci < L::NY) { p = 0; r = ci / L::YK; k = ci - r * L::YK; }
-    else { const int c = ci - L::NY; p = 1 + (c >= L::CR * L::CK); const int cc = c - (p - 1) * L::CR * L::CK; r = cc / L::CK; k = cc - r * L::CK; }
-}
+    static_assert(M::CPX == L::CPX && M::XL == L::XL && M::YP == L::YP && M::UVP == L::UVP && M::YK == L::YK &&
+                  M::CK == L::CK && M::CR == L::CR && M::NY == L::NY && M::NCHUNK == L::NCHUNK, "LfMap restates LfP");
+};
 
 // --------------------------------------------------------------- k_lf
 DEV int ad16(int a, int b) { return (int) __builtin_amdgcn_sad_u16((uint32_t) a, (uint32_t) b, 0u); }
@@ -1574,37 +1621,66 @@ DEV void lf_sb(const LFRec &rec, const FrameDesc *__restrict__ frames, LfLds<PIX
     PIX *lt = S.lt;
     PIX (*ct)[L::CR * FCP] = S.ct;
     const uint32_t *lut = S.lut;
+    // the frame's fields, once per workgroup: rec.frame is uniform, so these are scalar loads and
+    // a lane picks its plane's pointer and pitch by selects (FramePl)
     const FrameDesc &fd = frames[rec.frame];
+    const FramePl fp(fd);
     const int bd = fd.bd, sharp = fd.sharp;
     const int sbx = rec.sbx, sby = rec.sby;
-    for (int i = lane; i < L::PROG / 4; i += NT) S.prog[i] = ((const uint32_t *) rec.prog)[i];
+    typedef __attribute__((address_space(1))) PIX gpix;
     for (int i = lane; i < 64; i += NT) S.lut[i] = lf_eih(i, sharp, bd);
 
     // load: luma rows [y0-8, y0+64) x cols [x0-XL, x0+64), chroma [-8, CH) x [-XL, CW), in
     // aligned 16-byte chunks (4:2:0 8-bit: luma 72 x 5, chroma 2 x 40 x 3 = 600 chunks, <= 5
-    // per thread), all global loads of a thread in flight before its LDS writes
+    // per thread). The prog words and all NU chunks of a thread are issued back to back, through
+    // global (not flat) loads at addresses built from the scalar frame fields above, every one
+    // unconditional (a chunk outside the frame or past the last one reads a clamped address and
+    // is zeroed afterwards): nothing is waited for before the last load is out. The LDS writes
+    // follow in issue order.
     typedef Chunk16::T CT;
+    typedef LfM<PIX, G, NT> M;
     constexpr int CPX = L::CPX, XL = L::XL, XO = L::XO;
-    constexpr int NU = (L::NCHUNK + NT - 1) / NT;
+    constexpr int NU = M::NU, NPW = (L::PROG / 4 + NT - 1) / NT;
+    const typename M::Lane ml = M::of(lane);
+    const int lx0 = sbx * 64 - XL, ly0 = sby * 64 - 8, cx0 = sbx * CW - XL, cy0 = sby * CH - 8;
+    // pixel offset of chunk (p, r, k) in its plane, clamped into the frame, and whether the
+    // chunk lies in the frame
+    auto gpos = [&](int p, int r, int k, bool &in) -> uint32_t {
+        const int gx = (p ? cx0 : lx0) + CPX * k, gy = (p ? cy0 : ly0) + r;
+        in = gx >= 0 && gy >= 0;
+        return fp.at(p, max(gx, 0), max(gy, 0));
+    };
+    auto gplane = [&](int p) -> gpix * { return fp.template plane<PIX>(p); };
+    uint32_t pw[NPW];
     CT v[NU];
+    if (!(dbg & 4)) {
 #pragma unroll
-    for (int u = 0; u < NU; u++) {
-        const int ci = lane + u * NT;
-        int p, r, k;
-        lf_chunk<PIX, G>(ci, p, r, k);
-        const int gx = (p ? sbx * CW : sbx * 64) - XL + CPX * k, gy = (p ? sby * CH : sby * 64) - 8 + r;
-        v[u] = Chunk16::zero();
-        if (!(dbg & 4) && ci < L::NCHUNK && gx >= 0 && gy >= 0)
-            v[u] = *(const CT *) ((const PIX *) fd.plane[p] + (size_t) gy * fd.pitch[p ? 1 : 0] + gx);
+        for (int j = 0; j < NPW; j++) pw[j] = ((glb_u32 *) rec.prog)[min(lane + j * NT, L::PROG / 4 - 1)];
+#pragma unroll
+        for (int u = 0; u < NU; u++) {
+            int p, r, k;
+            bool in;
+            const bool ok = M::chunk(ml, u, p, r, k);
+            const uint32_t o = gpos(ok ? p : 0, ok ? r : 8, ok ? k : 1, in);
+            v[u] = Chunk16::from_glb(gplane(ok ? p : 0) + o);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < NPW; j++) pw[j] = 0;
+#pragma unroll
+        for (int u = 0; u < NU; u++) v[u] = Chunk16::zero();
     }
 #pragma unroll
+    for (int j = 0; j < NPW; j++)
+        if (lane + j * NT < L::PROG / 4) S.prog[lane + j * NT] = pw[j];
+#pragma unroll
     for (int u = 0; u < NU; u++) {
-        const int ci = lane + u * NT;
         int p, r, k;
-        lf_chunk<PIX, G>(ci, p, r, k);
-        if (ci < L::NCHUNK) {
-            PIX *t = p ? ct[p - 1] + r * FCP : lt + r * FLP;
-            Chunk16::to_lds(v[u], t + CPX * k);
+        bool in;
+        if (M::chunk(ml, u, p, r, k)) {
+            gpos(p, r, k, in);
+            PIX *t = (p ? ct[p - 1] : lt) + M::tile_off(p, r, k);
+            Chunk16::to_lds(in ? v[u] : Chunk16::zero(), t);
         }
     }
     LF_SYNC();
@@ -1612,17 +1688,27 @@ DEV void lf_sb(const LFRec &rec, const FrameDesc *__restrict__ frames, LfLds<PIX
     if (!(dbg & 1)) lf_passes<PIX, G, NT>(S, lane, bd);
     // ---- store the modified region: rows [0,h) x cols [-8,w) and rows [-8,0) x cols [0,w).
     // Other SBs of the same wavefront step never touch this region, so whole chunks are
-    // written back (pixels beyond the 8-aligned frame size are unchanged padding). ----
+    // written back (pixels beyond the 8-aligned frame size are unchanged padding). All LDS
+    // reads of a thread, then its global stores back to back: no store waits for another's
+    // acknowledgement. The lane's map is derived again (the asm keeps the compiler from holding
+    // the load phase's copy in registers across the filter passes, whose budget it would cost). ----
+    int lane_s = lane;
+    asm volatile("" : "+v"(lane_s));
+    const typename M::Lane ms = M::of(lane_s);
+    CT w[NU];
 #pragma unroll
     for (int u = 0; u < NU; u++) {
-        const int ci = lane + u * NT;
         int p, r, k;
-        lf_chunk<PIX, G>(ci, p, r, k);
-        const int gx = (p ? sbx * CW : sbx * 64) - XL + CPX * k, gy = (p ? sby * CH : sby * 64) - 8 + r;
-        if (!(dbg & 2) && ci < L::NCHUNK && gx >= 0 && gy >= 0 && (r >= 8 || k > 0)) {
-            const PIX *t = p ? ct[p - 1] + r * FCP : lt + r * FLP;
-            *(CT *) ((PIX *) fd.plane[p] + (size_t) gy * fd.pitch[p ? 1 : 0] + gx) = Chunk16::from_lds(t + CPX * k);
-        }
+        if (M::chunk(ms, u, p, r, k)) w[u] = Chunk16::from_lds((p ? ct[p - 1] : lt) + M::tile_off(p, r, k));
+        else w[u] = Chunk16::zero();
+    }
+#pragma unroll
+    for (int u = 0; u < NU; u++) {
+        int p, r, k;
+        bool in;
+        const bool ok = M::chunk(ms, u, p, r, k);
+        const uint32_t o = gpos(p, r, k, in);
+        if (!(dbg & 2) && ok && in && (r >= 8 || k > 0)) Chunk16::to_glb(w[u], gplane(p) + o);
     }
 #undef LF_SYNC
 }

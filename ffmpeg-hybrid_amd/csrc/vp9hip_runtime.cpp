@@ -708,13 +708,14 @@ static uint32_t pix_formula(int slot, int n, int x, int y)
 static int upload_ptab(vp9hip_ctx *c)
 {
     if (c->ptab) return 0;
-    std::vector<uint32_t> t(PTAB_SIZE);
+    std::vector<uint32_t> t(PTAB_ALLOC, 0u);
     for (int slot = 0; slot < 10; slot++)
         for (int ts = 0, off = 0; ts < 4; off += 16 << (2 * ts), ts++) {
             const int n = 4 << ts;
             for (int y = 0; y < n; y++)
                 for (int x = 0; x < n; x++) t[slot * PTAB_SLOT + off + y * n + x] = pix_formula(slot, n, x, y);
         }
+    for (int i = 0; i < PTAB_LTAB_WORDS; i++) t[PTAB_SIZE + i] = t[(i / 80) * PTAB_SLOT + i % 80];   // load_ltab's image
     if (hipMalloc(&c->ptab, t.size() * 4) != hipSuccess) return VP9HIP_ENOMEM;
     return hipMemcpy(c->ptab, t.data(), t.size() * 4, hipMemcpyHostToDevice) == hipSuccess ? 0 : VP9HIP_EEXTERNAL;
 }

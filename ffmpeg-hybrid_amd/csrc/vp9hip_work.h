@@ -87,6 +87,12 @@ typedef struct PJob {
  * job's edge array e (left column bottom-to-top, top-left, top row + top-right). */
 #define PTAB_SLOT 1360        /* 16 + 64 + 256 + 1024 entries per slot */
 #define PTAB_SIZE (10 * PTAB_SLOT)
+/* Behind the table, the image of the kernels' LDS copy (load_ltab): the first 80 words (the 4x4
+ * and 8x8 formulas) of the ten slots back to back, 800 words, zero-padded to 13 x 64 so that a
+ * wave copies it with 13 unconditional loads at lane + 64 u. */
+#define PTAB_LTAB_WORDS 800
+#define PTAB_LTAB_PAD (13 * 64)
+#define PTAB_ALLOC (PTAB_SIZE + PTAB_LTAB_PAD)
 
 /* One superblock of intra work (geometry only; its jobs live in a WGRec). */
 typedef struct SBRec {
