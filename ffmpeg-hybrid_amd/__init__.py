@@ -159,7 +159,9 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9hip_convert_frames_bicubic", "vp9hip_decoder_convert_bicubic", "vp9hip_bicubic_weights",
                "vp9hip_frame_metrics", "vp9hip_frame_metrics_host", "vp9hip_decoder_metrics",
                "vp9hip_resid_layout", "vp9hip_residual_frames_scaled", "vp9hip_residual_scaled_host",
-               "vp9hip_decoder_residual_scaled"]
+               "vp9hip_decoder_residual_scaled",
+               "vp9hip_mvt_layout", "vp9hip_motion_frames_scaled", "vp9hip_motion_scaled_host",
+               "vp9hip_decoder_motion_scaled"]
 
 
 def lib():
@@ -349,6 +351,15 @@ def lib():
                                              [ctypes.POINTER(ResidDesc), ctypes.c_void_p]
     L.vp9hip_decoder_residual_scaled.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int,
                                                  ctypes.POINTER(ResidDesc), ctypes.c_void_p, ctypes.c_void_p]
+    # motion tensors at model size
+    L.vp9hip_mvt_layout.restype = ctypes.c_int64
+    L.vp9hip_mvt_layout.argtypes = [ctypes.POINTER(MvtDesc), ctypes.POINTER(ctypes.c_int64)]
+    L.vp9hip_motion_frames_scaled.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(MvtDesc),
+                                              ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_motion_scaled_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ssize_t,
+                                            ctypes.POINTER(MvtDesc), ctypes.c_void_p]
+    L.vp9hip_decoder_motion_scaled.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int,
+                                               ctypes.POINTER(MvtDesc), ctypes.c_void_p, ctypes.c_void_p]
     # frame metrics
     L.vp9hip_frame_metrics.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -404,6 +415,14 @@ class ResidDesc(ctypes.Structure):
                 ("frame_stride", ctypes.c_int64)]
 
 
+class MvtDesc(ctypes.Structure):
+    """vp9hip_mvt_desc: the format, source and layout of motion tensors at model size."""
+    _fields_ = [("format", ctypes.c_int32), ("source", ctypes.c_int32), ("planes", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32), ("pitch", ctypes.c_int64),
+                ("frame_stride", ctypes.c_int64)]
+
+
 class Rect(ctypes.Structure):
     """vp9hip_rect: (x, y, w, h) in luma samples."""
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32)]
@@ -419,6 +438,9 @@ class Resample(ctypes.Structure):
 OUT_FORMATS = {"semiplanar": 0, "rgb24": 1, "rgbp_u8": 2, "rgbp_f16": 3}
 # VP9HIP_RESID_*: the names Device.residual_tensors / Decoder.residual_tensors take
 RESID_FORMATS = {"yuv_i16": 0, "yuv_f16": 1, "rgb_i16": 2, "rgb_f16": 3}
+# VP9HIP_MVT_*: the names Device.motion_tensors / Decoder.motion_tensors take for fmt and source
+MVT_FORMATS = {"i16": 0, "f16": 1}
+MVT_SOURCES = {"coded": 0, "acc": 1}
 # VP9HIP_FILTER_*: the names of their filter argument
 FILTERS = {"box": 0, "triangle": 1}
 # VP9HIP_FILTER_BICUBIC, filter="bicubic": entries of its own (vp9hip_convert_frames_bicubic)
@@ -984,6 +1006,82 @@ def _resid_out(n, d, out):
                                  (stride // 2, pitch.value * d.out_height // 2, pitch.value // 2, 1))
 
 
+def _mvt_desc(fmt, source, mask, resize, size, pitch, frame_stride):
+    """The MvtDesc of a motion_tensors call: resize=None is the visible size, the dense field."""
+    w, h = (int(x) for x in size)
+    ow, oh = (int(x) for x in (resize if resize is not None else size))
+    return MvtDesc(MVT_FORMATS[fmt], MVT_SOURCES[source], 3 if mask else 2, w, h, ow, oh, int(pitch), int(frame_stride))
+
+
+def motion_scaled_host(mv, info, width, height, fmt, resize, source="coded", acc=None, mask=False):
+    """The motion tensor of one frame on the host, vp9hip_motion_scaled_host, the C statement of
+    the definition in include/vp9hip.h ("motion tensors at model size"): source "coded" reads mv
+    int16 (GH, GW, 2, 2) and info uint8 (GH, GW, 4) as Device.motion / motion_host give them,
+    source "acc" reads acc, an ACC_CELL array (GH, GW) (mv and info may then be None); rows may
+    be strided, and the arrays must cover the (height + 3) >> 2 x (width + 3) >> 2 cells of the
+    visible width x height. The result is a (2 or 3, OH, OW) int16 or float16 array: x, y and
+    with mask the coverage; fmt a key of MVT_FORMATS, resize = (OW, OH) or None for the visible
+    size."""
+    fn = "vp9hip_motion_scaled_host"
+    d = _mvt_desc(fmt, source, mask, resize, (width, height), 0, 0)
+    sane = 1 <= width <= 16384 and 1 <= height <= 16384
+
+    def rows(a, name, dtype, tail, cell):
+        """a with rows of whole cells, its pitch in cells"""
+        a = np.asarray(a)
+        if a.dtype != dtype or a.shape[2:] != tail or a.ndim != 2 + len(tail):
+            raise ValueError("%s: %s must be a %s array (GH, GW%s)" % (fn, name, np.dtype(dtype).name, "".join(", %d" % t for t in tail)))
+        if not a[:1, :1].flags.c_contiguous or (a.shape[1] > 1 and a.strides[1] != cell) or a.strides[0] < 0 or a.strides[0] % cell:
+            a = np.ascontiguousarray(a)
+        if sane and (a.shape[0] < (height + 3) >> 2 or a.shape[1] < (width + 3) >> 2):
+            raise ValueError("%s: %s is smaller than the visible %d x %d" % (fn, name, width, height))
+        return a, (a.strides[0] // cell if a.shape[0] > 1 else a.shape[1])
+
+    ptrs, pitches = [None, None, None], []
+    if d.source == 0:
+        m, pm = rows(mv, "mv", np.int16, (2, 2), 8)
+        i, pi = rows(info, "info", np.uint8, (4,), 4)
+        if pm != pi:                                      # one pitch for both planes, as on the device
+            m, i = np.ascontiguousarray(m), np.ascontiguousarray(i)
+            pm = pi = m.shape[1]
+            if m.shape[:2] != i.shape[:2]:
+                raise ValueError("%s: mv and info of different grids" % fn)
+        ptrs[0], ptrs[1], pitches, keep = m.ctypes.data, i.ctypes.data, pm, (m, i)
+    else:
+        if acc is None:
+            raise ValueError("%s: source 'acc' needs acc" % fn)
+        a, pa = rows(acc, "acc", ACC_CELL, (), 16)
+        ptrs[2], pitches, keep = a.ctypes.data, pa, (a,)
+    ok = 1 <= d.out_width <= 16384 and 1 <= d.out_height <= 16384
+    out = np.full((d.planes, d.out_height, d.out_width) if ok else (d.planes, 1, 1), 0x5a5a, np.int16)
+    _check(fn, lib().vp9hip_motion_scaled_host(ptrs[0], ptrs[1], ptrs[2], pitches, ctypes.byref(d), out.ctypes.data))
+    del keep
+    return out.view(np.float16) if fmt == "f16" else out
+
+
+def _mvt_out(n, d, out):
+    """The destination of a motion_tensors call: (flat storage tensor, (N, P, OH, OW) view of
+    it), as _resid_out. A descriptor the library refuses gets one element to hand it, so the
+    refusal is the library's."""
+    import torch
+    dt = torch.float16 if d.format & 1 else torch.int16
+    pitch = ctypes.c_int64()
+    nbytes = lib().vp9hip_mvt_layout(ctypes.byref(d), ctypes.byref(pitch))
+    if nbytes < 0:
+        flat = out.view(-1) if out is not None else torch.empty(1, dtype=dt, device="cuda")
+        return flat, None
+    stride = d.frame_stride or nbytes
+    total = ((max(n, 1) - 1) * stride + nbytes) // 2
+    if out is None:
+        out = torch.empty(total, dtype=dt, device="cuda")
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == dt and out.is_contiguous()
+              and out.numel() >= total):
+        raise ValueError("motion_tensors: out must be a contiguous %s cuda tensor of at least %d elements" % (dt, total))
+    flat = out.view(-1)
+    return flat, flat.as_strided((max(n, 0), d.planes, d.out_height, d.out_width),
+                                 (stride // 2, pitch.value * d.out_height // 2, pitch.value // 2, 1))
+
+
 METRIC_FIELDS = ("sum_a", "sum_b", "sumsq_a", "sad", "sse", "ndiff", "maxdiff", "first")   # VP9HIP_METRIC_*
 METRIC_CELL = 16               # VP9HIP_METRIC_CELL
 
@@ -1213,6 +1311,45 @@ class Device:
         flat, res = _resid_out(len(bufs), d, out)
         arr = (ctypes.c_int * len(bufs))(*bufs)
         call = lambda st: lib().vp9hip_residual_frames_scaled(self._c, arr, len(bufs), ctypes.byref(d), flat.data_ptr(), st)
+        main = ctypes.c_void_p()
+        # an unconfigured context has no buffer to ask for its stream: the library refuses the call itself
+        if lib().vp9hip_frame_device(self._c, 0, (ctypes.c_void_p * 3)(), (ctypes.c_ssize_t * 3)(), None, None,
+                                     ctypes.byref(main)):
+            _check(fn, call(stream))
+        else:
+            _check(fn, _enqueue_for_torch(main.value, stream, call))
+        return res
+
+    def motion_tensors(self, bufs, fmt, resize=None, source="coded", mask=False, size=None, out=None, stream=None,
+                       pitch=0, frame_stride=0):
+        """The motion fields (source "coded") or accumulated motion fields (source "acc") of
+        device buffers `bufs` (any order, repeats allowed, all of the visible size `size` =
+        (width, height), default the configured size) as one (N, 2 or 3, OH, OW) cuda tensor at
+        the model's size, made on the GPU in one launch per 32 frames
+        (vp9hip_motion_frames_scaled, the definition in include/vp9hip.h "motion tensors at
+        model size"): every cell's first vector (intra cells, and acc cells of no hops, as zero;
+        acc sums clamped to int16) spread over its 4 x 4 pixels, cropped to the visible size and
+        box-resampled to resize = (OW, OH) with the exact signed box filter (None: the visible
+        size, the dense field itself, through the same kernel). Planes x, y and with mask=True
+        the inter coverage. fmt "i16": int16 in 1/8 luma pel of the source, the coverage
+        0..256; "f16": float16 displacement in output pixels, the coverage 0..1. `out` is a
+        contiguous int16 / float16 cuda tensor to write into (else one is allocated); pitch /
+        frame_stride in bytes as in vp9hip_mvt_desc (0 = tight), the result then strided over
+        them. Runs in the order of torch's current stream (or on `stream`, a hipStream_t handle;
+        see _enqueue_for_torch) and does not wait: order it after the fields' producer (sync(),
+        or vp9hip_slot_stream_wait), as for convert. Needs torch imported before the library was
+        loaded (see _torch_first)."""
+        fn = "vp9hip_motion_frames_scaled"
+        if not _torch_first:
+            raise Vp9HipUnavailable("motion_tensors: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        bufs = [int(b) for b in bufs]
+        if not bufs:
+            raise Vp9HipError(fn, EINVAL)
+        d = _mvt_desc(fmt, source, mask, resize, size if size is not None else (self.w, self.h), pitch, frame_stride)
+        flat, res = _mvt_out(len(bufs), d, out)
+        arr = (ctypes.c_int * len(bufs))(*bufs)
+        call = lambda st: lib().vp9hip_motion_frames_scaled(self._c, arr, len(bufs), ctypes.byref(d), flat.data_ptr(), st)
         main = ctypes.c_void_p()
         # an unconfigured context has no buffer to ask for its stream: the library refuses the call itself
         if lib().vp9hip_frame_device(self._c, 0, (ctypes.c_void_p * 3)(), (ctypes.c_ssize_t * 3)(), None, None,
@@ -1747,6 +1884,34 @@ class Decoder:
         _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
                                                                 (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
         call = lambda st: lib().vp9hip_decoder_residual_scaled(self._d, arr, len(infos), ctypes.byref(d), flat.data_ptr(), st)
+        _check(fn, _enqueue_for_torch(main.value, None, call))
+        torch.cuda.current_stream().synchronize()
+        return res
+
+    def motion_tensors(self, infos, fmt, resize=None, source="coded", mask=False, out=None):
+        """The motion fields (source "coded"; needs export_motion=True) or accumulated motion
+        fields (source "acc"; needs export_motion_acc=True) of frames of
+        receive_frame(download=False) (their DecodedFrameInfos, all of one size, all still held)
+        as Device.motion_tensors returns them, at the frames' own visible size
+        (vp9hip_decoder_motion_scaled), on torch's current stream; waits for it. A
+        show_existing_frame output has the tensor of the frame it shows. Like
+        Decoder.residual_tensors it releases nothing."""
+        fn = "vp9hip_decoder_motion_scaled"
+        if not _torch_first:
+            raise Vp9HipUnavailable("motion_tensors: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        import torch
+        infos = list(infos)
+        if not infos:
+            raise Vp9HipError(fn, EINVAL)
+        f = infos[0]
+        d = _mvt_desc(fmt, source, mask, resize, (f.width, f.height), 0, 0)
+        flat, res = _mvt_out(len(infos), d, out)
+        arr = (DecodedFrameInfo * len(infos))(*infos)
+        main = ctypes.c_void_p()
+        _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
+                                                                (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
+        call = lambda st: lib().vp9hip_decoder_motion_scaled(self._d, arr, len(infos), ctypes.byref(d), flat.data_ptr(), st)
         _check(fn, _enqueue_for_torch(main.value, None, call))
         torch.cuda.current_stream().synchronize()
         return res

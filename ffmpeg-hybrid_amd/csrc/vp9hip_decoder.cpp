@@ -518,6 +518,27 @@ extern "C" int vp9hip_decoder_residual_scaled(vp9hip_decoder *d, const vp9hip_de
     return vp9hip_residual_frames_scaled(d->ctx, bufs.data(), n, &o, dst_dev, stream);
 }
 
+// The motion tensors of received frames (vp9hip_motion_frames_scaled), under the same rules: the
+// frames are complete and stay the caller's, the size is the frames' own, and a
+// show_existing_frame output holds the shown buffer and with it that frame's fields. The runtime
+// refuses VP9HIP_MVT_ACC on a context without the accumulated planes.
+extern "C" int vp9hip_decoder_motion_scaled(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n,
+                                            const vp9hip_mvt_desc *desc, void *dst_dev, void *stream)
+{
+    if (!d || !frames || n <= 0 || !desc || !d->configured || !(d->export_flags & VP9HIP_EXPORT_MOTION)) return VP9HIP_EINVAL;
+    std::vector<int> bufs(n);
+    const vp9hip_decoded_frame &f0 = frames[0];
+    for (int i = 0; i < n; i++) {
+        const vp9hip_decoded_frame &f = frames[i];
+        if (f.buf < 0 || f.buf >= d->nbufs || d->pins[f.buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+        if (f.width != f0.width || f.height != f0.height) return VP9HIP_EINVAL;
+        bufs[i] = f.buf;
+    }
+    vp9hip_mvt_desc o = *desc;
+    o.width = f0.width; o.height = f0.height;
+    return vp9hip_motion_frames_scaled(d->ctx, bufs.data(), n, &o, dst_dev, stream);
+}
+
 // avcodec_flush_buffers (vp9.c:1865-1883): drop the decoder delay and the reference
 // state; frames already handed out stay valid until released.
 extern "C" int vp9hip_decoder_flush(vp9hip_decoder *d)

@@ -48,6 +48,7 @@
 #include "vp9hip_residual.h"
 #include "vp9hip_metrics.h"
 #include "vp9hip_residual_scale.h"
+#include "vp9hip_motion_scale.h"
 #include "vp9hip_residn.h"
 
 extern "C" {
@@ -4092,6 +4093,52 @@ extern "C" int vp9hip_residual_frames_scaled(vp9hip_ctx *c, const int *bufs, int
         for (int i = 0; i < k; i++) a.src[i] = c->res[bufs[i0 + i]];
         a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
         HIPCHK(vp9hip_residual_scale_launch(a, d->format, k, st));
+    }
+    return 0;
+}
+
+// Motion tensors at model size (include/vp9hip.h "motion tensors at model size"; k_motion_scale
+// in vp9hip_motion_scale.hip): the motion or accumulated fields of bufs[0 .. n-1] into dst_dev,
+// enqueued on `stream` (NULL: the current slot's main stream). Everything is validated before
+// the first launch, so a refused call writes nothing. The fields' pointers travel as kernel
+// arguments, MSC_MAX_FRAMES per launch: no device table, no copy, nothing to free.
+extern "C" int vp9hip_motion_frames_scaled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_mvt_desc *d,
+                                           void *dst_dev, void *stream)
+{
+    if (!c || c->mot.empty() || !bufs || n <= 0 || !d || !dst_dev || ((uintptr_t) dst_dev & 1)) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (bufs[i] < 0 || bufs[i] >= (int) c->mot.size()) return VP9HIP_EINVAL;
+    int64_t pitch = 0;
+    const int64_t bytes = vp9hip_mvt_layout(d, &pitch);
+    if (bytes < 0) return VP9HIP_EINVAL;
+    const bool acc = d->source == VP9HIP_MVT_ACC;
+    if (acc && c->acc.empty()) return VP9HIP_EINVAL;
+    const std::pair<int, int> grid = { 2 * ((d->width + 7) >> 3), 2 * ((d->height + 7) >> 3) };
+    for (int i = 0; i < n; i++) {
+        if (!c->mot_gwh[bufs[i]].first) return VP9HIP_EAGAIN;
+        if (c->mot_gwh[bufs[i]] != grid) return VP9HIP_EINVAL;
+    }
+    if (grid.first > c->mot_pitch || grid.second > c->mot_rows) return VP9HIP_EBUG;   // a field is inside its planes
+    MotionScaleArgs a;
+    memset(&a, 0, sizeof(a));
+    const int64_t stride = d->frame_stride ? d->frame_stride : bytes;
+    a.frame_stride = stride; a.pitch = pitch; a.plane = pitch * d->out_height;
+    a.info_off = (int64_t) c->mot_pitch * c->mot_rows * 8;
+    a.src_pitch = c->mot_pitch;
+    a.gw = grid.first; a.gh = grid.second;
+    a.w = d->width; a.h = d->height;
+    a.ow = d->out_width; a.oh = d->out_height;
+    a.kx = (float) ((double) a.ow / (8.0 * a.w));
+    a.ky = (float) ((double) a.oh / (8.0 * a.h));
+    a.rcp = 1.0 / ((double) a.w * (double) a.h);
+    a.rx = 1.0 / (4.0 * a.ow); a.ry = 1.0 / (4.0 * a.oh);
+    hipSetDevice(c->dev);
+    hipStream_t st = stream ? (hipStream_t) stream : c->st;
+    for (int i0 = 0; i0 < n; i0 += MSC_MAX_FRAMES) {
+        const int k = std::min(n - i0, MSC_MAX_FRAMES);
+        for (int i = 0; i < k; i++) a.src[i] = acc ? c->acc[bufs[i0 + i]] : c->mot[bufs[i0 + i]];
+        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * stride;
+        HIPCHK(vp9hip_motion_scale_launch(a, d->source, d->format, d->planes, k, st));
     }
     return 0;
 }

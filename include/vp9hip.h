@@ -53,7 +53,9 @@ extern "C" {
  * vp9hip_decoder_frame_motion_acc) likewise: a new macro, a new struct and new symbols. The
  * residual tensors at model size (VP9HIP_RESID_*, vp9hip_resid_desc,
  * vp9hip_residual_frames_scaled, vp9hip_residual_scaled_host, vp9hip_decoder_residual_scaled)
- * likewise: a new enum, a new struct and new symbols. */
+ * likewise: a new enum, a new struct and new symbols. The motion tensors at model size
+ * (VP9HIP_MVT_*, vp9hip_mvt_desc, vp9hip_mvt_layout, vp9hip_motion_frames_scaled,
+ * vp9hip_motion_scaled_host, vp9hip_decoder_motion_scaled) likewise. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -737,8 +739,7 @@ int  vp9hip_residual_host(const vp9h_frame *pkt, int16_t *const planes[3], const
  * RGB(pred + r) - RGB(pred) differs from the matrix of r by at most one code per channel (two
  * floors of sums that differ by the linear part), at the same size with chroma at full
  * resolution, for every matrix, range and depth.
- * Not offered: the triangle and bicubic filters, source / destination rectangles, motion fields
- * at model size, energy maps. */
+ * Not offered: the triangle and bicubic filters, source / destination rectangles, energy maps. */
 enum { VP9HIP_RESID_YUV_I16, VP9HIP_RESID_YUV_F16, VP9HIP_RESID_RGB_I16, VP9HIP_RESID_RGB_F16 };
 /* The output of n frames: planar (n, 3, OH, OW) 16-bit elements; plane p of frame i starts at
  * dst + i frame_stride + p pitch OH. */
@@ -774,6 +775,84 @@ int  vp9hip_residual_frames_scaled(vp9hip_ctx *ctx, const int *bufs, int n, cons
  * 12, and what vp9hip_residual_frames_scaled refuses of d and dst; a refused call writes nothing. */
 int  vp9hip_residual_scaled_host(const int16_t *const planes[3], const ptrdiff_t pitch[3], int width, int height,
                                  int ss_h, int ss_v, int bpp, const vp9hip_resid_desc *d, void *dst);
+
+/* ---- motion tensors at model size: signed box resize of the motion fields, fused ----
+ * The third input of a compressed-domain model at its own size, beside the pixels (the scaled
+ * conversion) and the residual (above): an (N, 2 or 3, OH, OW) tensor of the motion vectors, and
+ * optionally of how much of each output sample is inter-coded. One launch per 32 frames
+ * (k_motion_scale) makes it from the fields of the motion export or of the accumulated motion.
+ *
+ * Definition, in integers.
+ * Source: the motion field of a buffer as vp9hip_frame_motion reports it (VP9HIP_MVT_CODED), or
+ * its accumulated field as vp9hip_frame_motion_acc reports it (VP9HIP_MVT_ACC), of a frame of
+ * visible size w x h: GW = 2 ((w + 7) >> 3) and GH = 2 ((h + 7) >> 3) must equal the field's
+ * grid. Every cell (r, c) has a value (vx, vy) and a flag has:
+ *   VP9HIP_MVT_CODED  has = info[r][c][0] != 255; (vx, vy) = mv[r][c][0] when has, else (0, 0).
+ *     The first reference's vector, as k_mvacc follows it; mv[r][c][1] is never looked at. The
+ *     stored bytes are taken as they are (info[r][c][0] of 3..254 is has = 1), so a consumer that
+ *     wrote into the views gets a defined result.
+ *   VP9HIP_MVT_ACC    has = hops > 0; (vx, vy) = (clamp(dx, -32768, 32767),
+ *     clamp(dy, -32768, 32767)) when has, else (0, 0). The clamp comes before any sum, so the
+ *     bounds below hold for every int32 record.
+ * Dense field: F[y][x] = the value of cell (y >> 2, x >> 2) for x < w, y < h. The output planes
+ * are sbox(Fx, OW, OH), sbox(Fy, OW, OH) and, with three planes, sbox(256 has, OW, OH), sbox the
+ * signed box of "residual tensors at model size": the weights wx, wy of "Box-filter resize", then
+ * floor((A + (w h >> 1)) / (w h)). Intra cells count as zero vectors in the mean; dividing by
+ * the coverage plane is the caller's choice.
+ * F is constant over a cell, so the sum may run over cells with the aggregated weight
+ *   W(o, c) = max(0, min((o + 1) n, (4 c + 4) on) - max(o n, 4 c on))      n = w or h, on = OW or OH
+ * which is the sum of wx(o, sx) over the cell's four pixel columns (rows). The output intervals
+ * end at n on, so a partly visible last cell is clipped without a special case and a cell beyond
+ * the visible size has weight 0; the weights of one output sum to n.
+ * Bounds: a column sum over cell rows is at most 2^14 2^15 = 2^29 in magnitude, |A| <= 2^43.
+ * With the sign bit flipped the values are u16 and the bounds and the division of box hold as
+ * they stand, as for the residual.
+ * Formats:
+ *   VP9HIP_MVT_I16  the integers: 1/8 luma pel of the source picture; the coverage plane 0..256.
+ *   VP9HIP_MVT_F16  the displacement in output pixels: x is half(float(v) * kx) with
+ *     kx = (float) ((double) OW / (8.0 w)), y the same with ky from OH and h, the coverage
+ *     half(float(c) * (1.0f / 256)): one float32 multiply and one round-to-nearest-even
+ *     conversion, as VP9HIP_OUT_RGBP_F16. A product beyond the half range becomes +-inf by that
+ *     rounding.
+ * Not offered: other filters, rectangles, the second reference's vectors, a per-reference split. */
+enum { VP9HIP_MVT_I16, VP9HIP_MVT_F16 };
+enum { VP9HIP_MVT_CODED, VP9HIP_MVT_ACC };
+/* The output of n frames: planar (n, P, OH, OW) 16-bit elements, P = planes; plane p of frame i
+ * starts at dst + i frame_stride + p pitch OH. Planes: x, y and, with P = 3, the coverage. */
+typedef struct vp9hip_mvt_desc {
+    int32_t format;            /* VP9HIP_MVT_I16 / _F16 */
+    int32_t source;            /* VP9HIP_MVT_CODED / _ACC */
+    int32_t planes;            /* 2 or 3 */
+    int32_t width, height;     /* the frames' visible size, 1..16384; set by vp9hip_decoder_motion_scaled */
+    int32_t out_width, out_height;   /* 1..16384 */
+    int64_t pitch;             /* bytes per output row, 0 = tight (2 OW); else a multiple of 16, >= 2 OW */
+    int64_t frame_stride;      /* bytes between frames, 0 = tight (P pitch OH); else even, >= P pitch OH */
+} vp9hip_mvt_desc;
+/* Bytes of one frame of d (P pitch OH) and the pitch in effect, or VP9HIP_EINVAL for a format,
+ * source or planes out of range, a width, height or output size outside 1..16384 or a pitch /
+ * frame stride the comments above exclude. Host only. */
+int64_t vp9hip_mvt_layout(const vp9hip_mvt_desc *d, int64_t *pitch);
+/* The fields of bufs[0 .. n-1] (any order, repeats allowed) into dst_dev, under the contract of
+ * vp9hip_residual_frames_scaled: it enqueues on `stream` (NULL: the current slot's main stream)
+ * and returns, orders nothing itself, passes the buffers' pointers as kernel arguments, 32 frames
+ * per launch (no device table, no allocation, no host wait: it can sit in a captured stream),
+ * writes only the OW x OH elements of each plane, and checks everything before the first launch:
+ * a refused call writes nothing. VP9HIP_EINVAL: no motion export, VP9HIP_MVT_ACC without
+ * VP9HIP_EXPORT_MOTION_ACC, a buffer index out of range, n <= 0, NULL bufs or desc, a format,
+ * source or planes out of range, a width or height outside 1..16384 or not giving a field's grid
+ * (hence fields of different grids), an output size outside 1..16384, a NULL or odd dst_dev, a
+ * pitch or frame stride the struct's comments exclude. VP9HIP_EAGAIN: a buffer without a field. */
+int  vp9hip_motion_frames_scaled(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip_mvt_desc *d,
+                                 void *dst_dev, void *stream);
+/* Host only, no device: the C statement of the definition above for one frame, one output
+ * sample at a time in 64-bit integers. VP9HIP_MVT_CODED reads mv ([GH][pitch_cells][2][2]) and
+ * info ([GH][pitch_cells][4]), VP9HIP_MVT_ACC reads acc ([GH][pitch_cells]); the other pointers
+ * may be NULL. Only cells (r, c) with 4 c < width and 4 r < height are read. dst is the frame's
+ * output in host memory, laid out by d (frame_stride is checked, not used). VP9HIP_EINVAL: a
+ * NULL d or dst or source array, pitch_cells below (width + 3) >> 2, and what
+ * vp9hip_motion_frames_scaled refuses of d and dst; a refused call writes nothing. */
+int  vp9hip_motion_scaled_host(const int16_t *mv, const uint8_t *info, const vp9hip_acc_cell *acc,
+                               ptrdiff_t pitch_cells, const vp9hip_mvt_desc *d, void *dst);
 
 /* ---- frame metrics: exact sums over two device frames ---------------------------------
  * What a consumer needs to decide which frames are worth converting: near-duplicate and scene
@@ -1232,6 +1311,14 @@ int  vp9hip_decoder_frame_residual(vp9hip_decoder *d, const vp9hip_decoded_frame
  * vp9hip_decoder_set_export's flags. */
 int  vp9hip_decoder_residual_scaled(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n,
                                     const vp9hip_resid_desc *desc, void *dst_dev, void *stream);
+/* The motion tensors of received frames through vp9hip_motion_frames_scaled, under the rules
+ * of vp9hip_decoder_residual_scaled: every frame must be of one size and held by the caller, else
+ * VP9HIP_EINVAL; desc's width and height are not read but taken from the frames; it only
+ * enqueues and releases nothing. A show_existing_frame output uses the shown buffer's field, as
+ * vp9hip_decoder_frame_motion_acc does. Needs VP9HIP_EXPORT_MOTION in
+ * vp9hip_decoder_set_export's flags, and VP9HIP_EXPORT_MOTION_ACC for VP9HIP_MVT_ACC. */
+int  vp9hip_decoder_motion_scaled(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n,
+                                  const vp9hip_mvt_desc *desc, void *dst_dev, void *stream);
 /* The metrics of the pairs (frames_a[i], frames_b[i]) of received frames through
  * vp9hip_frame_metrics, under the rules of vp9hip_decoder_convert: every frame of both arrays
  * must be of one size, depth and subsampling and held by the caller, else VP9HIP_EINVAL; the size
