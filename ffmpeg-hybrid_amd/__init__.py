@@ -161,7 +161,9 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9hip_resid_layout", "vp9hip_residual_frames_scaled", "vp9hip_residual_scaled_host",
                "vp9hip_decoder_residual_scaled",
                "vp9hip_mvt_layout", "vp9hip_motion_frames_scaled", "vp9hip_motion_scaled_host",
-               "vp9hip_decoder_motion_scaled"]
+               "vp9hip_decoder_motion_scaled",
+               "vp9hip_warp_layout", "vp9hip_acc_warp", "vp9hip_acc_warp_host", "vp9hip_warp_launch_dev",
+               "vp9hip_decoder_acc_warp"]
 
 
 def lib():
@@ -367,6 +369,20 @@ def lib():
                                            [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p]
     L.vp9hip_decoder_metrics.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(DecodedFrameInfo), ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    # accumulated residual
+    L.vp9hip_warp_layout.restype = ctypes.c_int64
+    L.vp9hip_warp_layout.argtypes = [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int64 * 3)]
+    L.vp9hip_acc_warp.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 5 + \
+                                 [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_acc_warp_host.argtypes = [vp3, ctypes.POINTER(ctypes.c_ssize_t * 3), vp3, ctypes.POINTER(ctypes.c_ssize_t * 3),
+                                       ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_int] * 7 + \
+                                      [ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_warp_launch_dev.argtypes = [ctypes.POINTER(ctypes.c_void_p)] * 3 + [u32p, ctypes.c_int,
+                                         ctypes.POINTER(ctypes.c_int64 * 3), ctypes.POINTER(ctypes.c_int32 * 2),
+                                         ctypes.c_int64] + [ctypes.c_int] * 7 + \
+                                        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_decoder_acc_warp.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(DecodedFrameInfo)] + \
+                                         [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     _lib_handle = L
     return L
 
@@ -1129,6 +1145,118 @@ def frame_metrics_host(planes_a, planes_b, width, height, bpp, ss_h=1, ss_v=1, c
     return (out, cmap) if cells else out
 
 
+# VP9HIP_WARP_*: the names acc_warp takes for interp and output
+WARP_MODES = {"nearest": 0, "bilinear": 1}
+WARP_OUTPUTS = {"residual": 0, "picture": 1}
+
+
+def warp_layout(width, height, ss_h=1, ss_v=1):
+    """(bytes of one pair, (Y, U, V byte offsets)) of an accumulated-residual output
+    (vp9hip_warp_layout): tight 2-byte planes, Y then U then V."""
+    off = (ctypes.c_int64 * 3)()
+    stride = lib().vp9hip_warp_layout(int(width), int(height), int(ss_h), int(ss_v), ctypes.byref(off))
+    _check("vp9hip_warp_layout", stride)
+    return stride, tuple(off)
+
+
+def _warp_names(fn, output, interp):
+    if output not in WARP_OUTPUTS or interp not in WARP_MODES:
+        raise Vp9HipError(fn, EINVAL)
+    return WARP_MODES[interp], WARP_OUTPUTS[output]
+
+
+def acc_warp_host(planes_a, planes_b, acc, serial_b, width, height, bpp, ss_h=1, ss_v=1, output="residual",
+                  interp="nearest", mask=False):
+    """One pair of the accumulated residual on the host, vp9hip_acc_warp_host, the C statement of
+    the definition in include/vp9hip.h ("accumulated residual"): planes_a / planes_b are three 2-D
+    arrays each (uint8 at 8 bits, else uint16; rows may be strided), acc a's ACC_CELL array
+    (GH, GW), serial_b the serial of b's field. Returns (y, u, v), or (y, u, v, mask) with
+    mask=True: int16 arrays (H, W), (CH, CW), (CH, CW), for output "picture" the uint16 codes'
+    bit pattern; the mask uint8 (GH, GW)."""
+    fn = "vp9hip_acc_warp_host"
+    mode, outp = _warp_names(fn, output, interp)
+    dt = np.uint8 if bpp == 8 else np.uint16
+    width, height = int(width), int(height)
+    stride, off = warp_layout(width, height, ss_h, ss_v)
+    cw, ch = (width + ss_h) >> ss_h, (height + ss_v) >> ss_v
+    gw, gh = 2 * ((width + 7) >> 3), 2 * ((height + 7) >> 3)
+
+    def prep(planes):
+        out = []
+        for p, a in enumerate(planes):
+            a = np.asarray(a)
+            if a.ndim != 2 or a.dtype != dt:
+                raise ValueError("acc_warp_host: planes must be 2-D %s arrays" % np.dtype(dt).name)
+            if a.strides[1] != a.itemsize or a.strides[0] < 0:
+                a = np.ascontiguousarray(a)
+            pw, ph = (width, height) if p == 0 else (cw, ch)
+            if a.shape[0] < ph or a.shape[1] < pw:
+                raise ValueError("acc_warp_host: plane %d is smaller than %d x %d" % (p, pw, ph))
+            out.append(a)
+        if len(out) != 3:
+            raise ValueError("acc_warp_host: three planes a frame")
+        return out
+    pa, pb = prep(planes_a), prep(planes_b)
+    acc = np.ascontiguousarray(acc, ACC_CELL)
+    if acc.shape != (gh, gw):
+        raise ValueError("acc_warp_host: acc must be (%d, %d) cells" % (gh, gw))
+    dst = np.full(stride // 2, 0x5a5a, np.int16)
+    m = np.full((gh, gw), 0x5a, np.uint8) if mask else None
+    ap, als = _plane_ptrs(pa)
+    bp, bls = _plane_ptrs(pb)
+    _check(fn, lib().vp9hip_acc_warp_host(ctypes.byref(ap), ctypes.byref(als), ctypes.byref(bp), ctypes.byref(bls),
+                                          acc.ctypes.data, int(serial_b) & 0xffffffff, width, height, int(bpp), int(ss_h),
+                                          int(ss_v), mode, outp, dst.ctypes.data, m.ctypes.data if mask else None))
+    y = dst[:width * height].reshape(height, width)
+    u = dst[off[1] // 2:off[1] // 2 + cw * ch].reshape(ch, cw)
+    v = dst[off[2] // 2:off[2] // 2 + cw * ch].reshape(ch, cw)
+    return (y, u, v, m) if mask else (y, u, v)
+
+
+def _warp_out(n, width, height, ss_h, ss_v, mask, out):
+    """The destinations of an acc_warp call: (flat int16 cuda tensor, (y, u, v) views of it,
+    uint8 (N, GH, GW) mask or None). `out` is a contiguous int16 cuda tensor of at least
+    N * stride / 2 elements, or None."""
+    import torch
+    sane = 1 <= width <= 16384 and 1 <= height <= 16384 and ss_h in (0, 1) and ss_v in (0, 1)
+    stride, off = warp_layout(width, height, ss_h, ss_v) if sane else (2, (0, 0, 0))
+    n = max(n, 0)
+    need = n * stride // 2
+    if out is None:
+        out = torch.empty(max(need, 4), dtype=torch.int16, device="cuda")
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int16 and out.is_contiguous()
+              and out.numel() >= need):
+        raise ValueError("acc_warp: out must be a contiguous int16 cuda tensor of at least %d elements" % need)
+    flat = out.view(-1)
+    views, m = None, None
+    if sane:
+        cw, ch = (width + ss_h) >> ss_h, (height + ss_v) >> ss_v
+        views = tuple(flat.as_strided((n, ph, pw), (stride // 2, pw, 1), flat.storage_offset() + o // 2)
+                      for o, (pw, ph) in zip(off, ((width, height), (cw, ch), (cw, ch))))
+        if mask:
+            m = torch.empty((max(n, 1), 2 * ((height + 7) >> 3), 2 * ((width + 7) >> 3)), dtype=torch.uint8, device="cuda")[:n]
+    elif mask:
+        m = torch.empty((max(n, 1), 1, 1), dtype=torch.uint8, device="cuda")[:n]
+    return flat, views, m
+
+
+def warp_launch_dev(a_ptrs, b_ptrs, acc_ptrs, serials, plane_off, pitch, acc_pitch, width, height, bpp, ss_h, ss_v,
+                    interp, output, dst_ptr, mask_ptr=None, stream=None):
+    """k_acc_warp over caller-made device pictures and fields (vp9hip_warp_launch_dev; the bench
+    tool and the crafted-field tests): per pair the device pointers of frame a, frame b and a's
+    field and b's serial; plane_off the planes' byte offsets inside a frame, pitch the (luma,
+    chroma) row pitch in bytes, acc_pitch the field's pitch in cells."""
+    fn = "vp9hip_warp_launch_dev"
+    mode, outp = _warp_names(fn, output, interp)
+    n = len(a_ptrs)
+    arr = lambda v: (ctypes.c_void_p * max(n, 1))(*v)   # noqa: E731
+    _check(fn, lib().vp9hip_warp_launch_dev(arr(a_ptrs), arr(b_ptrs), arr(acc_ptrs),
+                                            (ctypes.c_uint32 * max(n, 1))(*[int(x) & 0xffffffff for x in serials]), n,
+                                            ctypes.byref((ctypes.c_int64 * 3)(*plane_off)),
+                                            ctypes.byref((ctypes.c_int32 * 2)(*pitch)), int(acc_pitch), int(width), int(height),
+                                            int(bpp), int(ss_h), int(ss_v), mode, outp, dst_ptr, mask_ptr, stream))
+
+
 def psnr(metrics, bpp, width, height, ss_h=1, ss_v=1):
     """PSNR in dB of each plane from metrics records (a host array (..., 3, 8), e.g.
     Device.metrics(...).cpu()): float64 (..., 3), 10 log10((2^bpp - 1)^2 count / sse) with count
@@ -1689,6 +1817,45 @@ class Device:
             _check("vp9hip_frame_metrics", _enqueue_for_torch(main.value, stream, call))
         return (res, cmap) if cells else res
 
+    def acc_warp(self, bufs, root_bufs, output="residual", interp="nearest", mask=False, size=None, out=None, stream=None):
+        """The accumulated residual of the pairs (bufs[i], root_bufs[i]) of device buffers on the GPU
+        (vp9hip_acc_warp, the definition in include/vp9hip.h "accumulated residual"): frame
+        bufs[i] minus frame root_bufs[i] displaced by bufs[i]'s accumulated motion, wherever a
+        cell's chain ended in the frame root_bufs[i] holds (elsewhere 0); output "picture" gives
+        the displaced picture itself (elsewhere bufs[i]'s own samples). interp "nearest" or
+        "bilinear". Returns (y, u, v), or (y, u, v, mask) with mask=True: int16 cuda views
+        (N, H, W), (N, CH, CW), (N, CH, CW) of one allocation laid out by warp_layout, for
+        "picture" the uint16 codes' bit pattern (codes of up to 12 bits are the values
+        themselves); the mask uint8 (N, GH, GW), 1 where the cell applies. `size` = (width,
+        height) is the visible size (default: the configured size); `out` a contiguous int16 cuda
+        tensor to write into (else one is allocated). Needs set_export(motion_acc=True). Runs in
+        the order of torch's current stream (or on `stream`, a hipStream_t handle; see
+        _enqueue_for_torch) and does not wait: order it after the frames' producer (sync(), or
+        vp9hip_slot_stream_wait), as for metrics. Needs torch imported before the library was
+        loaded (see _torch_first)."""
+        fn = "vp9hip_acc_warp"
+        if not _torch_first:
+            raise Vp9HipUnavailable("acc_warp: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        mode, outp = _warp_names(fn, output, interp)
+        bufs, root_bufs = [int(b) for b in bufs], [int(b) for b in root_bufs]
+        n = len(bufs)
+        if len(root_bufs) != n:
+            raise ValueError("acc_warp: bufs and root_bufs differ in length")
+        w, h = (int(x) for x in size) if size is not None else (self.w, self.h)
+        flat, views, m = _warp_out(n, w, h, getattr(self, "ss_h", 1), getattr(self, "ss_v", 1), mask, out)
+        aa, ab = (ctypes.c_int * max(n, 1))(*bufs), (ctypes.c_int * max(n, 1))(*root_bufs)
+        call = lambda st: lib().vp9hip_acc_warp(self._c, aa, ab, n, w, h, mode, outp, flat.data_ptr(),
+                                                m.data_ptr() if mask else None, st)
+        main = ctypes.c_void_p()
+        # an unconfigured context has no buffer to ask for its stream: the library refuses the call itself
+        if lib().vp9hip_frame_device(self._c, 0, (ctypes.c_void_p * 3)(), (ctypes.c_ssize_t * 3)(), None, None,
+                                     ctypes.byref(main)):
+            _check(fn, call(stream))
+        else:
+            _check(fn, _enqueue_for_torch(main.value, stream, call))
+        return views + (m,) if mask else views
+
     def upload(self, buf, planes):
         planes = [np.ascontiguousarray(p) for p in planes]
         ptrs, ls = self._plane_args(planes)
@@ -1990,6 +2157,36 @@ class Decoder:
         _check("vp9hip_decoder_metrics", _enqueue_for_torch(main.value, None, call))
         torch.cuda.current_stream().synchronize()
         return (res, cmap) if cells else res
+
+    def acc_warp(self, infos, root_infos, output="residual", interp="nearest", mask=False):
+        """The accumulated residual of the pairs (infos[i], root_infos[i]) of frames of
+        receive_frame(download=False) (all of one size, depth and subsampling, all still held;
+        needs export_motion_acc=True), as Device.acc_warp returns it (vp9hip_decoder_acc_warp):
+        keep the key frame un-released and pass it as every root. Runs on torch's current stream
+        and waits for it; like metrics it releases nothing."""
+        fn = "vp9hip_decoder_acc_warp"
+        if not _torch_first:
+            raise Vp9HipUnavailable("acc_warp: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        import torch
+        mode, outp = _warp_names(fn, output, interp)
+        infos, root_infos = list(infos), list(root_infos)
+        n = len(infos)
+        if len(root_infos) != n:
+            raise ValueError("acc_warp: infos and root_infos differ in length")
+        if not n:
+            raise Vp9HipError(fn, EINVAL)
+        f = infos[0]
+        flat, views, m = _warp_out(n, f.width, f.height, f.ss_h, f.ss_v, mask, None)
+        aa, ab = (DecodedFrameInfo * n)(*infos), (DecodedFrameInfo * n)(*root_infos)
+        main = ctypes.c_void_p()
+        _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
+                                                                (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
+        call = lambda st: lib().vp9hip_decoder_acc_warp(self._d, aa, ab, n, mode, outp, flat.data_ptr(),
+                                                        m.data_ptr() if mask else None, st)
+        _check(fn, _enqueue_for_torch(main.value, None, call))
+        torch.cuda.current_stream().synchronize()
+        return views + (m,) if mask else views
 
     def flush(self):
         _check("vp9hip_decoder_flush", lib().vp9hip_decoder_flush(self._d))

@@ -539,6 +539,27 @@ extern "C" int vp9hip_decoder_motion_scaled(vp9hip_decoder *d, const vp9hip_deco
     return vp9hip_motion_frames_scaled(d->ctx, bufs.data(), n, &o, dst_dev, stream);
 }
 
+// The accumulated residual of pairs of received frames (vp9hip_acc_warp), under the metrics'
+// rules: complete frames that stay the caller's, nothing ordered and nothing released. A
+// show_existing_frame output names the shown buffer, so its field and serial are that frame's.
+extern "C" int vp9hip_decoder_acc_warp(vp9hip_decoder *d, const vp9hip_decoded_frame *frames_a,
+                                       const vp9hip_decoded_frame *frames_b, int n, int mode, int output, void *dst_dev,
+                                       uint8_t *mask_dev, void *stream)
+{
+    if (!d || !frames_a || !frames_b || n <= 0 || !d->configured) return VP9HIP_EINVAL;
+    std::vector<int> ba(n), bb(n);
+    const vp9hip_decoded_frame &f0 = frames_a[0];
+    for (int s = 0; s < 2; s++)
+        for (int i = 0; i < n; i++) {
+            const vp9hip_decoded_frame &f = s ? frames_b[i] : frames_a[i];
+            if (f.buf < 0 || f.buf >= d->nbufs || d->pins[f.buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+            if (f.width != f0.width || f.height != f0.height || f.bpp != f0.bpp || f.ss_h != f0.ss_h || f.ss_v != f0.ss_v)
+                return VP9HIP_EINVAL;
+            (s ? bb : ba)[i] = f.buf;
+        }
+    return vp9hip_acc_warp(d->ctx, ba.data(), bb.data(), n, f0.width, f0.height, mode, output, dst_dev, mask_dev, stream);
+}
+
 // avcodec_flush_buffers (vp9.c:1865-1883): drop the decoder delay and the reference
 // state; frames already handed out stay valid until released.
 extern "C" int vp9hip_decoder_flush(vp9hip_decoder *d)

@@ -47,6 +47,7 @@
 #include "vp9hip_mvacc.h"
 #include "vp9hip_residual.h"
 #include "vp9hip_metrics.h"
+#include "vp9hip_warp.h"
 #include "vp9hip_residual_scale.h"
 #include "vp9hip_motion_scale.h"
 #include "vp9hip_residn.h"
@@ -4141,4 +4142,98 @@ extern "C" int vp9hip_motion_frames_scaled(vp9hip_ctx *c, const int *bufs, int n
         HIPCHK(vp9hip_motion_scale_launch(a, d->source, d->format, d->planes, k, st));
     }
     return 0;
+}
+
+// Accumulated residual (include/vp9hip.h "accumulated residual"; k_acc_warp in vp9hip_warp.hip).
+// warp_launches: the launches of a checked call, WARP_MAX_PAIRS pairs each; rec(i, k) fills pair
+// i's record into slot k of the arguments.
+template <class F>
+static int warp_launches(WarpArgs &a, int n, int hbd, int mode, int output, void *dst_dev, uint8_t *mask_dev, hipStream_t st,
+                         F rec)
+{
+    for (int i0 = 0; i0 < n; i0 += WARP_MAX_PAIRS) {
+        const int k = std::min(n - i0, WARP_MAX_PAIRS);
+        for (int i = 0; i < k; i++) rec(i0 + i, i);
+        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * a.dstride;
+        a.mask = mask_dev ? mask_dev + (size_t) i0 * a.gh * a.gw : nullptr;
+        HIPCHK(vp9hip_warp_launch(a, hbd, mode, output, k, st));
+    }
+    return 0;
+}
+
+// The sizes, grid and output layout of a call's arguments; < 0: a size or subsampling out of range
+static int warp_geometry(WarpArgs &a, int width, int height, int ss_h, int ss_v)
+{
+    memset(&a, 0, sizeof(a));
+    a.dstride = vp9hip_warp_layout(width, height, ss_h, ss_v, a.doff);
+    if (a.dstride < 0) return VP9HIP_EINVAL;
+    a.w = width; a.h = height;
+    a.cw = (width + ss_h) >> ss_h; a.ch = (height + ss_v) >> ss_v;
+    a.ss_h = ss_h; a.ss_v = ss_v;
+    a.gw = 2 * ((width + 7) >> 3); a.gh = 2 * ((height + 7) >> 3);
+    return 0;
+}
+
+// Everything is validated before the first launch, so a refused call writes nothing; the
+// records travel as kernel arguments, like the metrics' buffers.
+extern "C" int vp9hip_acc_warp(vp9hip_ctx *c, const int *bufs_a, const int *bufs_b, int n, int width, int height,
+                               int mode, int output, void *dst_dev, uint8_t *mask_dev, void *stream)
+{
+    if (!c || c->bufs.empty() || c->acc.empty() || !bufs_a || !bufs_b || n <= 0 || !dst_dev) return VP9HIP_EINVAL;
+    if (width < 1 || height < 1 || width > c->w || height > c->h || ((uintptr_t) dst_dev & 7)) return VP9HIP_EINVAL;
+    if ((mode != VP9HIP_WARP_NEAREST && mode != VP9HIP_WARP_BILINEAR) ||
+        (output != VP9HIP_WARP_RESIDUAL && output != VP9HIP_WARP_PICTURE))
+        return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (bufs_a[i] < 0 || bufs_a[i] >= (int) c->acc.size() || bufs_b[i] < 0 || bufs_b[i] >= (int) c->acc.size())
+            return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!c->mot_gwh[bufs_a[i]].first || !c->mot_gwh[bufs_b[i]].first) return VP9HIP_EAGAIN;
+    WarpArgs a;
+    if (warp_geometry(a, width, height, c->ss_h, c->ss_v) < 0) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (c->mot_gwh[bufs_a[i]].first != a.gw || c->mot_gwh[bufs_a[i]].second != a.gh) return VP9HIP_EINVAL;
+    for (int p = 0; p < 3; p++) a.off[p] = (int64_t) c->plane_off[p];
+    a.pitch[0] = (int32_t) (c->pitch[0] * c->bypp); a.pitch[1] = (int32_t) (c->pitch[1] * c->bypp);
+    a.acc_pitch = (int32_t) c->mot_pitch;
+    hipSetDevice(c->dev);
+    return warp_launches(a, n, c->hb, mode, output, dst_dev, mask_dev, stream ? (hipStream_t) stream : c->st,
+                         [&](int i, int k) {
+        a.a[k] = c->bufs[bufs_a[i]];
+        a.b[k] = c->bufs[bufs_b[i]];
+        a.acc[k] = (const uint4 *) c->acc[bufs_a[i]];
+        a.serial[k] = c->acc_serial[bufs_b[i]];
+    });
+}
+
+extern "C" int vp9hip_warp_launch_dev(const void *const *a_dev, const void *const *b_dev, const void *const *acc_dev,
+                                      const uint32_t *serial_b, int n, const int64_t plane_off[3], const int32_t pitch[2],
+                                      int64_t acc_pitch_cells, int width, int height, int bpp, int ss_h, int ss_v,
+                                      int mode, int output, void *dst_dev, uint8_t *mask_dev, void *stream)
+{
+    if (!a_dev || !b_dev || !acc_dev || !serial_b || n <= 0 || !plane_off || !pitch || !dst_dev || ((uintptr_t) dst_dev & 7))
+        return VP9HIP_EINVAL;
+    if ((bpp != 8 && bpp != 10 && bpp != 12) || (mode != VP9HIP_WARP_NEAREST && mode != VP9HIP_WARP_BILINEAR) ||
+        (output != VP9HIP_WARP_RESIDUAL && output != VP9HIP_WARP_PICTURE))
+        return VP9HIP_EINVAL;
+    WarpArgs a;
+    if (warp_geometry(a, width, height, ss_h, ss_v) < 0) return VP9HIP_EINVAL;
+    const int hbd = bpp > 8, bypp = hbd ? 2 : 1;
+    if (pitch[0] < a.w * bypp || pitch[1] < a.cw * bypp || (hbd && ((pitch[0] | pitch[1]) & 1))) return VP9HIP_EINVAL;
+    if (acc_pitch_cells < a.gw || acc_pitch_cells > INT32_MAX) return VP9HIP_EINVAL;
+    for (int p = 0; p < 3; p++)
+        if (plane_off[p] < 0 || (hbd && (plane_off[p] & 1))) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!a_dev[i] || !b_dev[i] || !acc_dev[i] || ((uintptr_t) acc_dev[i] & 15) ||
+            (hbd && (((uintptr_t) a_dev[i] | (uintptr_t) b_dev[i]) & 1)))
+            return VP9HIP_EINVAL;
+    for (int p = 0; p < 3; p++) a.off[p] = plane_off[p];
+    a.pitch[0] = pitch[0]; a.pitch[1] = pitch[1];
+    a.acc_pitch = (int32_t) acc_pitch_cells;
+    return warp_launches(a, n, hbd, mode, output, dst_dev, mask_dev, (hipStream_t) stream, [&](int i, int k) {
+        a.a[k] = (const uint8_t *) a_dev[i];
+        a.b[k] = (const uint8_t *) b_dev[i];
+        a.acc[k] = (const uint4 *) acc_dev[i];
+        a.serial[k] = serial_b[i];
+    });
 }

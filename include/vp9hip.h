@@ -55,7 +55,9 @@ extern "C" {
  * vp9hip_residual_frames_scaled, vp9hip_residual_scaled_host, vp9hip_decoder_residual_scaled)
  * likewise: a new enum, a new struct and new symbols. The motion tensors at model size
  * (VP9HIP_MVT_*, vp9hip_mvt_desc, vp9hip_mvt_layout, vp9hip_motion_frames_scaled,
- * vp9hip_motion_scaled_host, vp9hip_decoder_motion_scaled) likewise. */
+ * vp9hip_motion_scaled_host, vp9hip_decoder_motion_scaled) likewise. The accumulated residual
+ * (VP9HIP_WARP_*, vp9hip_warp_layout, vp9hip_acc_warp, vp9hip_acc_warp_host,
+ * vp9hip_warp_launch_dev, vp9hip_decoder_acc_warp) likewise: new enums and new symbols. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -909,6 +911,85 @@ int  vp9hip_frame_metrics_host(const void *const a[3], const ptrdiff_t linesize_
                                int width, int height, int bpp, int ss_h, int ss_v,
                                int64_t out[24], int32_t *cells);
 
+/* ---- accumulated residual: frame t minus the root frame displaced by the accumulated motion ----
+ * The input CoViAR-style models read beside the accumulated motion, and the motion-compensated
+ * prediction of a frame from its root (label and feature propagation): one launch per 32 pairs
+ * (k_acc_warp) gathers the root's samples through the accumulated field, where the fields and
+ * both pictures are resident. On demand, like the frame metrics: nothing in the decode path
+ * changes, and without the call nothing is launched or allocated.
+ *
+ * Definition, in integers. A pair is (a, b): two buffers of one configured context. a must hold
+ * an accumulated field (vp9hip_frame_motion_acc would succeed) whose grid GW x GH is the grid of
+ * the width x height given, GW = 2 ((width + 7) >> 3), GH = 2 ((height + 7) >> 3); width x height
+ * is the visible luma size, the top-left crop as in vp9hip_frame_metrics, and the chroma planes
+ * are ((width + ss_h) >> ss_h) x ((height + ss_v) >> ss_v). b must hold an accumulated field too;
+ * S_b is the serial stored with it (host-side state, no device read). A sample is the stored
+ * code, uint8_t at 8 bits, else uint16_t, not masked to the depth.
+ * For plane p with subsampling (sh, sv) ((0, 0) for luma), visible size PW x PH, and sample (x, y):
+ *   1. The cell is c = (x << sh) >> 2, r = (y << sv) >> 2, and q = acc_a[r][c].
+ *   2. The cell applies iff q.hops > 0 && q.root == S_b. So intra cells never apply, chains that
+ *      ended NOFIELD / SCALED (root 0; a serial is never 0) never apply, and a b that another
+ *      frame has since been decoded into never applies.
+ *   3. vx = clamp(q.dx, -32768, 32767), vy likewise, as VP9HIP_MVT_ACC. Px = vx << (1 - sh) and
+ *      Py = vy << (1 - sv) are in 1/16 sample of the plane (<< on a negative value multiplies).
+ *   4. VP9HIP_WARP_NEAREST: pred = B_p[cl(y + ((Py + 8) >> 4), PH)][cl(x + ((Px + 8) >> 4), PW)]
+ *      with cl(v, n) = clamp(v, 0, n - 1) and arithmetic shifts.
+ *   5. VP9HIP_WARP_BILINEAR: x0 = x + (Px >> 4), fx = Px & 15, y0 and fy likewise; the four
+ *      samples s00, s01 (row cl(y0, PH), columns cl(x0, PW), cl(x0 + 1, PW)) and s10, s11 (row
+ *      cl(y0 + 1, PH));
+ *      pred = ((16 - fx)(16 - fy) s00 + fx (16 - fy) s01 + (16 - fx) fy s10 + fx fy s11 + 128) >> 8,
+ *      at most 256 * 65535 + 128 < 2^32.
+ *   6. VP9HIP_WARP_RESIDUAL (int16_t): clamp(A_p[y][x] - pred, -32768, 32767) where the cell
+ *      applies, 0 elsewhere.
+ *   7. VP9HIP_WARP_PICTURE (uint16_t): pred where the cell applies, A_p[y][x] elsewhere.
+ *   8. The optional mask is uint8_t, tight (n, GH, GW): 1 where the cell applies, else 0.
+ * The destination is tight per pair, 2-byte elements: Y (PH x PW of luma), then U, then V;
+ * vp9hip_warp_layout gives the three offsets and the pair stride.
+ * Not offered: the result at model size, sub-pel filters other than bilinear, the second
+ * reference, a per-hop warp. */
+enum { VP9HIP_WARP_NEAREST, VP9HIP_WARP_BILINEAR };
+enum { VP9HIP_WARP_RESIDUAL, VP9HIP_WARP_PICTURE };
+/* Bytes of one pair's output (the stride between pairs) and, if off is not NULL, the byte
+ * offsets of its Y, U and V planes; VP9HIP_EINVAL for a width or height outside 1..16384 or a
+ * subsampling other than 0 / 1. Host only. */
+int64_t vp9hip_warp_layout(int width, int height, int ss_h, int ss_v, int64_t off[3]);
+/* The pairs (bufs_a[i], bufs_b[i]), i < n, into dst_dev (device memory, n strides of
+ * vp9hip_warp_layout) and, if mask_dev is not NULL, their masks into mask_dev (n * GH * GW
+ * bytes), under the contract of vp9hip_frame_metrics: any buffers in any order, repeats and
+ * a == b allowed; n above 32 is split into launches of at most 32 pairs; it enqueues on `stream`
+ * (NULL: the current slot's main stream) and returns without waiting, orders nothing itself, does
+ * not allocate and reads no device memory on the host, so it can sit in a captured stream; only
+ * the bytes of the layout (and of the mask) are written; everything is checked before the first
+ * launch: a refused call writes nothing. VP9HIP_EINVAL: a context without
+ * VP9HIP_EXPORT_MOTION_ACC or not configured, a buffer index out of range, n <= 0, NULL bufs_a,
+ * bufs_b or dst_dev, a width / height outside 1 .. the configured size or whose grid is not that
+ * of a's field, dst_dev not 8-byte aligned, an unknown mode or output. VP9HIP_EAGAIN: an a or a
+ * b without a field (checked after the indices, before the grid). */
+int  vp9hip_acc_warp(vp9hip_ctx *ctx, const int *bufs_a, const int *bufs_b, int n, int width, int height,
+                     int mode, int output, void *dst_dev, uint8_t *mask_dev, void *stream);
+/* Host only, no device: the C statement of the definition above for one pair of host frames
+ * (linesize in bytes) and a's field as a tight array acc[GH][GW], one sample at a time in 64-bit
+ * integers; dst is the pair's output laid out by vp9hip_warp_layout, mask ([GH][GW]) may be NULL.
+ * VP9HIP_EINVAL: a NULL a, b, linesize, acc or dst, sizes outside 1..16384, bpp not 8 / 10 / 12,
+ * ss not 0 / 1, an unknown mode or output; a refused call writes nothing. */
+int  vp9hip_acc_warp_host(const void *const a[3], const ptrdiff_t linesize_a[3],
+                          const void *const b[3], const ptrdiff_t linesize_b[3],
+                          const vp9hip_acc_cell *acc, uint32_t serial_b, int width, int height, int bpp,
+                          int ss_h, int ss_v, int mode, int output, void *dst, uint8_t *mask);
+/* Diagnostics (tools/acc_warp_bench.py, the crafted-field tests): k_acc_warp over caller-made
+ * pictures and fields in device memory, on `stream`, split into launches of 32 pairs like
+ * vp9hip_acc_warp. Pair i reads the frames a_dev[i] and b_dev[i] (planes at plane_off[p] bytes
+ * inside each, rows pitch[0] / pitch[1] bytes apart for luma / chroma, covering the visible
+ * size), the field acc_dev[i] (vp9hip_acc_cell [GH][acc_pitch_cells], 16-byte aligned) and the
+ * serial serial_b[i]; the arrays themselves are host memory. VP9HIP_EINVAL: NULL arguments,
+ * n <= 0, sizes outside 1..16384, bpp not 8 / 10 / 12, ss not 0 / 1, a pitch that does not
+ * cover the plane's visible width or is odd above 8 bits, acc_pitch_cells below GW, dst_dev not
+ * 8-byte aligned, an unknown mode or output. */
+int  vp9hip_warp_launch_dev(const void *const *a_dev, const void *const *b_dev, const void *const *acc_dev,
+                            const uint32_t *serial_b, int n, const int64_t plane_off[3], const int32_t pitch[2],
+                            int64_t acc_pitch_cells, int width, int height, int bpp, int ss_h, int ss_v,
+                            int mode, int output, void *dst_dev, uint8_t *mask_dev, void *stream);
+
 /* Upload host planes into device buffer `buf` (test hook for reference frames). */
 int  vp9hip_upload_frame(vp9hip_ctx *ctx, int buf, const uint8_t *const planes[3],
                          const ptrdiff_t linesize[3]);
@@ -1327,6 +1408,15 @@ int  vp9hip_decoder_motion_scaled(vp9hip_decoder *d, const vp9hip_decoded_frame 
 int  vp9hip_decoder_metrics(vp9hip_decoder *d, const vp9hip_decoded_frame *frames_a,
                             const vp9hip_decoded_frame *frames_b, int n,
                             int64_t *out_dev, int32_t *cells_dev, void *stream);
+/* The accumulated residual of the pairs (frames_a[i], frames_b[i]) of received frames through
+ * vp9hip_acc_warp, under the rules of vp9hip_decoder_metrics: every frame of both arrays must be
+ * of one size, depth and subsampling and held by the caller (a released frame is
+ * VP9HIP_EINVAL); the size is the frames' own; it only enqueues and releases nothing. A
+ * show_existing_frame output uses the shown buffer's field and serial. Needs
+ * VP9HIP_EXPORT_MOTION_ACC in vp9hip_decoder_set_export's flags. */
+int  vp9hip_decoder_acc_warp(vp9hip_decoder *d, const vp9hip_decoded_frame *frames_a,
+                             const vp9hip_decoded_frame *frames_b, int n, int mode, int output,
+                             void *dst_dev, uint8_t *mask_dev, void *stream);
 /* avcodec_flush_buffers: drop queued frames and reference state (seek). */
 int  vp9hip_decoder_flush(vp9hip_decoder *d);
 
