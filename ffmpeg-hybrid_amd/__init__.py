@@ -163,7 +163,9 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9hip_mvt_layout", "vp9hip_motion_frames_scaled", "vp9hip_motion_scaled_host",
                "vp9hip_decoder_motion_scaled",
                "vp9hip_warp_layout", "vp9hip_acc_warp", "vp9hip_acc_warp_host", "vp9hip_warp_launch_dev",
-               "vp9hip_decoder_acc_warp"]
+               "vp9hip_decoder_acc_warp",
+               "vp9hip_warpt_layout", "vp9hip_acc_warp_scaled", "vp9hip_acc_warp_scaled_host",
+               "vp9hip_warp_scale_launch_dev", "vp9hip_decoder_acc_warp_scaled"]
 
 
 def lib():
@@ -383,6 +385,20 @@ def lib():
                                         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.vp9hip_decoder_acc_warp.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(DecodedFrameInfo)] + \
                                          [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    # accumulated residual at model size
+    L.vp9hip_warpt_layout.restype = ctypes.c_int64
+    L.vp9hip_warpt_layout.argtypes = [ctypes.POINTER(WarptDesc), ctypes.POINTER(ctypes.c_int64)]
+    L.vp9hip_acc_warp_scaled.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                         ctypes.POINTER(WarptDesc), ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_acc_warp_scaled_host.argtypes = [vp3, ctypes.POINTER(ctypes.c_ssize_t * 3), vp3, ctypes.POINTER(ctypes.c_ssize_t * 3),
+                                              ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_int] * 3 + \
+                                             [ctypes.POINTER(WarptDesc), ctypes.c_void_p]
+    L.vp9hip_warp_scale_launch_dev.argtypes = [ctypes.POINTER(ctypes.c_void_p)] * 3 + [u32p, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_int64 * 3), ctypes.POINTER(ctypes.c_int32 * 2),
+                                               ctypes.c_int64] + [ctypes.c_int] * 3 + \
+                                              [ctypes.POINTER(WarptDesc), ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_decoder_acc_warp_scaled.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(DecodedFrameInfo),
+                                                 ctypes.c_int, ctypes.POINTER(WarptDesc), ctypes.c_void_p, ctypes.c_void_p]
     _lib_handle = L
     return L
 
@@ -427,6 +443,14 @@ class OutDesc(ctypes.Structure):
 class ResidDesc(ctypes.Structure):
     """vp9hip_resid_desc: the format and layout of residual tensors at model size."""
     _fields_ = [("format", ctypes.c_int32), ("colorspace", ctypes.c_int32), ("full_range", ctypes.c_int32),
+                ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32), ("pitch", ctypes.c_int64),
+                ("frame_stride", ctypes.c_int64)]
+
+
+class WarptDesc(ctypes.Structure):
+    """vp9hip_warpt_desc: the format, mode and layout of the accumulated residual at model size."""
+    _fields_ = [("format", ctypes.c_int32), ("colorspace", ctypes.c_int32), ("full_range", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("planes", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32), ("pitch", ctypes.c_int64),
                 ("frame_stride", ctypes.c_int64)]
 
@@ -1257,6 +1281,108 @@ def warp_launch_dev(a_ptrs, b_ptrs, acc_ptrs, serials, plane_off, pitch, acc_pit
                                             int(bpp), int(ss_h), int(ss_v), mode, outp, dst_ptr, mask_ptr, stream))
 
 
+def _warpt_desc(fn, fmt, interp, coverage, resize, size, colorspace, full_range, pitch, frame_stride):
+    """The WarptDesc of an acc_warp_tensors call: resize=None is the visible size itself."""
+    if fmt not in RESID_FORMATS or interp not in WARP_MODES:
+        raise Vp9HipError(fn, EINVAL)
+    w, h = (int(x) for x in size)
+    ow, oh = (int(x) for x in (resize if resize is not None else size))
+    return WarptDesc(RESID_FORMATS[fmt], int(colorspace), int(bool(full_range)), WARP_MODES[interp], 4 if coverage else 3,
+                     w, h, ow, oh, int(pitch), int(frame_stride))
+
+
+def warpt_layout(fmt, resize, coverage=False, pitch=0, frame_stride=0):
+    """(bytes of one pair, pitch in effect) of an accumulated residual at model size
+    (vp9hip_warpt_layout): planar (3 or 4, OH, OW) 16-bit elements, resize = (OW, OH)."""
+    d = _warpt_desc("vp9hip_warpt_layout", fmt, "nearest", coverage, resize, (1, 1), 2, 0, pitch, frame_stride)
+    p = ctypes.c_int64()
+    nbytes = lib().vp9hip_warpt_layout(ctypes.byref(d), ctypes.byref(p))
+    _check("vp9hip_warpt_layout", nbytes)
+    return nbytes, p.value
+
+
+def acc_warp_scaled_host(planes_a, planes_b, acc, serial_b, width, height, bpp, ss_h, ss_v, fmt, resize, interp="nearest",
+                         coverage=False, colorspace=2, full_range=False):
+    """One pair of the accumulated residual at model size on the host,
+    vp9hip_acc_warp_scaled_host, the C statement of the definition in include/vp9hip.h
+    ("accumulated residual at model size"): the arguments of acc_warp_host, fmt a key of
+    RESID_FORMATS, resize = (OW, OH) or None for the visible size. Returns a (3, OH, OW) int16 or
+    float16 array, (4, OH, OW) with coverage=True: the last plane the coverage."""
+    fn = "vp9hip_acc_warp_scaled_host"
+    dt = np.uint8 if bpp == 8 else np.uint16
+    width, height = int(width), int(height)
+    d = _warpt_desc(fn, fmt, interp, coverage, resize, (width, height), colorspace, full_range, 0, 0)
+    sane = 1 <= width <= 16384 and 1 <= height <= 16384 and ss_h in (0, 1) and ss_v in (0, 1)
+
+    def prep(planes):
+        out = []
+        for p, a in enumerate(planes):
+            a = np.asarray(a)
+            if a.ndim != 2 or a.dtype != dt:
+                raise ValueError("acc_warp_scaled_host: planes must be 2-D %s arrays" % np.dtype(dt).name)
+            if a.strides[1] != a.itemsize or a.strides[0] < 0:
+                a = np.ascontiguousarray(a)
+            if sane:                                  # what the library refuses it does not read
+                pw, ph = (width, height) if p == 0 else ((width + ss_h) >> ss_h, (height + ss_v) >> ss_v)
+                if a.shape[0] < ph or a.shape[1] < pw:
+                    raise ValueError("acc_warp_scaled_host: plane %d is smaller than %d x %d" % (p, pw, ph))
+            out.append(a)
+        if len(out) != 3:
+            raise ValueError("acc_warp_scaled_host: three planes a frame")
+        return out
+    pa, pb = prep(planes_a), prep(planes_b)
+    acc = np.ascontiguousarray(acc, ACC_CELL)
+    if sane and acc.shape != (2 * ((height + 7) >> 3), 2 * ((width + 7) >> 3)):
+        raise ValueError("acc_warp_scaled_host: acc must be (%d, %d) cells" % (2 * ((height + 7) >> 3), 2 * ((width + 7) >> 3)))
+    ok = 1 <= d.out_width <= 16384 and 1 <= d.out_height <= 16384
+    out = np.full((d.planes, d.out_height, d.out_width) if ok else (d.planes, 1, 1), 0x5a5a, np.int16)
+    ap, als = _plane_ptrs(pa)
+    bp, bls = _plane_ptrs(pb)
+    _check(fn, lib().vp9hip_acc_warp_scaled_host(ctypes.byref(ap), ctypes.byref(als), ctypes.byref(bp), ctypes.byref(bls),
+                                                 acc.ctypes.data, int(serial_b) & 0xffffffff, int(bpp), int(ss_h), int(ss_v),
+                                                 ctypes.byref(d), out.ctypes.data))
+    return out.view(np.float16) if fmt.endswith("f16") else out
+
+
+def _warpt_out(n, d, out):
+    """The destination of an acc_warp_tensors call, as _resid_out's: (flat storage tensor,
+    (N, P, OH, OW) view of it, or None for a descriptor the library refuses)."""
+    import torch
+    dt = torch.float16 if d.format & 1 else torch.int16
+    pitch = ctypes.c_int64()
+    nbytes = lib().vp9hip_warpt_layout(ctypes.byref(d), ctypes.byref(pitch))
+    if nbytes < 0:
+        flat = out.view(-1) if out is not None else torch.empty(1, dtype=dt, device="cuda")
+        return flat, None
+    stride = d.frame_stride or nbytes
+    total = ((max(n, 1) - 1) * stride + nbytes) // 2
+    if out is None:
+        out = torch.empty(total, dtype=dt, device="cuda")
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == dt and out.is_contiguous()
+              and out.numel() >= total):
+        raise ValueError("acc_warp_tensors: out must be a contiguous %s cuda tensor of at least %d elements" % (dt, total))
+    flat = out.view(-1)
+    return flat, flat.as_strided((max(n, 0), d.planes, d.out_height, d.out_width),
+                                 (stride // 2, pitch.value * d.out_height // 2, pitch.value // 2, 1))
+
+
+def warp_scale_launch_dev(a_ptrs, b_ptrs, acc_ptrs, serials, plane_off, pitch, acc_pitch, width, height, bpp, ss_h, ss_v,
+                          fmt, resize, dst_ptr, interp="nearest", coverage=False, colorspace=2, full_range=False,
+                          out_pitch=0, frame_stride=0, stream=None):
+    """k_acc_warp_scale over caller-made device pictures and fields (vp9hip_warp_scale_launch_dev;
+    the bench tool and the crafted-field tests): the pictures and fields as warp_launch_dev takes
+    them, the output as acc_warp_scaled_host describes it, written at dst_ptr."""
+    fn = "vp9hip_warp_scale_launch_dev"
+    d = _warpt_desc(fn, fmt, interp, coverage, resize, (width, height), colorspace, full_range, out_pitch, frame_stride)
+    n = len(a_ptrs)
+    arr = lambda v: (ctypes.c_void_p * max(n, 1))(*v)   # noqa: E731
+    _check(fn, lib().vp9hip_warp_scale_launch_dev(arr(a_ptrs), arr(b_ptrs), arr(acc_ptrs),
+                                                  (ctypes.c_uint32 * max(n, 1))(*[int(x) & 0xffffffff for x in serials]), n,
+                                                  ctypes.byref((ctypes.c_int64 * 3)(*plane_off)),
+                                                  ctypes.byref((ctypes.c_int32 * 2)(*pitch)), int(acc_pitch), int(bpp),
+                                                  int(ss_h), int(ss_v), ctypes.byref(d), dst_ptr, stream))
+
+
 def psnr(metrics, bpp, width, height, ss_h=1, ss_v=1):
     """PSNR in dB of each plane from metrics records (a host array (..., 3, 8), e.g.
     Device.metrics(...).cpu()): float64 (..., 3), 10 log10((2^bpp - 1)^2 count / sse) with count
@@ -1856,6 +1982,43 @@ class Device:
             _check(fn, _enqueue_for_torch(main.value, stream, call))
         return views + (m,) if mask else views
 
+    def acc_warp_tensors(self, bufs, root_bufs, fmt, resize=None, interp="nearest", coverage=False, colorspace=2,
+                         full_range=False, size=None, out=None, stream=None, pitch=0, frame_stride=0):
+        """The accumulated residual of the pairs (bufs[i], root_bufs[i]) as one (N, 3, OH, OW) cuda
+        tensor at the model's size, made on the GPU in one launch per 32 pairs
+        (vp9hip_acc_warp_scaled, the definition in include/vp9hip.h "accumulated residual at model
+        size"): what acc_warp(output="residual") leaves, box-resampled to resize = (OW, OH) and
+        formatted as residual_tensors does (fmt, colorspace, full_range, pitch, frame_stride as
+        there), without the full-size planes in between; resize=None is the visible size through
+        the same kernel. coverage=True adds a fourth plane: how much of each output sample's
+        area lies in applying cells, 0..256 (int16) or 0..1 (float16). `size` = (width, height)
+        is the visible size (default: the configured size). Needs set_export(motion_acc=True).
+        Runs in the order of torch's current stream (or on `stream`) and does not wait, like
+        residual_tensors. Needs torch imported before the library was loaded (see _torch_first)."""
+        fn = "vp9hip_acc_warp_scaled"
+        if not _torch_first:
+            raise Vp9HipUnavailable("acc_warp_tensors: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        bufs, root_bufs = [int(b) for b in bufs], [int(b) for b in root_bufs]
+        n = len(bufs)
+        if len(root_bufs) != n:
+            raise ValueError("acc_warp_tensors: bufs and root_bufs differ in length")
+        d = _warpt_desc(fn, fmt, interp, coverage, resize, size if size is not None else (self.w, self.h), colorspace,
+                        full_range, pitch, frame_stride)
+        if resize is None and not (1 <= d.out_width <= 16384 and 1 <= d.out_height <= 16384):
+            d.out_width = d.out_height = 1           # no size to default to: the library refuses the size itself
+        flat, res = _warpt_out(n, d, out)
+        aa, ab = (ctypes.c_int * max(n, 1))(*bufs), (ctypes.c_int * max(n, 1))(*root_bufs)
+        call = lambda st: lib().vp9hip_acc_warp_scaled(self._c, aa, ab, n, ctypes.byref(d), flat.data_ptr(), st)
+        main = ctypes.c_void_p()
+        # an unconfigured context has no buffer to ask for its stream: the library refuses the call itself
+        if lib().vp9hip_frame_device(self._c, 0, (ctypes.c_void_p * 3)(), (ctypes.c_ssize_t * 3)(), None, None,
+                                     ctypes.byref(main)):
+            _check(fn, call(stream))
+        else:
+            _check(fn, _enqueue_for_torch(main.value, stream, call))
+        return res
+
     def upload(self, buf, planes):
         planes = [np.ascontiguousarray(p) for p in planes]
         ptrs, ls = self._plane_args(planes)
@@ -2187,6 +2350,36 @@ class Decoder:
         _check(fn, _enqueue_for_torch(main.value, None, call))
         torch.cuda.current_stream().synchronize()
         return views + (m,) if mask else views
+
+    def acc_warp_tensors(self, infos, root_infos, fmt, resize=None, interp="nearest", coverage=False, out=None):
+        """The accumulated residual at model size of the pairs (infos[i], root_infos[i]) of frames
+        of receive_frame(download=False) (all of one size, depth and subsampling, all still held;
+        the infos of one colour space and range, which are the ones used; needs
+        export_motion_acc=True), as Device.acc_warp_tensors returns it
+        (vp9hip_decoder_acc_warp_scaled). Runs on torch's current stream and waits for it; like
+        acc_warp it releases nothing."""
+        fn = "vp9hip_decoder_acc_warp_scaled"
+        if not _torch_first:
+            raise Vp9HipUnavailable("acc_warp_tensors: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        import torch
+        infos, root_infos = list(infos), list(root_infos)
+        n = len(infos)
+        if len(root_infos) != n:
+            raise ValueError("acc_warp_tensors: infos and root_infos differ in length")
+        if not n:
+            raise Vp9HipError(fn, EINVAL)
+        f = infos[0]
+        d = _warpt_desc(fn, fmt, interp, coverage, resize, (f.width, f.height), 2, 0, 0, 0)
+        flat, res = _warpt_out(n, d, out)
+        aa, ab = (DecodedFrameInfo * n)(*infos), (DecodedFrameInfo * n)(*root_infos)
+        main = ctypes.c_void_p()
+        _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
+                                                                (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
+        call = lambda st: lib().vp9hip_decoder_acc_warp_scaled(self._d, aa, ab, n, ctypes.byref(d), flat.data_ptr(), st)
+        _check(fn, _enqueue_for_torch(main.value, None, call))
+        torch.cuda.current_stream().synchronize()
+        return res
 
     def flush(self):
         _check("vp9hip_decoder_flush", lib().vp9hip_decoder_flush(self._d))

@@ -1,8 +1,9 @@
 // Device code the four output conversion kernels share (vp9hip_convert.hip, _scale, _resample,
 // _cubic): the stored pixel that include/vp9hip.h defines bit for bit (matrix, clip, the half's
 // two roundings, the per-format stores) and the arithmetic the resize kernels have in common.
-// Included by those four files, and by vp9hip_residual_scale.hip for floordiv, rounded_quot and
-// to_half. Everything is __device__ __forceinline__: no kernels, no __shared__.
+// Included by those four files, and by vp9hip_residual_scale.hip and vp9hip_warp_scale.hip
+// (through vp9hip_resid_dev.h too) for floordiv, rounded_quot and to_half. Everything is
+// __device__ __forceinline__: no kernels, no __shared__.
 #ifndef VP9HIP_CONVERT_DEV_H
 #define VP9HIP_CONVERT_DEV_H
 

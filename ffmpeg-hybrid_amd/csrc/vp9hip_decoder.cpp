@@ -560,6 +560,32 @@ extern "C" int vp9hip_decoder_acc_warp(vp9hip_decoder *d, const vp9hip_decoded_f
     return vp9hip_acc_warp(d->ctx, ba.data(), bb.data(), n, f0.width, f0.height, mode, output, dst_dev, mask_dev, stream);
 }
 
+// The accumulated residual at model size of pairs of received frames (vp9hip_acc_warp_scaled),
+// under vp9hip_decoder_acc_warp's rules; the size is the frames' own, the colour description
+// that of the frames a, which must share it, as vp9hip_decoder_residual_scaled takes it.
+extern "C" int vp9hip_decoder_acc_warp_scaled(vp9hip_decoder *d, const vp9hip_decoded_frame *frames_a,
+                                              const vp9hip_decoded_frame *frames_b, int n, const vp9hip_warpt_desc *desc,
+                                              void *dst_dev, void *stream)
+{
+    if (!d || !frames_a || !frames_b || n <= 0 || !desc || !d->configured) return VP9HIP_EINVAL;
+    std::vector<int> ba(n), bb(n);
+    const vp9hip_decoded_frame &f0 = frames_a[0];
+    for (int s = 0; s < 2; s++)
+        for (int i = 0; i < n; i++) {
+            const vp9hip_decoded_frame &f = s ? frames_b[i] : frames_a[i];
+            if (f.buf < 0 || f.buf >= d->nbufs || d->pins[f.buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+            if (f.width != f0.width || f.height != f0.height || f.bpp != f0.bpp || f.ss_h != f0.ss_h || f.ss_v != f0.ss_v)
+                return VP9HIP_EINVAL;
+            if (!s && (f.colorspace != f0.colorspace || f.full_range != f0.full_range)) return VP9HIP_EINVAL;
+            (s ? bb : ba)[i] = f.buf;
+        }
+    vp9hip_warpt_desc o = *desc;
+    o.width = f0.width; o.height = f0.height;
+    o.colorspace = f0.colorspace == 0 || f0.colorspace == 6 ? 2 : f0.colorspace;   // unknown / reserved: BT.709
+    o.full_range = f0.full_range;
+    return vp9hip_acc_warp_scaled(d->ctx, ba.data(), bb.data(), n, &o, dst_dev, stream);
+}
+
 // avcodec_flush_buffers (vp9.c:1865-1883): drop the decoder delay and the reference
 // state; frames already handed out stay valid until released.
 extern "C" int vp9hip_decoder_flush(vp9hip_decoder *d)

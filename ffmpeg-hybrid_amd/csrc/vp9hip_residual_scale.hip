@@ -26,6 +26,7 @@
 // element, lanes on consecutive pixels, only at ox < out_w, oy < out_h. The row routine is this
 // file's own (the sample's flip is the one thing add_row does not do).
 #include "vp9hip_convert_dev.h"
+#include "vp9hip_resid_dev.h"
 #include "vp9hip_residual_scale.h"
 
 #include <array>
@@ -107,8 +108,6 @@ __device__ __forceinline__ void sbox_row(const uint8_t *const (&P)[NP], int pitc
         for (int k = 0; k < 2; k++) out[p][k] = rounded_quot(acc[p][k], den, rcp) - 32768;
 }
 
-__device__ __forceinline__ int clip_pm(int v, int m) { return min(max(v, -m), m); }
-
 // FMT: VP9HIP_RESID_*: bit 1 the RGB matrix, bit 0 the half output
 template <int FMT>
 __global__ __launch_bounds__(256) void k_residual_scale(const ResidScaleArgs a)
@@ -130,27 +129,7 @@ __global__ __launch_bounds__(256) void k_residual_scale(const ResidScaleArgs a)
     for (int k = 0; k < 2; k++) {
         const int ox = tx0 + lane + 64 * k;
         if (ox >= a.ow) continue;
-        int o0 = Yk[0][k], o1 = UV[0][k], o2 = UV[1][k];
-        if constexpr ((FMT & 2) != 0) {
-            const int y = o0, u = o1, v = o2;
-            if (a.rgb) {                                   // planes G, B, R
-                o0 = clip_pm(v, a.maxv); o1 = clip_pm(y, a.maxv); o2 = clip_pm(u, a.maxv);
-            } else {                                       // no offsets: the pixel's and its prediction's cancel
-                const int yy = a.c[0] * y + a.rnd;
-                o0 = clip_pm((yy + a.c[1] * v) >> a.shift, a.maxv);
-                o1 = clip_pm((yy - a.c[2] * u - a.c[3] * v) >> a.shift, a.maxv);
-                o2 = clip_pm((yy + a.c[4] * u) >> a.shift, a.maxv);
-            }
-        }
-        uint8_t *row = dst + (int64_t) oy * a.pitch;
-        const int64_t pl = a.plane / 2;
-        if constexpr ((FMT & 1) != 0) {                    // half: one float multiply, round to nearest even
-            _Float16 *p = reinterpret_cast<_Float16 *>(row) + ox;
-            p[0] = to_half(o0, a.fscale); p[pl] = to_half(o1, a.fscale); p[2 * pl] = to_half(o2, a.fscale);
-        } else {
-            int16_t *p = reinterpret_cast<int16_t *>(row) + ox;
-            p[0] = (int16_t) o0; p[pl] = (int16_t) o1; p[2 * pl] = (int16_t) o2;
-        }
+        residdev::resid_store_px<FMT>(a, dst, ox, oy, Yk[0][k], UV[0][k], UV[1][k]);   // shared with k_acc_warp_scale
     }
 }
 

@@ -48,6 +48,7 @@
 #include "vp9hip_residual.h"
 #include "vp9hip_metrics.h"
 #include "vp9hip_warp.h"
+#include "vp9hip_warp_scale.h"
 #include "vp9hip_residual_scale.h"
 #include "vp9hip_motion_scale.h"
 #include "vp9hip_residn.h"
@@ -4231,6 +4232,112 @@ extern "C" int vp9hip_warp_launch_dev(const void *const *a_dev, const void *cons
     a.pitch[0] = pitch[0]; a.pitch[1] = pitch[1];
     a.acc_pitch = (int32_t) acc_pitch_cells;
     return warp_launches(a, n, hbd, mode, output, dst_dev, mask_dev, (hipStream_t) stream, [&](int i, int k) {
+        a.a[k] = (const uint8_t *) a_dev[i];
+        a.b[k] = (const uint8_t *) b_dev[i];
+        a.acc[k] = (const uint4 *) acc_dev[i];
+        a.serial[k] = serial_b[i];
+    });
+}
+
+// Accumulated residual at model size (include/vp9hip.h "accumulated residual at model size";
+// k_acc_warp_scale in vp9hip_warp_scale.hip). warpt_args: what d asks for, checked, into the
+// arguments: format, mode, planes, colour, output size, pitch and frame stride, and the
+// geometry of a width x height picture; < 0: refused.
+static int warpt_args(WarpScaleArgs &a, const vp9hip_warpt_desc *d, int bpp, int ss_h, int ss_v)
+{
+    memset(&a, 0, sizeof(a));
+    int64_t pitch = 0;
+    const int64_t bytes = vp9hip_warpt_layout(d, &pitch);
+    if (bytes < 0) return VP9HIP_EINVAL;
+    if (d->mode != VP9HIP_WARP_NEAREST && d->mode != VP9HIP_WARP_BILINEAR) return VP9HIP_EINVAL;
+    if (d->width < 1 || d->width > 16384 || d->height < 1 || d->height > 16384 || (ss_h | ss_v) & ~1) return VP9HIP_EINVAL;
+    if (d->format == VP9HIP_RESID_RGB_I16 || d->format == VP9HIP_RESID_RGB_F16) {
+        if (vp9hip_out_coefs(d->colorspace, d->full_range, bpp, bpp, a.c, &a.shift) < 0) return VP9HIP_EINVAL;
+        a.rgb = d->colorspace == 7;
+        a.rnd = a.shift > 0 ? 1 << (a.shift - 1) : 0;
+    }
+    a.frame_stride = d->frame_stride ? d->frame_stride : bytes;
+    a.pitch = pitch; a.plane = pitch * d->out_height;
+    a.w = d->width; a.h = d->height;
+    a.cw = (a.w + ss_h) >> ss_h; a.ch = (a.h + ss_v) >> ss_v;
+    a.ss_h = ss_h; a.ss_v = ss_v;
+    a.gw = 2 * ((a.w + 7) >> 3); a.gh = 2 * ((a.h + 7) >> 3);
+    a.ow = d->out_width; a.oh = d->out_height;
+    a.cov = d->planes == 4;
+    a.maxv = (1 << bpp) - 1;
+    a.fscale = (float) (1.0 / a.maxv);
+    a.rcp[0] = 1.0 / ((double) a.w * (double) a.h);
+    a.rcp[1] = 1.0 / ((double) a.cw * (double) a.ch);
+    a.rx = 1.0 / a.ow; a.ry = 1.0 / a.oh;
+    return 0;
+}
+
+// The launches of a checked call, WSC_MAX_PAIRS pairs each; rec(i, k) fills pair i's record into
+// slot k of the arguments.
+template <class F>
+static int warpt_launches(WarpScaleArgs &a, int n, int hbd, const vp9hip_warpt_desc *d, void *dst_dev, hipStream_t st, F rec)
+{
+    for (int i0 = 0; i0 < n; i0 += WSC_MAX_PAIRS) {
+        const int k = std::min(n - i0, WSC_MAX_PAIRS);
+        for (int i = 0; i < k; i++) rec(i0 + i, i);
+        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * a.frame_stride;
+        HIPCHK(vp9hip_warp_scale_launch(a, hbd, d->mode, d->format, k, st));
+    }
+    return 0;
+}
+
+// Everything is validated before the first launch, so a refused call writes nothing; the
+// records travel as kernel arguments, like vp9hip_acc_warp's.
+extern "C" int vp9hip_acc_warp_scaled(vp9hip_ctx *c, const int *bufs_a, const int *bufs_b, int n,
+                                      const vp9hip_warpt_desc *d, void *dst_dev, void *stream)
+{
+    if (!c || c->bufs.empty() || c->acc.empty() || !bufs_a || !bufs_b || n <= 0 || !d || !dst_dev || ((uintptr_t) dst_dev & 1))
+        return VP9HIP_EINVAL;
+    WarpScaleArgs a;
+    if (warpt_args(a, d, c->bpp, c->ss_h, c->ss_v) < 0) return VP9HIP_EINVAL;
+    if (d->width > c->w || d->height > c->h) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (bufs_a[i] < 0 || bufs_a[i] >= (int) c->acc.size() || bufs_b[i] < 0 || bufs_b[i] >= (int) c->acc.size())
+            return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!c->mot_gwh[bufs_a[i]].first || !c->mot_gwh[bufs_b[i]].first) return VP9HIP_EAGAIN;
+    for (int i = 0; i < n; i++)
+        if (c->mot_gwh[bufs_a[i]].first != a.gw || c->mot_gwh[bufs_a[i]].second != a.gh) return VP9HIP_EINVAL;
+    for (int p = 0; p < 3; p++) a.off[p] = (int64_t) c->plane_off[p];
+    a.src_pitch[0] = (int32_t) (c->pitch[0] * c->bypp); a.src_pitch[1] = (int32_t) (c->pitch[1] * c->bypp);
+    a.acc_pitch = (int32_t) c->mot_pitch;
+    hipSetDevice(c->dev);
+    return warpt_launches(a, n, c->hb, d, dst_dev, stream ? (hipStream_t) stream : c->st, [&](int i, int k) {
+        a.a[k] = c->bufs[bufs_a[i]];
+        a.b[k] = c->bufs[bufs_b[i]];
+        a.acc[k] = (const uint4 *) c->acc[bufs_a[i]];
+        a.serial[k] = c->acc_serial[bufs_b[i]];
+    });
+}
+
+extern "C" int vp9hip_warp_scale_launch_dev(const void *const *a_dev, const void *const *b_dev, const void *const *acc_dev,
+                                            const uint32_t *serial_b, int n, const int64_t plane_off[3], const int32_t pitch[2],
+                                            int64_t acc_pitch_cells, int bpp, int ss_h, int ss_v,
+                                            const vp9hip_warpt_desc *d, void *dst_dev, void *stream)
+{
+    if (!a_dev || !b_dev || !acc_dev || !serial_b || n <= 0 || !plane_off || !pitch || !d || !dst_dev || ((uintptr_t) dst_dev & 1))
+        return VP9HIP_EINVAL;
+    if (bpp != 8 && bpp != 10 && bpp != 12) return VP9HIP_EINVAL;
+    WarpScaleArgs a;
+    if (warpt_args(a, d, bpp, ss_h, ss_v) < 0) return VP9HIP_EINVAL;
+    const int hbd = bpp > 8, bypp = hbd ? 2 : 1;
+    if (pitch[0] < a.w * bypp || pitch[1] < a.cw * bypp || (hbd && ((pitch[0] | pitch[1]) & 1))) return VP9HIP_EINVAL;
+    if (acc_pitch_cells < a.gw || acc_pitch_cells > INT32_MAX) return VP9HIP_EINVAL;
+    for (int p = 0; p < 3; p++)
+        if (plane_off[p] < 0 || (hbd && (plane_off[p] & 1))) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!a_dev[i] || !b_dev[i] || !acc_dev[i] || ((uintptr_t) acc_dev[i] & 15) ||
+            (hbd && (((uintptr_t) a_dev[i] | (uintptr_t) b_dev[i]) & 1)))
+            return VP9HIP_EINVAL;
+    for (int p = 0; p < 3; p++) a.off[p] = plane_off[p];
+    a.src_pitch[0] = pitch[0]; a.src_pitch[1] = pitch[1];
+    a.acc_pitch = (int32_t) acc_pitch_cells;
+    return warpt_launches(a, n, hbd, d, dst_dev, (hipStream_t) stream, [&](int i, int k) {
         a.a[k] = (const uint8_t *) a_dev[i];
         a.b[k] = (const uint8_t *) b_dev[i];
         a.acc[k] = (const uint4 *) acc_dev[i];

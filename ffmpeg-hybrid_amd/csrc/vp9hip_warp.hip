@@ -28,37 +28,11 @@
 // their size, else the run goes sample by sample, so odd widths, tight odd-sized outputs and
 // unaligned test planes are served by the same kernel.
 #include "vp9hip_warp.h"
+#include "vp9hip_warp_dev.h"
 
 namespace {
 
-__device__ __forceinline__ int cl(const int v, const int n)
-{
-    return v < 0 ? 0 : v > n - 1 ? n - 1 : v;
-}
-
-template <typename T> __device__ __forceinline__ uint32_t ld(const uint8_t *row, const int x)
-{
-    return ((const T *) row)[x];
-}
-
-// NS consecutive samples from byte address p, which need not be aligned: one load of the next
-// power of two of bytes (the caller has checked that all of them lie inside the visible row)
-template <typename T, int NS> __device__ __forceinline__ void ld_span(const uint8_t *p, uint32_t (&v)[NS])
-{
-    constexpr int NB = NS * (int) sizeof(T), W = NB <= 2 ? 2 : NB <= 4 ? 4 : NB <= 8 ? 8 : 16;
-    uint32_t w[4] = { 0, 0, 0, 0 };
-    __builtin_memcpy(w, p, W);
-#pragma unroll
-    for (int i = 0; i < NS; i++) {
-        constexpr int SPD = 4 / (int) sizeof(T);
-        v[i] = (w[i / SPD] >> (8 * sizeof(T) * (i % SPD))) & (sizeof(T) == 1 ? 0xffu : 0xffffu);
-    }
-}
-// the bytes ld_span<T, NS> reads
-template <typename T, int NS> __device__ __forceinline__ constexpr int span_bytes()
-{
-    return NS * (int) sizeof(T) <= 2 ? 2 : NS * (int) sizeof(T) <= 4 ? 4 : NS * (int) sizeof(T) <= 8 ? 8 : 16;
-}
+using namespace warpdev;                // cl, ld_run, warp_pred: shared with k_acc_warp_scale
 
 // One run of RUN samples of a plane from (x0, y): pa / pb the plane in a and b, PW x PH its
 // visible size, (px, py) the cell's vector in 1/16 sample of the plane, drow the output row.
@@ -73,59 +47,9 @@ __device__ __forceinline__ void warp_run(const uint8_t *const pa, const uint8_t 
 #pragma unroll
     for (int i = 0; i < RUN; i++) av[i] = pv[i] = 0;
     if (OUT == VP9HIP_WARP_PICTURE || app) {
-        const uint8_t *const ra = pa + (size_t) y * pitch;
-        const uint8_t *const at = ra + (size_t) x0 * sizeof(T);
-        if (nv == RUN && !((uintptr_t) at & (RUN * sizeof(T) - 1))) {
-            uint32_t wv[2] = { 0, 0 };
-            if (RUN * sizeof(T) == 8) { const uint2 v = *(const uint2 *) at; wv[0] = v.x; wv[1] = v.y; }
-            else if (RUN * sizeof(T) == 4) wv[0] = *(const uint32_t *) at;
-            else wv[0] = *(const uint16_t *) at;
-#pragma unroll
-            for (int i = 0; i < RUN; i++) {
-                constexpr int SPD = 4 / (int) sizeof(T);
-                av[i] = (wv[i / SPD] >> (8 * sizeof(T) * (i % SPD))) & (sizeof(T) == 1 ? 0xffu : 0xffffu);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < RUN; i++)
-                if (i < nv) av[i] = ld<T>(ra, x0 + i);
-        }
+        ld_run<T, RUN>(pa + (size_t) y * pitch, x0, nv, av);
     }
-    if (app) {
-        if (MODE == VP9HIP_WARP_NEAREST) {
-            const uint8_t *const rb = pb + (size_t) cl(y + ((py + 8) >> 4), PH) * pitch;
-            const int xs = x0 + ((px + 8) >> 4);
-            if (xs >= 0 && xs * (int) sizeof(T) + span_bytes<T, RUN>() <= PW * (int) sizeof(T)) {
-                ld_span<T, RUN>(rb + (size_t) xs * sizeof(T), pv);           // no column clamps: the run is contiguous
-            } else {
-#pragma unroll
-                for (int i = 0; i < RUN; i++) pv[i] = ld<T>(rb, cl(xs + i, PW));
-            }
-        } else {
-            const int ys = y + (py >> 4), xs = x0 + (px >> 4);
-            const uint32_t fx = (uint32_t) px & 15, fy = (uint32_t) py & 15;
-            const uint8_t *const r0 = pb + (size_t) cl(ys, PH) * pitch, *const r1 = pb + (size_t) cl(ys + 1, PH) * pitch;
-            // the run's RUN + 1 columns of both rows, blended down the column first
-            uint32_t t[RUN + 1], u[RUN + 1];
-            if (xs >= 0 && xs * (int) sizeof(T) + span_bytes<T, RUN + 1>() <= PW * (int) sizeof(T)) {
-                ld_span<T, RUN + 1>(r0 + (size_t) xs * sizeof(T), t);        // no column clamps: one span a row
-                ld_span<T, RUN + 1>(r1 + (size_t) xs * sizeof(T), u);
-            } else {
-#pragma unroll
-                for (int i = 0; i <= RUN; i++) {
-                    const int xx = cl(xs + i, PW);
-                    t[i] = ld<T>(r0, xx);
-                    u[i] = ld<T>(r1, xx);
-                }
-            }
-            // (16 - fx)(16 - fy) s00 + fx (16 - fy) s01 + (16 - fx) fy s10 + fx fy s11, regrouped by
-            // column: exact in integers, at most 256 * 65535 + 128 < 2^32
-#pragma unroll
-            for (int i = 0; i <= RUN; i++) t[i] = (16 - fy) * t[i] + fy * u[i];
-#pragma unroll
-            for (int i = 0; i < RUN; i++) pv[i] = ((16 - fx) * t[i] + fx * t[i + 1] + 128) >> 8;
-        }
-    }
+    if (app) warp_pred<T, RUN, MODE>(pb, pitch, PW, PH, x0, y, px, py, pv);
     uint32_t o[RUN];
 #pragma unroll
     for (int i = 0; i < RUN; i++) {

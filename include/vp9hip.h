@@ -57,7 +57,10 @@ extern "C" {
  * (VP9HIP_MVT_*, vp9hip_mvt_desc, vp9hip_mvt_layout, vp9hip_motion_frames_scaled,
  * vp9hip_motion_scaled_host, vp9hip_decoder_motion_scaled) likewise. The accumulated residual
  * (VP9HIP_WARP_*, vp9hip_warp_layout, vp9hip_acc_warp, vp9hip_acc_warp_host,
- * vp9hip_warp_launch_dev, vp9hip_decoder_acc_warp) likewise: new enums and new symbols. */
+ * vp9hip_warp_launch_dev, vp9hip_decoder_acc_warp) likewise: new enums and new symbols. The
+ * accumulated residual at model size (vp9hip_warpt_desc, vp9hip_warpt_layout,
+ * vp9hip_acc_warp_scaled, vp9hip_acc_warp_scaled_host, vp9hip_warp_scale_launch_dev,
+ * vp9hip_decoder_acc_warp_scaled) likewise: a new struct and new symbols. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -945,8 +948,7 @@ int  vp9hip_frame_metrics_host(const void *const a[3], const ptrdiff_t linesize_
  *   8. The optional mask is uint8_t, tight (n, GH, GW): 1 where the cell applies, else 0.
  * The destination is tight per pair, 2-byte elements: Y (PH x PW of luma), then U, then V;
  * vp9hip_warp_layout gives the three offsets and the pair stride.
- * Not offered: the result at model size, sub-pel filters other than bilinear, the second
- * reference, a per-hop warp. */
+ * Not offered: sub-pel filters other than bilinear, the second reference, a per-hop warp. */
 enum { VP9HIP_WARP_NEAREST, VP9HIP_WARP_BILINEAR };
 enum { VP9HIP_WARP_RESIDUAL, VP9HIP_WARP_PICTURE };
 /* Bytes of one pair's output (the stride between pairs) and, if off is not NULL, the byte
@@ -989,6 +991,78 @@ int  vp9hip_warp_launch_dev(const void *const *a_dev, const void *const *b_dev, 
                             const uint32_t *serial_b, int n, const int64_t plane_off[3], const int32_t pitch[2],
                             int64_t acc_pitch_cells, int width, int height, int bpp, int ss_h, int ss_v,
                             int mode, int output, void *dst_dev, uint8_t *mask_dev, void *stream);
+
+/* ---- accumulated residual at model size: warp, signed box resize and the RGB matrix, fused ----
+ * The accumulated residual as an (N, 3 or 4, OH, OW) tensor at the model's size, in one launch
+ * per 32 pairs (k_acc_warp_scale): the composition of the two sections it names, without the
+ * full-size planes between them. On demand, under the contract of vp9hip_acc_warp: nothing in the
+ * decode path changes, and without the call nothing is launched or allocated.
+ *
+ * Definition, in integers. For a pair (a, b) of visible size w x h and mode VP9HIP_WARP_NEAREST /
+ * VP9HIP_WARP_BILINEAR:
+ *   1. R_Y, R_U, R_V are the VP9HIP_WARP_RESIDUAL planes of "accumulated residual", steps 1-6:
+ *      int16 after the clamp, 0 where the cell does not apply.
+ *   2. The output is "residual tensors at model size" applied to (R_Y, R_U, R_V) as a field of
+ *      visible size w x h: all three planes through sbox(., OW, OH) with the same weights, the
+ *      same floor and the same bounds (R is any int16, so the bounds hold as stated there), then
+ *      one of the four formats VP9HIP_RESID_YUV_I16 / YUV_F16 / RGB_I16 / RGB_F16 with the same
+ *      matrix without offsets, the same clip to [-m, m], m = 2^bpp - 1, the same colorspace 7
+ *      rule and the same half rounding.
+ *   3. The optional fourth plane is the coverage: C = sbox(256 applies(x >> 2, y >> 2), OW, OH)
+ *      over the w x h luma samples (x, y), applies being step 2 of "accumulated residual"
+ *      (hops > 0 && root == S_b): the integer 0..256 in the I16 formats,
+ *      half(float(C) * (1.0f / 256)) in the F16 formats, as VP9HIP_MVT_F16's coverage. It is not
+ *      the coverage of vp9hip_motion_frames_scaled over VP9HIP_MVT_ACC, which knows nothing of
+ *      the root match.
+ *   4. Layout: planar (n, P, OH, OW) 16-bit elements, P = 3 or 4; plane p of pair i starts at
+ *      dst + i frame_stride + p pitch OH. Pitch and frame stride follow the rules of
+ *      vp9hip_resid_desc with P in place of 3.
+ * Not offered: the picture output at model size (an unsigned picture with offsets is the scaled
+ * conversion's ground), other filters, rectangles. */
+typedef struct vp9hip_warpt_desc {
+    int32_t format;                 /* VP9HIP_RESID_* */
+    int32_t colorspace, full_range; /* as vp9hip_resid_desc */
+    int32_t mode;                   /* VP9HIP_WARP_NEAREST / VP9HIP_WARP_BILINEAR */
+    int32_t planes;                 /* 3, or 4 with the coverage */
+    int32_t width, height;          /* the visible size; vp9hip_decoder_acc_warp_scaled sets it from the frames */
+    int32_t out_width, out_height;  /* 1..16384 */
+    int64_t pitch;                  /* bytes per output row, 0 = tight (2 OW); else a multiple of 16, >= 2 OW */
+    int64_t frame_stride;           /* bytes between pairs, 0 = tight (P pitch OH); else even, >= P pitch OH */
+} vp9hip_warpt_desc;
+/* Bytes of one pair of d (P pitch OH) and the pitch in effect, or VP9HIP_EINVAL for a format
+ * outside the enum, planes not 3 / 4, an output size outside 1..16384 or a pitch / frame stride
+ * the comments above exclude. Host only; mode, size and the colour fields are not looked at. */
+int64_t vp9hip_warpt_layout(const vp9hip_warpt_desc *d, int64_t *pitch);
+/* The pairs (bufs_a[i], bufs_b[i]), i < n, into dst_dev under the contract of vp9hip_acc_warp:
+ * any buffers in any order, repeats and a == b allowed; n above 32 is split into launches of at
+ * most 32 pairs; it enqueues on `stream` (NULL: the current slot's main stream) and returns
+ * without waiting, orders nothing itself, does not allocate and reads no device memory on the
+ * host, so it can sit in a captured stream; only the OW x OH elements of each plane are written;
+ * everything is checked before the first launch: a refused call writes nothing. VP9HIP_EINVAL:
+ * what vp9hip_acc_warp refuses (with d->width, d->height as the size), what
+ * vp9hip_residual_frames_scaled refuses of format, colour, output size, dst_dev (NULL or odd),
+ * pitch and frame stride, a NULL d, planes not 3 / 4, an unknown mode. VP9HIP_EAGAIN: an a or a b
+ * without a field (checked after the indices, before the grid). */
+int  vp9hip_acc_warp_scaled(vp9hip_ctx *ctx, const int *bufs_a, const int *bufs_b, int n,
+                            const vp9hip_warpt_desc *d, void *dst_dev, void *stream);
+/* Host only, no device: the C statement of the definition above for one pair of host frames
+ * (linesize in bytes) and a's field as a tight array acc[GH][GW], one output sample at a time in
+ * 64-bit integers; the size is d->width x d->height; dst is the pair's output in host memory,
+ * laid out by d (frame_stride is checked, not used). It reads only visible samples.
+ * VP9HIP_EINVAL: what vp9hip_acc_warp_host and vp9hip_residual_scaled_host refuse, planes not
+ * 3 / 4; a refused call writes nothing. */
+int  vp9hip_acc_warp_scaled_host(const void *const a[3], const ptrdiff_t linesize_a[3],
+                                 const void *const b[3], const ptrdiff_t linesize_b[3],
+                                 const vp9hip_acc_cell *acc, uint32_t serial_b, int bpp, int ss_h, int ss_v,
+                                 const vp9hip_warpt_desc *d, void *dst);
+/* Diagnostics (tools/acc_warp_scale_bench.py, the crafted-field tests): k_acc_warp_scale over
+ * caller-made pictures and fields in device memory, as vp9hip_warp_launch_dev describes them,
+ * with the size from d. VP9HIP_EINVAL: what vp9hip_warp_launch_dev refuses of its arguments and
+ * what vp9hip_acc_warp_scaled refuses of d and dst_dev. */
+int  vp9hip_warp_scale_launch_dev(const void *const *a_dev, const void *const *b_dev, const void *const *acc_dev,
+                                  const uint32_t *serial_b, int n, const int64_t plane_off[3], const int32_t pitch[2],
+                                  int64_t acc_pitch_cells, int bpp, int ss_h, int ss_v,
+                                  const vp9hip_warpt_desc *d, void *dst_dev, void *stream);
 
 /* Upload host planes into device buffer `buf` (test hook for reference frames). */
 int  vp9hip_upload_frame(vp9hip_ctx *ctx, int buf, const uint8_t *const planes[3],
@@ -1417,6 +1491,16 @@ int  vp9hip_decoder_metrics(vp9hip_decoder *d, const vp9hip_decoded_frame *frame
 int  vp9hip_decoder_acc_warp(vp9hip_decoder *d, const vp9hip_decoded_frame *frames_a,
                              const vp9hip_decoded_frame *frames_b, int n, int mode, int output,
                              void *dst_dev, uint8_t *mask_dev, void *stream);
+/* The accumulated residual at model size of the pairs (frames_a[i], frames_b[i]) of received
+ * frames through vp9hip_acc_warp_scaled, under the rules of vp9hip_decoder_acc_warp: every frame
+ * of both arrays must be of one size, depth and subsampling and held by the caller; desc's width
+ * and height are not read but taken from the frames; a show_existing_frame output uses the shown
+ * buffer's field and serial. The colour space and range are those of the frames_a, which must
+ * share them, as vp9hip_decoder_residual_scaled with colorspace < 0 (unknown: BT.709); desc's
+ * own are not read. It only enqueues and releases nothing. Needs VP9HIP_EXPORT_MOTION_ACC. */
+int  vp9hip_decoder_acc_warp_scaled(vp9hip_decoder *d, const vp9hip_decoded_frame *frames_a,
+                                    const vp9hip_decoded_frame *frames_b, int n,
+                                    const vp9hip_warpt_desc *desc, void *dst_dev, void *stream);
 /* avcodec_flush_buffers: drop queued frames and reference state (seek). */
 int  vp9hip_decoder_flush(vp9hip_decoder *d);
 
