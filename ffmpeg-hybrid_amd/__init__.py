@@ -165,7 +165,9 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9hip_warp_layout", "vp9hip_acc_warp", "vp9hip_acc_warp_host", "vp9hip_warp_launch_dev",
                "vp9hip_decoder_acc_warp",
                "vp9hip_warpt_layout", "vp9hip_acc_warp_scaled", "vp9hip_acc_warp_scaled_host",
-               "vp9hip_warp_scale_launch_dev", "vp9hip_decoder_acc_warp_scaled"]
+               "vp9hip_warp_scale_launch_dev", "vp9hip_decoder_acc_warp_scaled",
+               "vp9hip_prop_layout", "vp9hip_acc_propagate", "vp9hip_acc_propagate_host", "vp9hip_prop_launch_dev",
+               "vp9hip_decoder_acc_propagate"]
 
 
 def lib():
@@ -399,6 +401,16 @@ def lib():
                                               [ctypes.POINTER(WarptDesc), ctypes.c_void_p, ctypes.c_void_p]
     L.vp9hip_decoder_acc_warp_scaled.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(DecodedFrameInfo),
                                                  ctypes.c_int, ctypes.POINTER(WarptDesc), ctypes.c_void_p, ctypes.c_void_p]
+    # accumulated propagation
+    L.vp9hip_prop_layout.restype = ctypes.c_int64
+    L.vp9hip_prop_layout.argtypes = [ctypes.POINTER(PropDesc), ctypes.POINTER(ctypes.c_int64)]
+    L.vp9hip_acc_propagate.argtypes = [vp, ctypes.POINTER(ctypes.c_int), u32p, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                       ctypes.c_int, ctypes.POINTER(PropDesc)] + [ctypes.c_void_p] * 4
+    L.vp9hip_acc_propagate_host.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(PropDesc)] + [ctypes.c_void_p] * 3
+    L.vp9hip_prop_launch_dev.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64, u32p, ctypes.POINTER(ctypes.c_int),
+                                         ctypes.c_int, ctypes.c_int, ctypes.POINTER(PropDesc)] + [ctypes.c_void_p] * 4
+    L.vp9hip_decoder_acc_propagate.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), u32p, ctypes.POINTER(ctypes.c_int),
+                                               ctypes.c_int, ctypes.c_int, ctypes.POINTER(PropDesc)] + [ctypes.c_void_p] * 4
     _lib_handle = L
     return L
 
@@ -453,6 +465,13 @@ class WarptDesc(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("planes", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32), ("pitch", ctypes.c_int64),
                 ("frame_stride", ctypes.c_int64)]
+
+
+class PropDesc(ctypes.Structure):
+    """vp9hip_prop_desc: the sizes, element, layout, mode and fill of an accumulated propagation."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("fw", ctypes.c_int32), ("fh", ctypes.c_int32),
+                ("channels", ctypes.c_int32), ("elem_size", ctypes.c_int32), ("layout", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32), ("fill", ctypes.c_uint64)]
 
 
 class MvtDesc(ctypes.Structure):
@@ -1237,6 +1256,127 @@ def acc_warp_host(planes_a, planes_b, acc, serial_b, width, height, bpp, ss_h=1,
     return (y, u, v, m) if mask else (y, u, v)
 
 
+# VP9HIP_PROP_*: the names acc_propagate takes for layout, and its flag
+PROP_LAYOUTS = {"nchw": 0, "nhwc": 1}
+PROP_KEEP = 1
+
+
+def _prop_names(fn, interp, layout):
+    if interp not in WARP_MODES or layout not in PROP_LAYOUTS:
+        raise Vp9HipError(fn, EINVAL)
+    return WARP_MODES[interp], PROP_LAYOUTS[layout]
+
+
+def _prop_dims(what, shape, layout):
+    """(C, FH, FW, squeezed) of one item's shape: (C, FH, FW), (FH, FW, C) with layout "nhwc", or
+    (FH, FW), which is C = 1."""
+    if len(shape) == 2:
+        return 1, int(shape[0]), int(shape[1]), True
+    if len(shape) != 3:
+        raise ValueError("%s: an item is (C, FH, FW), (FH, FW, C) with layout=\"nhwc\", or (FH, FW)" % what)
+    if layout == "nhwc":
+        return int(shape[2]), int(shape[0]), int(shape[1]), False
+    return int(shape[0]), int(shape[1]), int(shape[2]), False
+
+
+def _prop_desc(fn, size, c, fh, fw, esize, interp, layout, fill_bits, keep):
+    """The PropDesc of a call; interp and layout are names."""
+    mode, lay = _prop_names(fn, interp, layout)
+    w, h = (int(x) for x in size)
+    return PropDesc(w, h, fw, fh, c, esize, lay, mode, PROP_KEEP if keep else 0, 0, int(fill_bits) & 0xffffffffffffffff)
+
+
+def prop_layout(desc):
+    """(bytes of one item, bytes of one item's valid map) of a PropDesc (vp9hip_prop_layout)."""
+    vb = ctypes.c_int64()
+    item = lib().vp9hip_prop_layout(ctypes.byref(desc), ctypes.byref(vb))
+    _check("vp9hip_prop_layout", item)
+    return item, vb.value
+
+
+def acc_propagate_host(acc, root_serial, src, width, height, interp="nearest", layout="nchw", fill=0, keep=False,
+                       valid=False, out=None):
+    """One pair of the accumulated propagation on the host, vp9hip_acc_propagate_host, the C
+    statement of the definition in include/vp9hip.h ("accumulated propagation"): acc the frame's
+    ACC_CELL array (GH, GW), root_serial the root's serial, src one source item, a numpy array
+    (C, FH, FW), (FH, FW, C) with layout "nhwc", or (FH, FW), of 1, 2, 4 or 8-byte elements
+    (float16 for interp "bilinear"). fill is a number converted to src's dtype; keep=True leaves
+    `out` (an array like src, required then) where the cell does not apply. Returns the item, of
+    src's dtype and shape, or (item, valid) with valid=True: uint8 (FH, FW)."""
+    fn = "vp9hip_acc_propagate_host"
+    src = np.ascontiguousarray(src)
+    c, fh, fw, _ = _prop_dims("acc_propagate_host", src.shape, layout)
+    if src.dtype.itemsize not in (1, 2, 4, 8):
+        raise ValueError("acc_propagate_host: elements of 1, 2, 4 or 8 bytes")
+    if interp == "bilinear" and src.dtype != np.float16:
+        raise ValueError("acc_propagate_host: interp=\"bilinear\" needs float16")
+    bits = int.from_bytes(np.array([fill]).astype(src.dtype).tobytes(), "little")
+    d = _prop_desc(fn, (width, height), c, fh, fw, src.dtype.itemsize, interp, layout, bits, keep)
+    gw, gh = 2 * ((int(width) + 7) >> 3), 2 * ((int(height) + 7) >> 3)
+    acc = np.ascontiguousarray(acc, ACC_CELL)
+    if acc.shape != (gh, gw):
+        raise ValueError("acc_propagate_host: acc must be (%d, %d) cells" % (gh, gw))
+    if keep and out is None:
+        raise ValueError("acc_propagate_host: keep=True needs out=")
+    if out is None:
+        out = np.full(src.nbytes, 0x5a, np.uint8).view(src.dtype).reshape(src.shape)
+    elif not (isinstance(out, np.ndarray) and out.dtype == src.dtype and out.shape == src.shape and out.flags.c_contiguous):
+        raise ValueError("acc_propagate_host: out must be a contiguous array of src's dtype and shape")
+    m = np.full((fh, fw), 0x5a, np.uint8) if valid else None
+    _check(fn, lib().vp9hip_acc_propagate_host(acc.ctypes.data, int(root_serial) & 0xffffffff, ctypes.byref(d),
+                                               src.ctypes.data, out.ctypes.data, m.ctypes.data if valid else None))
+    return (out, m) if valid else out
+
+
+def prop_launch_dev(acc_ptrs, acc_pitch, serials, src_index, m, desc, src_ptr, dst_ptr, valid_ptr=None, stream=None):
+    """The propagation kernels over caller-made device fields (vp9hip_prop_launch_dev; the bench
+    tool and the crafted-field tests): per pair the device pointer of the frame's field and the
+    root's serial; acc_pitch the fields' pitch in cells, src_index the pairs' source items (None:
+    pair i reads item i) of the m items at src_ptr, desc a PropDesc."""
+    n = len(acc_ptrs)
+    idx = (ctypes.c_int * max(n, 1))(*[int(x) for x in src_index]) if src_index is not None else None
+    _check("vp9hip_prop_launch_dev",
+           lib().vp9hip_prop_launch_dev((ctypes.c_void_p * max(n, 1))(*acc_ptrs), int(acc_pitch),
+                                        (ctypes.c_uint32 * max(n, 1))(*[int(x) & 0xffffffff for x in serials]), idx, n, int(m),
+                                        ctypes.byref(desc), src_ptr, dst_ptr, valid_ptr, stream))
+
+
+def _prop_torch(what, n, src, size, interp, layout, fill, keep, valid, src_index, out, fn):
+    """The checked arguments of an acc_propagate call over torch tensors: (PropDesc, M, src_index
+    array or None, destination, uint8 (N, FH, FW) valid map or None)."""
+    import torch
+    esize = {torch.uint8: 1, torch.int8: 1, torch.int16: 2, torch.float16: 2, torch.bfloat16: 2, torch.int32: 4,
+             torch.float32: 4, torch.int64: 8, torch.float64: 8}
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.is_contiguous() and src.dtype in esize and src.dim() in (3, 4)):
+        raise ValueError("%s: src must be a contiguous cuda tensor (M, C, FH, FW), (M, FH, FW, C) or (M, FH, FW) of an "
+                         "integer or floating type of 1, 2, 4 or 8 bytes" % what)
+    if interp == "bilinear" and src.dtype != torch.float16:
+        raise ValueError("%s: interp=\"bilinear\" needs float16" % what)
+    if keep and out is None:
+        raise ValueError("%s: keep=True needs out=" % what)
+    m = int(src.shape[0])
+    c, fh, fw, _ = _prop_dims(what, tuple(src.shape[1:]), layout)
+    if src_index is None:
+        if m != n and m != 1:
+            raise ValueError("%s: src_index=None needs as many source items as pairs, or one" % what)
+        idx = None if m == n else (ctypes.c_int * max(n, 1))()
+    else:
+        src_index = [int(x) for x in src_index]
+        if len(src_index) != n:
+            raise ValueError("%s: src_index and the pairs differ in length" % what)
+        idx = (ctypes.c_int * max(n, 1))(*src_index)
+    bits = int.from_bytes(bytes(torch.tensor([fill]).to(src.dtype).view(torch.uint8).tolist()), "little")
+    d = _prop_desc(fn, size, c, fh, fw, esize[src.dtype], interp, layout, bits, keep)
+    shape = (n,) + tuple(src.shape[1:])
+    if out is None:
+        out = torch.empty((max(n, 1),) + shape[1:], dtype=src.dtype, device=src.device)[:n]
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == src.dtype and tuple(out.shape) == shape
+              and out.is_contiguous()):
+        raise ValueError("%s: out must be a contiguous cuda tensor of src's dtype and shape %s" % (what, shape))
+    v = torch.empty((max(n, 1), fh, fw), dtype=torch.uint8, device=src.device)[:n] if valid else None
+    return d, m, idx, out, v
+
+
 def _warp_out(n, width, height, ss_h, ss_v, mask, out):
     """The destinations of an acc_warp call: (flat int16 cuda tensor, (y, u, v) views of it,
     uint8 (N, GH, GW) mask or None). `out` is a contiguous int16 cuda tensor of at least
@@ -1982,6 +2122,47 @@ class Device:
             _check(fn, _enqueue_for_torch(main.value, stream, call))
         return views + (m,) if mask else views
 
+    def acc_propagate(self, bufs, root_serials, src, interp="nearest", layout="nchw", fill=0, keep=False, valid=False,
+                      src_index=None, size=None, out=None, stream=None):
+        """A tensor of the root frame carried to the frames in bufs through their accumulated
+        motion, on the GPU (vp9hip_acc_propagate, the definition in include/vp9hip.h "accumulated
+        propagation"): item i of the result is source item src_index[i] displaced by bufs[i]'s
+        accumulated field wherever a cell's chain ended in the frame of serial root_serials[i]
+        (frame_motion_acc / download_motion_acc report a frame's serial; the root's pixels need
+        not exist any more). src is a contiguous cuda tensor (M, C, FH, FW), (M, FH, FW, C) with
+        layout "nhwc", or (M, FH, FW) (C = 1), on any feature grid FW x FH that covers the
+        picture; uint8 / int8, int16 / float16 / bfloat16, int32 / float32 or int64 / float64.
+        interp "nearest" copies elements bit for bit (label maps); "bilinear" needs float16.
+        Elsewhere an element is `fill` (converted to src's dtype), or with keep=True what `out`
+        held (keep needs out=). src_index=None reads item i when M == N and item 0 when M == 1.
+        Returns the tensor, of src's dtype and layout with N items, or (tensor, valid) with
+        valid=True: uint8 (N, FH, FW), 1 where the sample's cell applies. `size` = (width,
+        height) is the visible size (default: the configured size). Needs
+        set_export(motion_acc=True). Runs in the order of torch's current stream (or on `stream`,
+        a hipStream_t handle; see _enqueue_for_torch) and does not wait, like acc_warp. Needs
+        torch imported before the library was loaded (see _torch_first)."""
+        fn = "vp9hip_acc_propagate"
+        if not _torch_first:
+            raise Vp9HipUnavailable("acc_propagate: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        bufs, root_serials = [int(b) for b in bufs], [int(x) & 0xffffffff for x in root_serials]
+        n = len(bufs)
+        if len(root_serials) != n:
+            raise ValueError("acc_propagate: bufs and root_serials differ in length")
+        d, m, idx, res, v = _prop_torch("acc_propagate", n, src, size if size is not None else (self.w, self.h), interp, layout,
+                                        fill, keep, valid, src_index, out, fn)
+        aa, ser = (ctypes.c_int * max(n, 1))(*bufs), (ctypes.c_uint32 * max(n, 1))(*root_serials)
+        call = lambda st: lib().vp9hip_acc_propagate(self._c, aa, ser, idx, n, m, ctypes.byref(d), src.data_ptr(),
+                                                     res.data_ptr(), v.data_ptr() if valid else None, st)
+        main = ctypes.c_void_p()
+        # an unconfigured context has no buffer to ask for its stream: the library refuses the call itself
+        if lib().vp9hip_frame_device(self._c, 0, (ctypes.c_void_p * 3)(), (ctypes.c_ssize_t * 3)(), None, None,
+                                     ctypes.byref(main)):
+            _check(fn, call(stream))
+        else:
+            _check(fn, _enqueue_for_torch(main.value, stream, call))
+        return (res, v) if valid else res
+
     def acc_warp_tensors(self, bufs, root_bufs, fmt, resize=None, interp="nearest", coverage=False, colorspace=2,
                          full_range=False, size=None, out=None, stream=None, pitch=0, frame_stride=0):
         """The accumulated residual of the pairs (bufs[i], root_bufs[i]) as one (N, 3, OH, OW) cuda
@@ -2350,6 +2531,37 @@ class Decoder:
         _check(fn, _enqueue_for_torch(main.value, None, call))
         torch.cuda.current_stream().synchronize()
         return views + (m,) if mask else views
+
+    def acc_propagate(self, infos, root_serials, src, interp="nearest", layout="nchw", fill=0, keep=False, valid=False,
+                      src_index=None, out=None):
+        """A tensor of the root frame carried to the frames infos of receive_frame(download=False)
+        (all of one size, all still held; needs export_motion_acc=True), as Device.acc_propagate
+        returns it (vp9hip_decoder_acc_propagate): take the key frame's serial from
+        motion_acc(info)[1], run the model on it, release it, and pass the serial as every root.
+        Runs on torch's current stream and waits for it; like acc_warp it releases nothing."""
+        fn = "vp9hip_decoder_acc_propagate"
+        if not _torch_first:
+            raise Vp9HipUnavailable("acc_propagate: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        import torch
+        infos, root_serials = list(infos), [int(x) & 0xffffffff for x in root_serials]
+        n = len(infos)
+        if len(root_serials) != n:
+            raise ValueError("acc_propagate: infos and root_serials differ in length")
+        if not n:
+            raise Vp9HipError(fn, EINVAL)
+        f = infos[0]
+        d, m, idx, res, v = _prop_torch("acc_propagate", n, src, (f.width, f.height), interp, layout, fill, keep, valid,
+                                        src_index, out, fn)
+        aa, ser = (DecodedFrameInfo * n)(*infos), (ctypes.c_uint32 * n)(*root_serials)
+        main = ctypes.c_void_p()
+        _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
+                                                                (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
+        call = lambda st: lib().vp9hip_decoder_acc_propagate(self._d, aa, ser, idx, n, m, ctypes.byref(d), src.data_ptr(),
+                                                             res.data_ptr(), v.data_ptr() if valid else None, st)
+        _check(fn, _enqueue_for_torch(main.value, None, call))
+        torch.cuda.current_stream().synchronize()
+        return (res, v) if valid else res
 
     def acc_warp_tensors(self, infos, root_infos, fmt, resize=None, interp="nearest", coverage=False, out=None):
         """The accumulated residual at model size of the pairs (infos[i], root_infos[i]) of frames

@@ -586,6 +586,29 @@ extern "C" int vp9hip_decoder_acc_warp_scaled(vp9hip_decoder *d, const vp9hip_de
     return vp9hip_acc_warp_scaled(d->ctx, ba.data(), bb.data(), n, &o, dst_dev, stream);
 }
 
+// The accumulated propagation of received frames (vp9hip_acc_propagate), under
+// vp9hip_decoder_acc_warp's rules: complete frames of one size that stay the caller's, nothing
+// ordered and nothing released. The roots are serials, so the key frame needs no pin. A
+// show_existing_frame output names the shown buffer, so its field is that frame's.
+extern "C" int vp9hip_decoder_acc_propagate(vp9hip_decoder *d, const vp9hip_decoded_frame *frames,
+                                            const uint32_t *root_serials, const int *src_index, int n, int m,
+                                            const vp9hip_prop_desc *desc, const void *src_dev, void *dst_dev,
+                                            uint8_t *valid_dev, void *stream)
+{
+    if (!d || !frames || n <= 0 || !desc || !d->configured || !(d->export_flags & VP9HIP_EXPORT_MOTION_ACC)) return VP9HIP_EINVAL;
+    std::vector<int> bufs(n);
+    const vp9hip_decoded_frame &f0 = frames[0];
+    for (int i = 0; i < n; i++) {
+        const vp9hip_decoded_frame &f = frames[i];
+        if (f.buf < 0 || f.buf >= d->nbufs || d->pins[f.buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+        if (f.width != f0.width || f.height != f0.height) return VP9HIP_EINVAL;
+        bufs[i] = f.buf;
+    }
+    vp9hip_prop_desc o = *desc;
+    o.width = f0.width; o.height = f0.height;
+    return vp9hip_acc_propagate(d->ctx, bufs.data(), root_serials, src_index, n, m, &o, src_dev, dst_dev, valid_dev, stream);
+}
+
 // avcodec_flush_buffers (vp9.c:1865-1883): drop the decoder delay and the reference
 // state; frames already handed out stay valid until released.
 extern "C" int vp9hip_decoder_flush(vp9hip_decoder *d)

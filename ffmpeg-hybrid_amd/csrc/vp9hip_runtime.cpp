@@ -49,6 +49,7 @@
 #include "vp9hip_metrics.h"
 #include "vp9hip_warp.h"
 #include "vp9hip_warp_scale.h"
+#include "vp9hip_prop.h"
 #include "vp9hip_residual_scale.h"
 #include "vp9hip_motion_scale.h"
 #include "vp9hip_residn.h"
@@ -4342,5 +4343,93 @@ extern "C" int vp9hip_warp_scale_launch_dev(const void *const *a_dev, const void
         a.b[k] = (const uint8_t *) b_dev[i];
         a.acc[k] = (const uint4 *) acc_dev[i];
         a.serial[k] = serial_b[i];
+    });
+}
+
+// Accumulated propagation (include/vp9hip.h "accumulated propagation"; k_prop_nchw / k_prop_nhwc
+// in vp9hip_prop.hip). prop_args: what d asks for, checked, into the arguments, with the checks
+// of the tensors that need no context: src_index, the pointers' alignment and the two byte
+// ranges; < 0: refused.
+static int prop_args(PropArgs &a, const vp9hip_prop_desc *d, const int *src_index, int n, int m, const void *src_dev,
+                     void *dst_dev)
+{
+    memset(&a, 0, sizeof(a));
+    if (n <= 0 || m <= 0 || !d || !src_dev || !dst_dev) return VP9HIP_EINVAL;
+    const int64_t item = vp9hip_prop_layout(d, nullptr);
+    if (item < 0) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (src_index ? src_index[i] < 0 || src_index[i] >= m : i >= m) return VP9HIP_EINVAL;
+    const uintptr_t s0 = (uintptr_t) src_dev, d0 = (uintptr_t) dst_dev, e = (uintptr_t) d->elem_size;
+    if ((s0 | d0) & (e - 1)) return VP9HIP_EINVAL;
+    if (s0 < d0 + (uintptr_t) n * (uintptr_t) item && d0 < s0 + (uintptr_t) m * (uintptr_t) item) return VP9HIP_EINVAL;
+    a.item = item;
+    a.w = d->width; a.h = d->height; a.fw = d->fw; a.fh = d->fh; a.c = d->channels;
+    a.gw = 2 * ((a.w + 7) >> 3); a.gh = 2 * ((a.h + 7) >> 3);
+    a.rw = 1.0 / (2.0 * a.w); a.rh = 1.0 / (2.0 * a.h); a.rfw = 1.0 / (2.0 * a.fw); a.rfh = 1.0 / (2.0 * a.fh);
+    a.keep = d->flags & VP9HIP_PROP_KEEP;
+    uint64_t f = d->elem_size == 8 ? d->fill : d->fill & ((1ull << (8 * d->elem_size)) - 1);
+    for (int b = d->elem_size; b < 8; b *= 2) f |= f << (8 * b);
+    a.fill = f;
+    return 0;
+}
+
+// The launches of a checked call, PROP_MAX_PAIRS pairs each; rec(i, k) fills pair i's field and
+// serial into slot k of the arguments.
+template <class F>
+static int prop_launches(PropArgs &a, int n, const vp9hip_prop_desc *d, const int *src_index, const void *src_dev,
+                         void *dst_dev, uint8_t *valid_dev, hipStream_t st, F rec)
+{
+    for (int i0 = 0; i0 < n; i0 += PROP_MAX_PAIRS) {
+        const int k = std::min(n - i0, PROP_MAX_PAIRS);
+        for (int i = 0; i < k; i++) {
+            rec(i0 + i, i);
+            a.src[i] = (const uint8_t *) src_dev + (int64_t) (src_index ? src_index[i0 + i] : i0 + i) * a.item;
+        }
+        a.dst = (uint8_t *) dst_dev + (int64_t) i0 * a.item;
+        a.valid = valid_dev ? valid_dev + (size_t) i0 * a.fh * a.fw : nullptr;
+        HIPCHK(vp9hip_prop_launch(a, d->elem_size, d->layout, d->mode, k, st));
+    }
+    return 0;
+}
+
+// Everything is validated before the first launch, so a refused call writes nothing; the
+// records travel as kernel arguments, like vp9hip_acc_warp's.
+extern "C" int vp9hip_acc_propagate(vp9hip_ctx *c, const int *bufs_a, const uint32_t *root_serials, const int *src_index,
+                                    int n, int m, const vp9hip_prop_desc *d, const void *src_dev, void *dst_dev,
+                                    uint8_t *valid_dev, void *stream)
+{
+    if (!c || c->bufs.empty() || c->acc.empty() || !bufs_a || !root_serials) return VP9HIP_EINVAL;
+    PropArgs a;
+    if (prop_args(a, d, src_index, n, m, src_dev, dst_dev) < 0) return VP9HIP_EINVAL;
+    if (d->width > c->w || d->height > c->h) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (bufs_a[i] < 0 || bufs_a[i] >= (int) c->acc.size()) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!c->mot_gwh[bufs_a[i]].first) return VP9HIP_EAGAIN;
+    for (int i = 0; i < n; i++)
+        if (c->mot_gwh[bufs_a[i]].first != a.gw || c->mot_gwh[bufs_a[i]].second != a.gh) return VP9HIP_EINVAL;
+    a.acc_pitch = (int32_t) c->mot_pitch;
+    hipSetDevice(c->dev);
+    return prop_launches(a, n, d, src_index, src_dev, dst_dev, valid_dev, stream ? (hipStream_t) stream : c->st,
+                         [&](int i, int k) {
+        a.acc[k] = (const uint4 *) c->acc[bufs_a[i]];
+        a.serial[k] = root_serials[i];
+    });
+}
+
+extern "C" int vp9hip_prop_launch_dev(const void *const *acc_dev, int64_t acc_pitch_cells, const uint32_t *serials,
+                                      const int *src_index, int n, int m, const vp9hip_prop_desc *d, const void *src_dev,
+                                      void *dst_dev, uint8_t *valid_dev, void *stream)
+{
+    if (!acc_dev || !serials) return VP9HIP_EINVAL;
+    PropArgs a;
+    if (prop_args(a, d, src_index, n, m, src_dev, dst_dev) < 0) return VP9HIP_EINVAL;
+    if (acc_pitch_cells < a.gw || acc_pitch_cells > INT32_MAX) return VP9HIP_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!acc_dev[i] || ((uintptr_t) acc_dev[i] & 15)) return VP9HIP_EINVAL;
+    a.acc_pitch = (int32_t) acc_pitch_cells;
+    return prop_launches(a, n, d, src_index, src_dev, dst_dev, valid_dev, (hipStream_t) stream, [&](int i, int k) {
+        a.acc[k] = (const uint4 *) acc_dev[i];
+        a.serial[k] = serials[i];
     });
 }

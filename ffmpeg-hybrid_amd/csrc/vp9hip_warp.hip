@@ -32,7 +32,7 @@
 
 namespace {
 
-using namespace warpdev;                // cl, ld_run, warp_pred: shared with k_acc_warp_scale
+using namespace warpdev;                // cl, vclamp, ld_run, warp_pred: shared with k_acc_warp_scale
 
 // One run of RUN samples of a plane from (x0, y): pa / pb the plane in a and b, PW x PH its
 // visible size, (px, py) the cell's vector in 1/16 sample of the plane, drow the output row.
@@ -84,8 +84,7 @@ __global__ __launch_bounds__(WARP_TW * WARP_TH) void k_acc_warp(const WarpArgs g
     const bool app = (q.w & 0xffffu) != 0 && q.z == g.serial[z];
     if (g.mask && j == 0) g.mask[((size_t) z * g.gh + r) * g.gw + c] = app ? 1 : 0;
     const int dx = (int) q.x, dy = (int) q.y;
-    const int vx = dx < -32768 ? -32768 : dx > 32767 ? 32767 : dx;
-    const int vy = dy < -32768 ? -32768 : dy > 32767 ? 32767 : dy;
+    const int vx = vclamp(dx), vy = vclamp(dy);
     uint8_t *const out = g.dst + (size_t) z * g.dstride;
 
     // luma: row 4 r + j, samples 4 c .. 4 c + 3; 1/8 -> 1/16 sample

@@ -1,5 +1,6 @@
-// Device code k_acc_warp (vp9hip_warp.hip) and k_acc_warp_scale (vp9hip_warp_scale.hip) share:
-// one run of consecutive samples of a plane, as include/vp9hip.h "accumulated residual" defines
+// Device code k_acc_warp (vp9hip_warp.hip), k_acc_warp_scale (vp9hip_warp_scale.hip) and the
+// propagation kernels (vp9hip_prop.hip) share: cl, the vector clamp and the split of a
+// displacement in 1/16 sample (vclamp, near16, whole16, phase16), which all three use, and one run of consecutive samples of a plane, as include/vp9hip.h "accumulated residual" defines
 // them: a's samples of the run, and the run's prediction from b through the cell's vector
 // (steps 4 and 5: nearest, bilinear). Everything is __device__ __forceinline__: no kernels, no
 // __shared__.
@@ -24,6 +25,18 @@ __device__ __forceinline__ int cl(const int v, const int n)
 {
     return v < 0 ? 0 : v > n - 1 ? n - 1 : v;
 }
+
+// step 3: a cell's accumulated component clamped to the int16 range
+__device__ __forceinline__ int vclamp(const int d)
+{
+    return d < -32768 ? -32768 : d > 32767 ? 32767 : d;
+}
+
+// a displacement p in 1/16 sample: the whole samples to the nearest position (step 4), and the
+// whole samples below it and the phase 0..15 (step 5); arithmetic shifts
+__device__ __forceinline__ int near16(const int p) { return (p + 8) >> 4; }
+__device__ __forceinline__ int whole16(const int p) { return p >> 4; }
+__device__ __forceinline__ uint32_t phase16(const int p) { return (uint32_t) p & 15; }
 
 template <typename T> __device__ __forceinline__ uint32_t ld(const uint8_t *row, const int x)
 {
@@ -78,8 +91,8 @@ __device__ __forceinline__ void warp_pred(const uint8_t *const pb, const size_t 
                                           const int x0, const int y, const int px, const int py, uint32_t (&pv)[RUN])
 {
     if (MODE == VP9HIP_WARP_NEAREST) {
-        const uint8_t *const rb = pb + (size_t) cl(y + ((py + 8) >> 4), PH) * pitch;
-        const int xs = x0 + ((px + 8) >> 4);
+        const uint8_t *const rb = pb + (size_t) cl(y + near16(py), PH) * pitch;
+        const int xs = x0 + near16(px);
         if (xs >= 0 && xs * (int) sizeof(T) + span_bytes<T, RUN>() <= PW * (int) sizeof(T)) {
             ld_span<T, RUN>(rb + (size_t) xs * sizeof(T), pv);           // no column clamps: the run is contiguous
         } else {
@@ -87,8 +100,8 @@ __device__ __forceinline__ void warp_pred(const uint8_t *const pb, const size_t 
             for (int i = 0; i < RUN; i++) pv[i] = ld<T>(rb, cl(xs + i, PW));
         }
     } else {
-        const int ys = y + (py >> 4), xs = x0 + (px >> 4);
-        const uint32_t fx = (uint32_t) px & 15, fy = (uint32_t) py & 15;
+        const int ys = y + whole16(py), xs = x0 + whole16(px);
+        const uint32_t fx = phase16(px), fy = phase16(py);
         const uint8_t *const r0 = pb + (size_t) cl(ys, PH) * pitch, *const r1 = pb + (size_t) cl(ys + 1, PH) * pitch;
         // the run's RUN + 1 columns of both rows, blended down the column first
         uint32_t t[RUN + 1], u[RUN + 1];

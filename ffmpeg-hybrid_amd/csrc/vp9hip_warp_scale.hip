@@ -52,6 +52,7 @@ namespace {
 
 using namespace cvtdev;
 using warpdev::cl;
+using warpdev::vclamp;
 
 __device__ __forceinline__ uint32_t overlap(int lo, int n_src, int so, int n_out)
 {
@@ -66,8 +67,8 @@ __device__ __forceinline__ Cell cell_of(const uint4 q, const uint32_t serial, co
     const int dx = (int) q.x, dy = (int) q.y;
     Cell c;
     c.app = (q.w & 0xffffu) != 0 && q.z == serial;
-    c.px = (dx < -32768 ? -32768 : dx > 32767 ? 32767 : dx) * mx;
-    c.py = (dy < -32768 ? -32768 : dy > 32767 ? 32767 : dy) * my;
+    c.px = vclamp(dx) * mx;
+    c.py = vclamp(dy) * my;
     return c;
 }
 

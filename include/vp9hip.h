@@ -60,7 +60,10 @@ extern "C" {
  * vp9hip_warp_launch_dev, vp9hip_decoder_acc_warp) likewise: new enums and new symbols. The
  * accumulated residual at model size (vp9hip_warpt_desc, vp9hip_warpt_layout,
  * vp9hip_acc_warp_scaled, vp9hip_acc_warp_scaled_host, vp9hip_warp_scale_launch_dev,
- * vp9hip_decoder_acc_warp_scaled) likewise: a new struct and new symbols. */
+ * vp9hip_decoder_acc_warp_scaled) likewise: a new struct and new symbols. The accumulated
+ * propagation (VP9HIP_PROP_*, vp9hip_prop_desc, vp9hip_prop_layout, vp9hip_acc_propagate,
+ * vp9hip_acc_propagate_host, vp9hip_prop_launch_dev, vp9hip_decoder_acc_propagate) likewise: new
+ * enums, a new struct and new symbols. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -1064,6 +1067,111 @@ int  vp9hip_warp_scale_launch_dev(const void *const *a_dev, const void *const *b
                                   int64_t acc_pitch_cells, int bpp, int ss_h, int ss_v,
                                   const vp9hip_warpt_desc *d, void *dst_dev, void *stream);
 
+/* ---- accumulated propagation: a caller's tensor of the root frame displaced by the accumulated motion ----
+ * Temporal propagation of labels or features: a model runs on the key frame, and its label map
+ * or feature map is carried to the frames that follow through their accumulated fields. It is
+ * the gather of "accumulated residual" with the caller's tensor as source and destination
+ * instead of the frame buffers: the tensor lives on its own grid, has C channels and its own
+ * element type. One launch per 32 pairs (k_prop_nchw / k_prop_nhwc). On demand, like
+ * vp9hip_acc_warp: nothing in the decode path changes, and without the call nothing is launched
+ * or allocated.
+ *
+ * Definition. A pair i is (a, S, src item): a is a buffer of a configured context that holds an
+ * accumulated field, of grid GW x GH for the visible size w x h exactly as in "accumulated
+ * residual"; S is the root's serial, a uint32_t the caller gives (vp9hip_frame_motion_acc and
+ * vp9hip_download_motion_acc report a frame's serial). No root buffer is needed: the key frame's
+ * pixels may have been released long ago, and its buffer overwritten. Serial 0 never applies.
+ * The source item is src[src_index[i]]; a NULL src_index means i.
+ * The tensor: M source items and n destination items, each of C channels on a feature grid
+ * FW x FH that covers the visible w x h picture uniformly; elements of E = 1, 2, 4 or 8 bytes;
+ * tight NCHW (VP9HIP_PROP_NCHW: element (ch, fy, fx) of an item at ((ch FH + fy) FW + fx) E
+ * bytes) or tight NHWC (VP9HIP_PROP_NHWC: at ((fy FW + fx) C + ch) E bytes). The layout changes
+ * addresses only. FW, FH in 1..16384, C in 1..4096, w and h as vp9hip_acc_warp.
+ * For an output sample (fx, fy), all channels alike:
+ *   1. The luma sample under its centre is X = ((2 fx + 1) w) / (2 FW), Y = ((2 fy + 1) h) / (2 FH):
+ *      non-negative operands, the division floors, X < w and Y < h. The cell is c = X >> 2,
+ *      r = Y >> 2, and q = acc_a[r][c].
+ *   2. The cell applies iff q.hops > 0 && q.root == S: step 2 of "accumulated residual" with S in
+ *      place of S_b.
+ *   3. vx = clamp(q.dx, -32768, 32767), vy likewise. The displacement in 1/16 feature sample is
+ *      Px = floor((4 vx FW + w) / (2 w)), Py = floor((4 vy FH + h) / (2 h)): a floor division of
+ *      possibly negative 64-bit values, 2 vx FW / w rounded half up. With FW = w it is 2 vx, the
+ *      luma rule of vp9hip_acc_warp; with w even and FW = w / 2 it is vx, its 4:2:0 chroma rule.
+ *   4. VP9HIP_WARP_NEAREST: xs = cl(fx + ((Px + 8) >> 4), FW), ys = cl(fy + ((Py + 8) >> 4), FH)
+ *      with cl and the shifts of "accumulated residual"; the element (ch, ys, xs) of the source
+ *      item is copied bit for bit, at any E.
+ *   5. VP9HIP_WARP_BILINEAR: E = 2 only, the elements are IEEE binary16. x0 = fx + (Px >> 4),
+ *      frx = Px & 15, y0 and fry likewise; the four samples s00, s01 (row cl(y0, FH), columns
+ *      cl(x0, FW), cl(x0 + 1, FW)) and s10, s11 (row cl(y0 + 1, FH)) are widened to binary32
+ *      (exact). Each of the following operations is one binary32 operation, rounded to nearest
+ *      even and never contracted:
+ *        top = (16 - frx) s00 + frx s01
+ *        bot = (16 - frx) s10 + frx s11
+ *        v   = ((16 - fry) top + fry bot) 2^-8
+ *      and the element is v rounded to the nearest-even binary16, subnormal halves included. The
+ *      products of top and bot are exact, and no binary32 subnormal can arise. Non-finite inputs
+ *      are outside the definition.
+ *   6. Where the cell does not apply the element is the low E bytes of `fill`; with
+ *      VP9HIP_PROP_KEEP the destination element is not written at all (the caller pre-fills it,
+ *      e.g. with a cheap fresh inference).
+ *   7. The optional valid output is uint8_t, tight (n, FH, FW): 1 where the sample's cell applies,
+ *      else 0; written in both cases of step 6.
+ * Not offered: source or destination rectangles, letterboxed grids, other filters, bilinear on
+ * other element types, the second reference, strided tensors. */
+enum { VP9HIP_PROP_NCHW, VP9HIP_PROP_NHWC };
+#define VP9HIP_PROP_KEEP 1          /* flags: leave the destination where the cell does not apply */
+typedef struct vp9hip_prop_desc {
+    int32_t width, height;          /* the visible size w x h; vp9hip_decoder_acc_propagate sets it from the frames */
+    int32_t fw, fh;                 /* the feature grid FW x FH, 1..16384 */
+    int32_t channels;               /* C, 1..4096 */
+    int32_t elem_size;              /* E: 1, 2, 4 or 8 bytes */
+    int32_t layout;                 /* VP9HIP_PROP_NCHW / VP9HIP_PROP_NHWC */
+    int32_t mode;                   /* VP9HIP_WARP_NEAREST / VP9HIP_WARP_BILINEAR (E = 2: binary16) */
+    int32_t flags;                  /* 0 or VP9HIP_PROP_KEEP */
+    int32_t reserved;               /* 0 */
+    uint64_t fill;                  /* its low E bytes are the element where the cell does not apply */
+} vp9hip_prop_desc;
+/* Bytes of one item of d (C FH FW E) and, if valid_bytes is not NULL, of one item's valid map
+ * (FH FW); VP9HIP_EINVAL for a NULL d, a width, height, fw or fh outside 1..16384, channels
+ * outside 1..4096, an elem_size other than 1 / 2 / 4 / 8, an unknown layout or mode, bilinear
+ * with elem_size != 2, unknown flag bits or a reserved field that is not 0. Host only. */
+int64_t vp9hip_prop_layout(const vp9hip_prop_desc *d, int64_t *valid_bytes);
+/* The pairs (bufs_a[i], root_serials[i], src item src_index[i]), i < n, of the m source items at
+ * src_dev into the n items at dst_dev (device memory, strides of vp9hip_prop_layout) and, if
+ * valid_dev is not NULL, their valid maps into valid_dev (n FH FW bytes), under the contract of
+ * vp9hip_acc_warp: any buffers in any order, repeats allowed; n above 32 is split into launches
+ * of at most 32 pairs; it enqueues on `stream` (NULL: the current slot's main stream) and returns
+ * without waiting, orders nothing itself, does not allocate and reads no device memory on the
+ * host, so it can sit in a captured stream; only the elements of the definition (and the valid
+ * maps) are written; everything is checked before the first launch: a refused call writes
+ * nothing. VP9HIP_EINVAL: a context without VP9HIP_EXPORT_MOTION_ACC or not configured, a buffer
+ * index out of range, n <= 0 or m <= 0, NULL bufs_a, root_serials, d, src_dev or dst_dev, a
+ * src_index[i] outside 0..m-1 (a NULL src_index with n > m), a width / height outside 1 .. the
+ * configured size or whose grid is not that of a's field, what vp9hip_prop_layout refuses,
+ * src_dev or dst_dev not aligned to E, the byte ranges of the m source items and the n
+ * destination items overlapping. VP9HIP_EAGAIN: an a without a field (checked after the indices,
+ * before the grid). */
+int  vp9hip_acc_propagate(vp9hip_ctx *ctx, const int *bufs_a, const uint32_t *root_serials, const int *src_index,
+                          int n, int m, const vp9hip_prop_desc *d, const void *src_dev, void *dst_dev,
+                          uint8_t *valid_dev, void *stream);
+/* Host only, no device: the C statement of the definition above for one pair, one sample at a
+ * time: a's field as a tight array acc[GH][GW], one source item src and one destination item dst
+ * in host memory, valid ([FH][FW]) may be NULL. The binary32 operations of step 5 are spelled
+ * one a statement and the file is compiled with contraction off; the conversions to and from
+ * binary16 are done in integers. VP9HIP_EINVAL: a NULL acc, d, src or dst, what
+ * vp9hip_prop_layout refuses; a refused call writes nothing. */
+int  vp9hip_acc_propagate_host(const vp9hip_acc_cell *acc, uint32_t root_serial, const vp9hip_prop_desc *d,
+                               const void *src, void *dst, uint8_t *valid);
+/* Diagnostics (tools/acc_propagate_bench.py, the crafted-field tests): the propagation kernels
+ * over caller-made fields in device memory, on `stream`, split into launches of 32 pairs like
+ * vp9hip_acc_propagate. Pair i reads the field acc_dev[i] (vp9hip_acc_cell
+ * [GH][acc_pitch_cells], 16-byte aligned) with the serial serials[i]; the arrays themselves are
+ * host memory. VP9HIP_EINVAL: NULL arguments, n <= 0 or m <= 0, acc_pitch_cells below GW, and
+ * what vp9hip_acc_propagate refuses of src_index, d, src_dev and dst_dev. */
+int  vp9hip_prop_launch_dev(const void *const *acc_dev, int64_t acc_pitch_cells, const uint32_t *serials,
+                            const int *src_index, int n, int m, const vp9hip_prop_desc *d, const void *src_dev,
+                            void *dst_dev, uint8_t *valid_dev, void *stream);
+
 /* Upload host planes into device buffer `buf` (test hook for reference frames). */
 int  vp9hip_upload_frame(vp9hip_ctx *ctx, int buf, const uint8_t *const planes[3],
                          const ptrdiff_t linesize[3]);
@@ -1501,6 +1609,16 @@ int  vp9hip_decoder_acc_warp(vp9hip_decoder *d, const vp9hip_decoded_frame *fram
 int  vp9hip_decoder_acc_warp_scaled(vp9hip_decoder *d, const vp9hip_decoded_frame *frames_a,
                                     const vp9hip_decoded_frame *frames_b, int n,
                                     const vp9hip_warpt_desc *desc, void *dst_dev, void *stream);
+/* The accumulated propagation of the pairs (frames[i], root_serials[i], src item src_index[i]) of
+ * received frames through vp9hip_acc_propagate, under the rules of vp9hip_decoder_acc_warp: every
+ * frame must be of one size and held by the caller; desc's width and height are not read but
+ * taken from the frames; a show_existing_frame output uses the shown buffer's field. The root
+ * needs no frame: its serial is enough, also after the caller released it. It only enqueues and
+ * releases nothing. Needs VP9HIP_EXPORT_MOTION_ACC. */
+int  vp9hip_decoder_acc_propagate(vp9hip_decoder *d, const vp9hip_decoded_frame *frames,
+                                  const uint32_t *root_serials, const int *src_index, int n, int m,
+                                  const vp9hip_prop_desc *desc, const void *src_dev, void *dst_dev,
+                                  uint8_t *valid_dev, void *stream);
 /* avcodec_flush_buffers: drop queued frames and reference state (seek). */
 int  vp9hip_decoder_flush(vp9hip_decoder *d);
 
