@@ -167,7 +167,9 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9hip_warpt_layout", "vp9hip_acc_warp_scaled", "vp9hip_acc_warp_scaled_host",
                "vp9hip_warp_scale_launch_dev", "vp9hip_decoder_acc_warp_scaled",
                "vp9hip_prop_layout", "vp9hip_acc_propagate", "vp9hip_acc_propagate_host", "vp9hip_prop_launch_dev",
-               "vp9hip_decoder_acc_propagate"]
+               "vp9hip_decoder_acc_propagate",
+               "vp9hip_grade_create", "vp9hip_grade_destroy", "vp9hip_convert_frames_graded",
+               "vp9hip_decoder_convert_graded", "vp9hip_grade_host", "vp9h_webm_read_colour"]
 
 
 def lib():
@@ -303,6 +305,16 @@ def lib():
                                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
     L.vp9hip_convert_frames_bicubic.argtypes = L.vp9hip_convert_frames_resampled.argtypes
     L.vp9hip_decoder_convert_bicubic.argtypes = L.vp9hip_decoder_convert_resampled.argtypes
+    L.vp9hip_grade_create.argtypes = [vp, ctypes.POINTER(GradeDesc), ctypes.POINTER(vp)]
+    L.vp9hip_grade_destroy.argtypes = [vp]
+    L.vp9hip_grade_destroy.restype = None
+    L.vp9hip_convert_frames_graded.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(OutDesc),
+                                               ctypes.POINTER(Resample), vp, ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_decoder_convert_graded.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(Resample), vp, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_void_p]
+    L.vp9hip_grade_host.argtypes = [ctypes.POINTER(GradeDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    L.vp9h_webm_read_colour.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(WebmColour)]
     L.vp9hip_bicubic_weights.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int32),
                                                                ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                                                ctypes.POINTER(ctypes.c_int64)]
@@ -434,6 +446,14 @@ class WebmCursor(ctypes.Structure):
                 ("lace_size", ctypes.c_uint32 * 256)]
 
 
+class WebmColour(ctypes.Structure):
+    """vp9h_webm_colour: the Colour element of the first VP9 video track."""
+    _fields_ = [("present", ctypes.c_int32), ("matrix", ctypes.c_int32), ("bits_per_channel", ctypes.c_int32),
+                ("range", ctypes.c_int32), ("transfer", ctypes.c_int32), ("primaries", ctypes.c_int32),
+                ("max_cll", ctypes.c_int32), ("max_fall", ctypes.c_int32), ("luminance_max", ctypes.c_double),
+                ("luminance_min", ctypes.c_double)]
+
+
 class DecoderParams(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("max_batch", ctypes.c_int32), ("extra_bufs", ctypes.c_int32),
                 ("max_width", ctypes.c_int32), ("max_height", ctypes.c_int32), ("parse_threads", ctypes.c_int32)]
@@ -491,6 +511,12 @@ class Resample(ctypes.Structure):
     """vp9hip_resample: filter, output size, per-frame rectangles (or NULL) and the fill codes."""
     _fields_ = [("filter", ctypes.c_int32), ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32),
                 ("src_rects", ctypes.POINTER(Rect)), ("dst_rects", ctypes.POINTER(Rect)), ("fill", ctypes.c_int32 * 3)]
+
+
+class GradeDesc(ctypes.Structure):
+    """vp9hip_grade_desc: the depth, the output's largest code and the three host tables."""
+    _fields_ = [("bpp", ctypes.c_int32), ("out_max", ctypes.c_int32), ("in_lut", ctypes.c_void_p), ("m", ctypes.c_void_p),
+                ("out_lut", ctypes.c_void_p)]
 
 
 # VP9HIP_OUT_*: the names Device.convert / Decoder.convert take
@@ -815,6 +841,194 @@ def bicubic_weights(n_src, n_out, o):
     first, d, a, w = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), (ctypes.c_int32 * n)()
     _check("vp9hip_bicubic_weights", fn(int(n_src), int(n_out), int(o), ctypes.byref(first), w, n, ctypes.byref(d), ctypes.byref(a)))
     return first.value, list(w), d.value, a.value
+
+
+GRADE_OUT_LUT = 4097           # VP9HIP_GRADE_OUT_LUT
+
+
+def _grade_table(name, values, n, top):
+    a = np.asarray(values)
+    if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer) or (a.size and (a.min() < 0 or a.max() > top)):
+        raise ValueError("Grade: %s takes %d integers in 0..%d" % (name, n, top))
+    return np.ascontiguousarray(a, np.uint16)
+
+
+class Grade:
+    """A graded output's three tables (include/vp9hip.h "Graded output"): in_lut, 2^bpp u16; m,
+    3 x 3 int32 with 14 fractional bits, |m| <= 2^16; out_lut, 4097 u16 of at most out_max (255 for
+    "rgb24" / "rgbp_u8", 65535 for "rgbp_f16": `fmt` is the format name or out_max itself). On
+    its own it is host data (grade_host takes it); Device.grade / Decoder.grade return the one
+    that convert(grade=...) takes, with the tables in device memory (vp9hip_grade_create) until
+    close() or collection."""
+
+    def __init__(self, bpp, fmt, in_lut, m, out_lut):
+        self.bpp = int(bpp)
+        self.out_max = int(fmt) if not isinstance(fmt, str) else 65535 if fmt == "rgbp_f16" else 255
+        if self.bpp not in (8, 10, 12) or self.out_max not in (255, 65535) or fmt == "semiplanar":
+            raise ValueError("Grade: bpp is 8, 10 or 12 and fmt one of the RGB formats")
+        self.in_lut = _grade_table("in_lut", in_lut, 1 << self.bpp, 65535)
+        self.out_lut = _grade_table("out_lut", out_lut, GRADE_OUT_LUT, self.out_max)
+        m = np.asarray(m)
+        if m.size != 9 or not np.issubdtype(m.dtype, np.integer) or np.abs(m).max() > 1 << 16:
+            raise ValueError("Grade: m takes 3 x 3 integers of magnitude at most 2^16")
+        self.m = np.ascontiguousarray(m.reshape(3, 3), np.int32)
+        self._g = None
+        self._ctx = None
+
+    def desc(self):
+        """The vp9hip_grade_desc of the tables (they stay this object's)."""
+        return GradeDesc(self.bpp, self.out_max, self.in_lut.ctypes.data, self.m.ctypes.data, self.out_lut.ctypes.data)
+
+    def _on(self, ctx):
+        g = Grade(self.bpp, self.out_max, self.in_lut, self.m, self.out_lut)
+        h = ctypes.c_void_p()
+        d = g.desc()
+        _check("vp9hip_grade_create", lib().vp9hip_grade_create(ctx, ctypes.byref(d), ctypes.byref(h)))
+        g._g, g._ctx = h, ctx
+        return g
+
+    def close(self):
+        if self._g is not None:
+            lib().vp9hip_grade_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _grade_handle(grade, fmt):
+    """convert(grade=...)'s checks of its own: an RGB format, a grade with device tables."""
+    if fmt == "semiplanar":
+        raise ValueError("convert: a grade is defined for the RGB formats, not semiplanar")
+    if not isinstance(grade, Grade) or grade._g is None:
+        raise ValueError("convert: grade takes what Device.grade / Decoder.grade return")
+    return grade._g
+
+
+def grade_host(g, codes):
+    """The three stages of Grade g on the host (vp9hip_grade_host, the C statement of the
+    definition): codes is an integer array (..., 3) of R, G, B codes below 2^bpp; returns the
+    uint16 array of the same shape."""
+    codes = np.asarray(codes)
+    if codes.ndim < 1 or codes.shape[-1] != 3 or (codes.size and (codes.min() < 0 or codes.max() >= 1 << g.bpp)):
+        raise ValueError("grade_host: codes is (..., 3) with values below 2^bpp")
+    c = np.ascontiguousarray(codes, np.uint16)
+    v = np.empty(c.shape, np.uint16)
+    d = g.desc()
+    _check("vp9hip_grade_host", lib().vp9hip_grade_host(ctypes.byref(d), c.ctypes.data, c.size // 3, v.ctypes.data))
+    return v
+
+
+# CIE xy of R, G, B; the white point of all of them is D65
+_PRIMARIES = {"bt709": ((.64, .33), (.30, .60), (.15, .06)),
+              "bt601": ((.64, .33), (.29, .60), (.15, .06)),              # 625 lines (BT.470BG)
+              "bt601_525": ((.63, .34), (.31, .595), (.155, .07)),        # 525 lines (SMPTE 170M)
+              "bt2020": ((.708, .292), (.170, .797), (.131, .046))}
+_SDR_TRANSFERS = ("bt709", "srgb", "linear")
+
+
+def _rgb_to_xyz(name):
+    xy = np.array(_PRIMARIES[name], np.float64)
+    P = np.stack([xy[:, 0] / xy[:, 1], np.ones(3), (1 - xy[:, 0] - xy[:, 1]) / xy[:, 1]])
+    white = np.array([.3127 / .3290, 1., (1 - .3127 - .3290) / .3290])
+    return P * np.linalg.solve(P, white)
+
+
+def _eotf_nits(transfer, e, peak_nits, white_nits):
+    """Display light in cd/m^2 of the signal e in [0, 1]."""
+    e = np.asarray(e, np.float64)
+    if transfer == "pq":                                   # SMPTE ST 2084
+        m1, m2, c1, c2, c3 = 2610 / 16384, 2523 / 4096 * 128, 3424 / 4096, 2413 / 4096 * 32, 2392 / 4096 * 32
+        p = e ** (1 / m2)
+        return 10000. * (np.maximum(p - c1, 0) / (c2 - c3 * p)) ** (1 / m1)
+    if transfer == "hlg":                                  # BT.2100: inverse OETF, then gamma 1.2 per channel
+        a = .17883277
+        b, c = 1 - 4 * a, .5 - a * np.log(4 * a)
+        s = np.where(e <= .5, e * e / 3, (np.exp((np.minimum(e, 1.) - c) / a) + b) / 12)
+        return peak_nits * s ** 1.2
+    if transfer == "bt709":
+        return white_nits * np.where(e < .081, e / 4.5, ((e + .099) / 1.099) ** (1 / .45))
+    if transfer == "srgb":
+        return white_nits * np.where(e <= .04045, e / 12.92, ((e + .055) / 1.055) ** 2.4)
+    if transfer == "linear":
+        return white_nits * e
+    raise ValueError("make_grade: transfer_in is 'pq', 'hlg', 'bt709', 'srgb' or 'linear'")
+
+
+def _oetf(transfer, x):
+    x = np.clip(np.asarray(x, np.float64), 0, 1)
+    if transfer == "srgb":
+        return np.where(x <= .0031308, 12.92 * x, 1.055 * x ** (1 / 2.4) - .055)
+    if transfer == "bt709":
+        return np.where(x < .018, 4.5 * x, 1.099 * x ** .45 - .099)
+    if transfer == "linear":
+        return x
+    raise ValueError("make_grade: transfer_out is 'srgb', 'bt709' or 'linear' (display-referred SDR)")
+
+
+def make_grade(bpp, fmt, transfer_in, primaries_in, transfer_out="srgb", primaries_out="bt709", peak_nits=1000,
+               white_nits=203, tonemap="reinhard"):
+    """The integer tables of a colour pipeline, computed once in float64 on the host: a Grade
+    (host data; Device.grade(g) uploads it).
+      in_lut[c]  = the input EOTF of c / (2^bpp - 1) in cd/m^2, / peak_nits, clipped to 1, as the
+                   nearest u16. transfer_in: "pq" (ST 2084), "hlg", "bt709", "srgb", "linear".
+                   "hlg" is the inverse OETF and then the system gamma 1.2 on each channel: an
+                   approximation of BT.2100's OOTF, which applies the gamma to the luminance.
+                   The SDR transfers take peak_nits = white_nits.
+      m          = primaries_in -> primaries_out through XYZ with D65 ("bt709", "bt601" (625
+                   lines), "bt601_525", "bt2020"), round(x 2^14).
+      out_lut[i] = x = (i / 4096) peak_nits / white_nits, tone-mapped ("clip": min(x, 1);
+                   "reinhard": x (1 + x / w^2) / (1 + x), w = peak_nits / white_nits, which maps
+                   w to 1), through the output OETF (transfer_out: "srgb", "bt709", "linear"),
+                   times out_max, as the nearest integer.
+    Both curves are per channel. Operators that need the three channels at once (BT.2390 in
+    ICtCp, max-RGB hue-preserving maps) cannot be a grade and are out of scope."""
+    bpp = int(bpp)
+    if bpp not in (8, 10, 12):
+        raise ValueError("make_grade: bpp is 8, 10 or 12")
+    if tonemap not in ("clip", "reinhard"):
+        raise ValueError("make_grade: tonemap is 'clip' or 'reinhard'")
+    if primaries_in not in _PRIMARIES or primaries_out not in _PRIMARIES:
+        raise ValueError("make_grade: primaries are " + ", ".join(repr(k) for k in _PRIMARIES))
+    peak, white = float(peak_nits), float(white_nits)
+    if transfer_in in _SDR_TRANSFERS:
+        peak = white
+    if not (white > 0 and peak >= white):
+        raise ValueError("make_grade: 0 < white_nits <= peak_nits")
+    out_max = 65535 if fmt == "rgbp_f16" else 255
+    code = np.arange(1 << bpp, dtype=np.float64) / ((1 << bpp) - 1)
+    in_lut = np.rint(np.clip(_eotf_nits(transfer_in, code, peak, white) / peak, 0, 1) * 65535).astype(np.int64)
+    if primaries_in == primaries_out:
+        m = np.eye(3)
+    else:
+        m = np.linalg.solve(_rgb_to_xyz(primaries_out), _rgb_to_xyz(primaries_in))
+    m = np.rint(m * (1 << 14)).astype(np.int64)
+    x = np.arange(GRADE_OUT_LUT, dtype=np.float64) / 4096 * (peak / white)
+    w = peak / white
+    x = np.minimum(x, 1) if tonemap == "clip" else x * (1 + x / (w * w)) / (1 + x)
+    out_lut = np.rint(_oetf(transfer_out, x) * out_max).astype(np.int64)
+    return Grade(bpp, fmt, in_lut, m, out_lut)
+
+
+# Matroska's TransferCharacteristics / Primaries codes -> make_grade's names
+_WEBM_TRANSFERS = {16: "pq", 18: "hlg", 1: "bt709", 13: "srgb"}
+_WEBM_PRIMARIES = {9: "bt2020", 1: "bt709", 5: "bt601", 6: "bt601_525"}
+
+
+def grade_for(colour, bpp, fmt, **kw):
+    """make_grade for a stream's colour description (webm_colour's dict): transfer codes 16 (PQ),
+    18 (HLG), 1 (BT.709), 13 (sRGB) and primaries 9 (BT.2020), 1 (BT.709), 5 / 6 (BT.601 625 /
+    525); any other code, "unspecified" included, is a ValueError (pass the names to make_grade
+    yourself). A mastering LuminanceMax becomes peak_nits unless given; kw goes to make_grade."""
+    t, p = colour.get("transfer", 2), colour.get("primaries", 2)
+    if t not in _WEBM_TRANSFERS or p not in _WEBM_PRIMARIES:
+        raise ValueError("grade_for: no grade for transfer %r, primaries %r" % (t, p))
+    if "peak_nits" not in kw and colour.get("luminance_max", 0) > 0:
+        kw["peak_nits"] = colour["luminance_max"]
+    return make_grade(bpp, fmt, _WEBM_TRANSFERS[t], _WEBM_PRIMARIES[p], **kw)
 
 
 def letterbox_rect(w, h, OW, OH, align=(1, 1)):
@@ -1976,8 +2190,15 @@ class Device:
             raise Vp9HipError(fn, EINVAL)
         return ow, oh
 
+    def grade(self, fmt, in_lut=None, m=None, out_lut=None):
+        """A Grade for convert(grade=...) with its tables in this device's memory
+        (vp9hip_grade_create): grade(g) of a host Grade (make_grade's, grade_for's), or
+        grade(fmt, in_lut, m, out_lut) at the configured depth."""
+        g = fmt if isinstance(fmt, Grade) else Grade(self.bpp, fmt, in_lut, m, out_lut)
+        return g._on(self._c)
+
     def convert(self, bufs, fmt, colorspace=2, full_range=False, size=None, out=None, stream=None,
-                pitch=0, frame_stride=0, resize=None, filter="box", src_rects=None, dst_rects=None, fill=None):
+                pitch=0, frame_stride=0, resize=None, filter="box", src_rects=None, dst_rects=None, fill=None, grade=None):
         """Convert device buffers `bufs` (any order) to `fmt` on the GPU (vp9hip_convert_frames):
         "rgb24" -> (N,H,W,3) uint8, "rgbp_u8" -> (N,3,H,W) uint8, "rgbp_f16" -> (N,3,H,W)
         float16 in [0,1], "semiplanar" -> (y, uv) views of one allocation, (N,H,W) and
@@ -1996,7 +2217,11 @@ class Device:
         vp9hip_convert_frames_resampled, the exact definitions of include/vp9hip.h;
         filter="bicubic" (Keys a = -1/2, antialiased when downscaling, clipped: within one code of
         torch's interpolate(mode="bicubic", antialias=True)) takes the same arguments through
-        vp9hip_convert_frames_bicubic; any of them without resize is a ValueError. Runs in the order of torch's current stream (or on
+        vp9hip_convert_frames_bicubic; any of them without resize is a ValueError. grade (what
+        Device.grade returns; RGB formats only, "semiplanar" is a ValueError) passes every stored
+        pixel through the grade's in_lut, matrix and out_lut in the same launch
+        (vp9hip_convert_frames_graded, any filter; without resize the visible size, which is the
+        box filter at equal size). Runs in the order of torch's current stream (or on
         `stream`, a hipStream_t handle; see _enqueue_for_torch) and does not wait: order it after the frames' producer (sync(), or
         vp9hip_slot_stream_wait), as for frame_tensors. Needs torch imported before the library
         was loaded (see _torch_first)."""
@@ -2008,7 +2233,12 @@ class Device:
         w, h = size if size is not None else (self.w, self.h)
         d = OutDesc(OUT_FORMATS[fmt], int(colorspace), int(bool(full_range)), int(w), int(h), int(pitch), int(frame_stride))
         rs = _resample_arg(len(bufs), resize, filter, src_rects, dst_rects, fill, self.bpp, int(colorspace), full_range)
-        fn = ("vp9hip_convert_frames" if resize is None else
+        if grade is not None:
+            gh = _grade_handle(grade, fmt)
+            if rs is None:
+                rs = Resample(FILTERS["box"], *(int(x) for x in (resize if resize is not None else (w, h))))
+        fn = ("vp9hip_convert_frames_graded" if grade is not None else
+              "vp9hip_convert_frames" if resize is None else
               "vp9hip_convert_frames_scaled" if rs is None else
               "vp9hip_convert_frames_bicubic" if rs.filter == FILTER_BICUBIC else "vp9hip_convert_frames_resampled")
         if not bufs:
@@ -2016,7 +2246,10 @@ class Device:
         ow, oh = (w, h) if resize is None else self._resize_arg(fn, resize)
         flat, res, _, _ = self._convert_out(len(bufs), fmt, ow, oh, self.bpp, self.ss_h, self.ss_v, out, pitch, frame_stride)
         arr = (ctypes.c_int * len(bufs))(*bufs)
-        if rs is not None:
+        if grade is not None:
+            call = lambda st: lib().vp9hip_convert_frames_graded(self._c, arr, len(bufs), ctypes.byref(d), ctypes.byref(rs), gh,
+                                                                 flat.data_ptr(), st)
+        elif rs is not None:
             call = lambda st: getattr(lib(), fn)(self._c, arr, len(bufs), ctypes.byref(d), ctypes.byref(rs), flat.data_ptr(), st)
         elif resize is None:
             call = lambda st: lib().vp9hip_convert_frames(self._c, arr, len(bufs), ctypes.byref(d), flat.data_ptr(), st)
@@ -2427,13 +2660,20 @@ class Decoder:
         torch.cuda.current_stream().synchronize()
         return res
 
-    def convert(self, infos, fmt, out=None, resize=None, filter="box", src_rects=None, dst_rects=None, fill=None):
+    def grade(self, fmt, in_lut=None, m=None, out_lut=None, bpp=None):
+        """A Grade for convert(grade=...) with its tables in the decoder's device memory, as
+        Device.grade: grade(g) of a host Grade, or grade(fmt, in_lut, m, out_lut, bpp=...)."""
+        g = fmt if isinstance(fmt, Grade) else Grade(bpp, fmt, in_lut, m, out_lut)
+        return g._on(self.context())
+
+    def convert(self, infos, fmt, out=None, resize=None, filter="box", src_rects=None, dst_rects=None, fill=None, grade=None):
         """Convert the frames of receive_frame(download=False) (their DecodedFrameInfos, all of
         one size, colour space and range) to `fmt` as Device.convert does, with the frames' own
         colour description (vp9hip_decoder_convert; with resize=(OW, OH)
         vp9hip_decoder_convert_scaled; with filter / src_rects / dst_rects / fill as well, which
         mean what they mean there, vp9hip_decoder_convert_resampled, or vp9hip_decoder_convert_bicubic for
-        filter="bicubic"), on torch's current stream; waits for it and releases
+        filter="bicubic"; with grade, what Decoder.grade returns, vp9hip_decoder_convert_graded for
+        any of them), on torch's current stream; waits for it and releases
         the buffers. Returns the tensor(s)."""
         if not _torch_first:
             raise Vp9HipUnavailable("convert: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
@@ -2443,7 +2683,12 @@ class Decoder:
         f = infos[0] if infos else DecodedFrameInfo()
         cs = 2 if f.colorspace in (0, 6) else f.colorspace
         rs = _resample_arg(len(infos), resize, filter, src_rects, dst_rects, fill, f.bpp or 8, cs, f.full_range)
-        fn = ("vp9hip_decoder_convert" if resize is None else
+        if grade is not None:
+            gh = _grade_handle(grade, fmt)
+            if rs is None:
+                rs = Resample(FILTERS["box"], *(int(x) for x in (resize if resize is not None else (f.width, f.height))))
+        fn = ("vp9hip_decoder_convert_graded" if grade is not None else
+              "vp9hip_decoder_convert" if resize is None else
               "vp9hip_decoder_convert_scaled" if rs is None else
               "vp9hip_decoder_convert_bicubic" if rs.filter == FILTER_BICUBIC else "vp9hip_decoder_convert_resampled")
         if not infos:
@@ -2454,7 +2699,10 @@ class Decoder:
         main = ctypes.c_void_p()
         _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
                                                                 (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
-        if rs is not None:
+        if grade is not None:
+            call = lambda st: lib().vp9hip_decoder_convert_graded(self._d, arr, len(infos), OUT_FORMATS[fmt], ctypes.byref(rs), gh,
+                                                                  flat.data_ptr(), 0, 0, st)
+        elif rs is not None:
             call = lambda st: getattr(lib(), fn)(self._d, arr, len(infos), OUT_FORMATS[fmt], ctypes.byref(rs),
                                                  flat.data_ptr(), 0, 0, st)
         elif resize is None:
@@ -2733,17 +2981,41 @@ def _uint(i, v):
     return _el(i, v.to_bytes(max(1, (v.bit_length() + 7) // 8), "big"))
 
 
+WEBM_COLOUR_IDS = {"matrix": 0x55B1, "bits_per_channel": 0x55B2, "range": 0x55B9, "transfer": 0x55BA, "primaries": 0x55BB,
+                   "max_cll": 0x55BC, "max_fall": 0x55BD}
+
+
+def webm_colour(data):
+    """The Colour element of the first VP9 video track as a dict (vp9h_webm_read_colour):
+    present, matrix, bits_per_channel, range, transfer, primaries, max_cll, max_fall,
+    luminance_max, luminance_min; absent fields are 2 ("unspecified") or 0."""
+    data = bytes(data)
+    c = WebmColour()
+    _check("vp9h_webm_read_colour", lib().vp9h_webm_read_colour(data, len(data), ctypes.byref(c)))
+    return {k: getattr(c, k) for k, _ in WebmColour._fields_}
+
+
+def _webm_colour_element(colour):
+    """The Colour element (0x55B0) of webm_colour's keys; luminance_* as 8-byte floats."""
+    import struct
+    body = b"".join(_uint(i, int(colour[k])) for k, i in WEBM_COLOUR_IDS.items() if k in colour)
+    mm = b"".join(_el(i, struct.pack(">d", float(colour[k]))) for k, i in (("luminance_max", 0x55D9), ("luminance_min", 0x55DA))
+                  if k in colour)
+    return _el(0x55B0, body + (_el(0x55D0, mm) if mm else b""))
+
+
 def webm_write(frames, width, height, timecode_scale=1000000, cluster_frames=8, lacing=None,
-               unknown_sizes=False, block_groups=False, other_track=False, voids=False):
+               unknown_sizes=False, block_groups=False, other_track=False, voids=False, colour=None):
     """[(pts, bytes)] or [bytes] -> WebM bytes with one V_VP9 track (number 1). Options for
     tests: lacing = "xiph" / "fixed" / "ebml" (frames laced in pairs), unknown-size Segment
     and Clusters, BlockGroup + Block instead of SimpleBlock, an interleaved second track's
-    blocks, Void elements."""
+    blocks, Void elements. colour: a dict of webm_colour's keys, written as the video track's
+    Colour element (None: no element)."""
     fr = [f if isinstance(f, tuple) else (i, f) for i, f in enumerate(frames)]
     hdr = _el(0x1A45DFA3, _uint(0x4286, 1) + _uint(0x42F7, 1) + _uint(0x42F2, 4) + _uint(0x42F3, 8) +
               _el(0x4282, b"webm") + _uint(0x4287, 4) + _uint(0x4285, 2))
     info = _el(0x1549A966, _uint(0x2AD7B1, timecode_scale) + _el(0x4D80, b"vp9hip"))
-    video = _el(0xE0, _uint(0xB0, width) + _uint(0xBA, height))
+    video = _el(0xE0, _uint(0xB0, width) + _uint(0xBA, height) + (_webm_colour_element(colour) if colour is not None else b""))
     tracks = [_el(0xAE, _uint(0xD7, 1) + _uint(0x73C5, 1) + _uint(0x83, 1) + _el(0x86, b"V_VP9") + video)]
     if other_track:
         tracks.append(_el(0xAE, _uint(0xD7, 2) + _uint(0x73C5, 2) + _uint(0x83, 2) + _el(0x86, b"A_OPUS")))

@@ -245,6 +245,115 @@ int vp9h_webm_read_header(const uint8_t *buf, size_t size, vp9h_webm_info *info,
     return 0;
 }
 
+/* an EBML float: 4 or 8 bytes, big-endian IEEE; any other length reads as 0 */
+static double rd_float(const uint8_t *b, const Elem *e)
+{
+    const uint64_t v = rd_uint(b, e);
+    if (e->size == 4) {
+        const uint32_t u = (uint32_t) v;
+        float f;
+        memcpy(&f, &u, sizeof(f));
+        return f;
+    }
+    if (e->size == 8) {
+        double d;
+        memcpy(&d, &v, sizeof(d));
+        return d;
+    }
+    return 0;
+}
+
+/* the children of one master element [p, end): each must end inside it */
+static int next_child(const uint8_t *b, size_t size, uint64_t p, uint64_t end, Elem *e)
+{
+    const int r = rd_elem(b, size, p, e);
+    if (r < 0) return r == VP9HIP_EOF ? VP9HIP_EINVALIDDATA : r;
+    if (e->size == UNKNOWN || e->data > end || e->size > end - e->data) return VP9HIP_EINVALIDDATA;
+    return 0;
+}
+
+/* the first child `id` of [p, end), or found->size = UNKNOWN if there is none */
+static int find_child(const uint8_t *b, size_t size, uint64_t p, uint64_t end, uint32_t id, Elem *found)
+{
+    found->size = UNKNOWN;
+    while (p < end) {
+        Elem e;
+        const int r = next_child(b, size, p, end, &e);
+        if (r < 0) return r;
+        if (e.id == id && found->size == UNKNOWN) *found = e;
+        p = e.data + e.size;
+    }
+    return 0;
+}
+
+static int parse_colour(const uint8_t *b, size_t size, const Elem *col, vp9h_webm_colour *out)
+{
+    const uint64_t end = col->data + col->size;
+    int r;
+    out->present = 1;
+    for (uint64_t p = col->data; p < end;) {
+        Elem e;
+        if ((r = next_child(b, size, p, end, &e)) < 0) return r;
+        const int32_t v = (int32_t) (rd_uint(b, &e) & 0x7fffffff);
+        switch (e.id) {
+        case 0x55B1: out->matrix = v; break;
+        case 0x55B2: out->bits_per_channel = v; break;
+        case 0x55B9: out->range = v; break;
+        case 0x55BA: out->transfer = v; break;
+        case 0x55BB: out->primaries = v; break;
+        case 0x55BC: out->max_cll = v; break;
+        case 0x55BD: out->max_fall = v; break;
+        case 0x55D0:
+            for (uint64_t q = e.data; q < e.data + e.size;) {
+                Elem m;
+                if ((r = next_child(b, size, q, e.data + e.size, &m)) < 0) return r;
+                if (m.id == 0x55D9) out->luminance_max = rd_float(b, &m);
+                else if (m.id == 0x55DA) out->luminance_min = rd_float(b, &m);
+                q = m.data + m.size;
+            }
+            break;
+        default: break;
+        }
+        p = e.data + e.size;
+    }
+    return 0;
+}
+
+int vp9h_webm_read_colour(const uint8_t *buf, size_t size, vp9h_webm_colour *out)
+{
+    if (!buf || !out) return VP9HIP_EINVAL;
+    memset(out, 0, sizeof(*out));
+    out->matrix = out->transfer = out->primaries = 2;
+    vp9h_webm_info info;
+    vp9h_webm_cursor cur;
+    int r = vp9h_webm_read_header(buf, size, &info, &cur);   /* the header's checks, and which track */
+    if (r < 0) return r;
+    Elem e;
+    uint64_t p = 0;
+    do {                                                      /* the Segment, as read_header found it */
+        if ((r = rd_elem(buf, size, p, &e)) < 0) return VP9HIP_EINVALIDDATA;
+        p = e.data + (e.id == ID_SEGMENT ? 0 : e.size);
+    } while (e.id != ID_SEGMENT);
+    for (; p < cur.pos; p = e.data + e.size) {                /* its elements before the first Cluster */
+        if ((r = rd_elem(buf, size, p, &e)) < 0 || e.size == UNKNOWN) return VP9HIP_EINVALIDDATA;
+        if (e.id != ID_TRACKS) continue;
+        const uint64_t tend = e.data + e.size;
+        for (uint64_t q = e.data; q < tend;) {
+            Elem te, num, video, col;
+            if ((r = next_child(buf, size, q, tend, &te)) < 0) return r;
+            q = te.data + te.size;
+            if (te.id != ID_TRACKENTRY) continue;
+            if ((r = find_child(buf, size, te.data, q, ID_TRACKNUMBER, &num)) < 0) return r;
+            if (num.size == UNKNOWN || rd_uint(buf, &num) != info.track) continue;
+            if ((r = find_child(buf, size, te.data, q, ID_VIDEO, &video)) < 0) return r;
+            if (video.size == UNKNOWN) return 0;
+            if ((r = find_child(buf, size, video.data, video.data + video.size, 0x55B0u, &col)) < 0) return r;
+            return col.size == UNKNOWN ? 0 : parse_colour(buf, size, &col, out);
+        }
+    }
+    return 0;
+}
+
 /* Xiph / fixed / EBML lacing (matroska_parse_laces): lace sizes, data start */
 static int parse_laces(const uint8_t *b, size_t size, uint64_t p, uint64_t end, int type, vp9h_webm_cursor *c)
 {

@@ -82,4 +82,22 @@ struct CvtCubicArgs {
 // One launch of k_convert_cubic over n <= CVT_MAX_FRAMES frames.
 hipError_t vp9hip_convert_cubic_launch(const CvtCubicArgs &a, int format, int hbd, int n, hipStream_t st);
 
+// Graded output (include/vp9hip.h "Graded output"): the tables in device memory and the matrix,
+// a kernel argument of its own beside the conversion's, which stay as they are. The graded
+// kernels take c.c / c.shift / c.maxv at the source's depth (out_bits = bpp) for every RGB
+// format and c.fscale = float(1.0 / 65535).
+struct CvtGrade {
+    const uint16_t *in_lut;            // 1 << bpp entries
+    const uint16_t *out_lut;           // VP9HIP_GRADE_OUT_LUT entries
+    int32_t m[9];                      // row-major, 14 fractional bits
+};
+
+// The same launches through the graded instantiations; format: one of the three RGB formats.
+hipError_t vp9hip_convert_resample_graded_launch(const CvtResampleArgs &a, const CvtGrade &g, int format, int hbd, int filter,
+                                                 int n, hipStream_t st);
+hipError_t vp9hip_convert_cubic_graded_launch(const CvtCubicArgs &a, const CvtGrade &g, int format, int hbd, int n, hipStream_t st);
+
+// host/vp9h_grade.c: 0, or VP9HIP_EINVAL for a description vp9hip_grade_create refuses.
+extern "C" int vp9hip_grade_check(const vp9hip_grade_desc *g);
+
 #endif

@@ -282,6 +282,35 @@ __global__ __launch_bounds__(256) void k_convert_cubic(const CvtCubicArgs ca)
         cvt_store_px<FMT, HBD>(a, dst, tx0 + lane + 64 * k, oy, s.ow, s.oh, s.cow, s.coh, ctile, Yk[0][k], UV[0][k], UV[1][k]);
 }
 
+// The graded instantiations (include/vp9hip.h "Graded output"; FMT is an RGB format): the same
+// tile with the grade on the stored pixel. A kernel of its own with a second argument, its body
+// repeated here: routing both kernels through one inlined function changed k_convert_cubic's
+// register allocation, and the ungraded instantiations stay instruction for instruction.
+template <int FMT, int HBD>
+__global__ __launch_bounds__(256) void k_convert_cubic_graded(const CvtCubicArgs ca, const CvtGrade g)
+{
+    __shared__ Lds L;
+    const CvtResampleArgs &s = ca.r;
+    const CvtArgs &a = s.c;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH, oy = ty0 + wave;
+    const int z = blockIdx.z;
+    const uint8_t *src = a.src[z];
+    uint8_t *dst = a.dst + (int64_t) z * a.frame_stride;
+
+    Geo gy, gc;
+    frame_geo(s, z, gy, gc);
+    int Yk[1][2], UV[2][2] = {};
+    const uint8_t *const py[1] = { src + a.src_off[0] }, *const puv[2] = { src + a.src_off[1], src + a.src_off[2] };
+    const int fy[1] = { s.fill[0] }, fuv[2] = { s.fill[1], s.fill[2] };
+    resample_row<HBD, 1>(py, a.src_pitch[0], gy, tx0, ty0, oy, L, wave, lane, fy, ca.smax, Yk);
+    const bool ctile = tx0 < s.cow;                    // uniform: semi-planar chroma has fewer tiles
+    if (ctile) resample_row<HBD, 2>(puv, a.src_pitch[1], gc, tx0, ty0, oy, L, wave, lane, fuv, ca.smax, UV);
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+        cvt_store_px<FMT, HBD, 1>(a, dst, tx0 + lane + 64 * k, oy, s.ow, s.oh, s.cow, s.coh, ctile, Yk[0][k], UV[0][k], UV[1][k], g);
+}
+
 typedef void (*KFn)(const CvtCubicArgs);
 // index: format << 1 | hbd
 template <size_t... I>
@@ -291,11 +320,27 @@ constexpr std::array<KFn, sizeof...(I)> kernel_table(std::index_sequence<I...>)
 }
 const std::array<KFn, 8> g_kernels = kernel_table(std::make_index_sequence<8>());
 
+typedef void (*KGFn)(const CvtCubicArgs, const CvtGrade);
+// index: (format - 1) << 1 | hbd
+template <size_t... I>
+constexpr std::array<KGFn, sizeof...(I)> graded_table(std::index_sequence<I...>)
+{
+    return { { k_convert_cubic_graded<(int) (I >> 1) + 1, (int) (I & 1)>... } };
+}
+const std::array<KGFn, 6> g_graded = graded_table(std::make_index_sequence<6>());
+
 }  // namespace
 
 hipError_t vp9hip_convert_cubic_launch(const CvtCubicArgs &a, int format, int hbd, int n, hipStream_t st)
 {
     if (!cvt_launch_ok(format, n)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(g_kernels[format << 1 | !!hbd], cvt_tile_grid(a.r.ow, a.r.oh, n), dim3(64 * TH, 1, 1), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t vp9hip_convert_cubic_graded_launch(const CvtCubicArgs &a, const CvtGrade &g, int format, int hbd, int n, hipStream_t st)
+{
+    if (!cvt_launch_ok(format, n) || format == VP9HIP_OUT_SEMIPLANAR) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(g_graded[(format - 1) << 1 | !!hbd], cvt_tile_grid(a.r.ow, a.r.oh, n), dim3(64 * TH, 1, 1), 0, st, a, g);
     return hipGetLastError();
 }

@@ -103,6 +103,28 @@ __device__ __forceinline__ void cvt_rgb(const CvtArgs &a, int Y, int U, int V, i
     }
 }
 
+// One row of a grade's matrix over the three linear codes, then out_lut: the definition of
+// include/vp9hip.h "Graded output". Each product is one 32 x 32 -> 64 multiply-add (|m| <= 2^16,
+// L < 2^16: the sum passes 32 bits); P >> 4 <= 4095, so the second entry read is at most 4096.
+__device__ __forceinline__ int grade_row(const int32_t *m, const uint16_t *out_lut, int LR, int LG, int LB)
+{
+    int64_t s = (int64_t) m[0] * LR + 8192;
+    s += (int64_t) m[1] * LG;
+    s += (int64_t) m[2] * LB;
+    const int P = (int) min(max(s >> 14, (int64_t) 0), (int64_t) 65535);
+    const int i = P >> 4, f = P & 15;
+    return ((int) out_lut[i] * (16 - f) + (int) out_lut[i + 1] * f + 8) >> 4;
+}
+
+// R, G, B codes at the source's depth (each <= 2^bpp - 1: cvt_rgb clipped them) -> graded codes.
+__device__ __forceinline__ void cvt_grade(const CvtGrade &g, int &R, int &G, int &B)
+{
+    const int LR = g.in_lut[R], LG = g.in_lut[G], LB = g.in_lut[B];
+    R = grade_row(g.m, g.out_lut, LR, LG, LB);
+    G = grade_row(g.m + 3, g.out_lut, LR, LG, LB);
+    B = grade_row(g.m + 6, g.out_lut, LR, LG, LB);
+}
+
 // Output pixel (x, oy) of frame `dst` from the resize kernels: Y, U, V are the samples of an
 // ow x oh RGB output's pixel, or, semi-planar, the luma sample (x, oy) of ow x oh and the chroma
 // pair (x, oy) of cow x coh (ctile: this workgroup's tile has chroma). Stores are per element,
@@ -110,10 +132,13 @@ __device__ __forceinline__ void cvt_rgb(const CvtArgs &a, int Y, int U, int V, i
 // the copy is free (everything here is inlined into a kernel whose arguments they are), and it
 // leaves k_convert_scale's code before this call the same instruction for instruction, where a
 // reference changed its register allocation from the first load on (90 -> 91 VGPRs).
-template <int FMT, int HBD>
+// GR: the graded instantiations (RGB formats only) pass the codes through the grade g, a second
+// by-value argument for the same reason; without GR it is never read and costs nothing.
+template <int FMT, int HBD, int GR = 0>
 __device__ __forceinline__ void cvt_store_px(const CvtArgs a, uint8_t *dst, int x, int oy, int ow, int oh, int cow, int coh,
-                                             bool ctile, int Y, int U, int V)
+                                             bool ctile, int Y, int U, int V, const CvtGrade g = CvtGrade())
 {
+    static_assert(!GR || FMT != VP9HIP_OUT_SEMIPLANAR, "a grade is defined for the RGB formats");
     constexpr int BS = HBD ? 2 : 1;
     if constexpr (FMT == VP9HIP_OUT_SEMIPLANAR) {
         if (x < ow && oy < oh) {
@@ -134,6 +159,7 @@ __device__ __forceinline__ void cvt_store_px(const CvtArgs a, uint8_t *dst, int 
         if (x >= ow || oy >= oh) return;
         int R, G, B;
         cvt_rgb(a, Y, U, V, R, G, B);
+        if constexpr (GR) cvt_grade(g, R, G, B);
         uint8_t *row = dst + (int64_t) oy * a.pitch;
         if constexpr (FMT == VP9HIP_OUT_RGB24) {
             uint8_t *p = row + (int64_t) x * 3;

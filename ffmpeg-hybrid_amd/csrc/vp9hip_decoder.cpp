@@ -381,7 +381,8 @@ extern "C" int vp9hip_decoder_release(vp9hip_decoder *d, int buf)
 // ordered here.
 static int decoder_convert(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n, int format, bool scaled,
                            int out_width, int out_height, void *dst_dev, int64_t pitch, int64_t frame_stride, void *stream,
-                           const vp9hip_resample *rs = nullptr, bool cubic = false)
+                           const vp9hip_resample *rs = nullptr, bool cubic = false, const vp9hip_grade *grade = nullptr,
+                           bool graded = false)
 {
     if (!d || !frames || n <= 0 || !d->configured) return VP9HIP_EINVAL;
     std::vector<int> bufs(n);
@@ -400,6 +401,7 @@ static int decoder_convert(vp9hip_decoder *d, const vp9hip_decoded_frame *frames
     o.full_range = frames[0].full_range;
     o.width = frames[0].width; o.height = frames[0].height;
     o.pitch = pitch; o.frame_stride = frame_stride;
+    if (graded) return vp9hip_convert_frames_graded(d->ctx, bufs.data(), n, &o, rs, grade, dst_dev, stream);
     if (rs && cubic) return vp9hip_convert_frames_bicubic(d->ctx, bufs.data(), n, &o, rs, dst_dev, stream);
     if (rs) return vp9hip_convert_frames_resampled(d->ctx, bufs.data(), n, &o, rs, dst_dev, stream);
     if (scaled) return vp9hip_convert_frames_scaled(d->ctx, bufs.data(), n, &o, out_width, out_height, dst_dev, stream);
@@ -433,6 +435,14 @@ extern "C" int vp9hip_decoder_convert_bicubic(vp9hip_decoder *d, const vp9hip_de
 {
     if (!rs) return VP9HIP_EINVAL;
     return decoder_convert(d, frames, n, format, false, 0, 0, dst_dev, pitch, frame_stride, stream, rs, true);
+}
+
+extern "C" int vp9hip_decoder_convert_graded(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n, int format,
+                                             const vp9hip_resample *rs, const vp9hip_grade *grade, void *dst_dev,
+                                             int64_t pitch, int64_t frame_stride, void *stream)
+{
+    if (!rs || !grade) return VP9HIP_EINVAL;
+    return decoder_convert(d, frames, n, format, false, 0, 0, dst_dev, pitch, frame_stride, stream, rs, false, grade, true);
 }
 
 // The metrics of pairs of received frames (vp9hip_frame_metrics). The frames are complete and

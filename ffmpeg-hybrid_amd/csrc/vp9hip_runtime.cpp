@@ -3128,9 +3128,10 @@ extern "C" int vp9hip_motion_launch_dev(const void *frames_dev, int nframes, int
 //
 // convert_args: the checks and the kernel arguments both entry points share. The output is
 // out_w x out_h (the visible size itself for the unscaled call); *stride is the frame stride
-// in effect.
+// in effect. graded: the RGB codes stay at the source's depth for every RGB format, and the
+// half is of 65535 (include/vp9hip.h "Graded output").
 static int convert_args(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d, int out_w, int out_h,
-                        void *dst_dev, CvtArgs &a, int64_t *stride_out)
+                        void *dst_dev, CvtArgs &a, int64_t *stride_out, bool graded = false)
 {
     if (!c || !bufs || n <= 0 || !d || !dst_dev || c->bufs.empty()) return VP9HIP_EINVAL;
     if (d->width <= 0 || d->height <= 0 || d->width > c->w || d->height > c->h) return VP9HIP_EINVAL;
@@ -3153,14 +3154,14 @@ static int convert_args(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_
     a.cw = (d->width + c->ss_h) >> c->ss_h; a.ch = (d->height + c->ss_v) >> c->ss_v;
     a.msb = c->hb ? 16 - c->bpp : 0;
     if (rgb_out) {
-        const int ob = d->format == VP9HIP_OUT_RGBP_F16 ? c->bpp : 8;
+        const int ob = graded || d->format == VP9HIP_OUT_RGBP_F16 ? c->bpp : 8;
         if (vp9hip_out_coefs(d->colorspace, d->full_range, c->bpp, ob, a.c, &a.shift) < 0) return VP9HIP_EINVAL;
         a.rgb = d->colorspace == 7;
         a.rnd = a.shift > 0 ? 1 << (a.shift - 1) : 0;
         a.yoff = d->full_range ? 0 : 16 << (c->bpp - 8);
         a.coff = 1 << (c->bpp - 1);
         a.maxv = (1 << ob) - 1;
-        a.fscale = (float) (1.0 / a.maxv);
+        a.fscale = (float) (1.0 / (graded ? 65535 : a.maxv));
     }
     *stride_out = stride;
     return 0;
@@ -3313,11 +3314,56 @@ static int64_t bicubic_s_upper(int n_src, int n_out)
     return ((int64_t) 1 << 14) * (m4 / n_out + 1);
 }
 
+// A grade (include/vp9hip.h "Graded output"): both tables in one device allocation, in_lut's
+// 1 << bpp entries, then out_lut's 4097 padded to 4104 (a multiple of 16 bytes), and the matrix,
+// which travels as a kernel argument.
+struct vp9hip_grade {
+    int dev, bpp, out_max;
+    uint16_t *tables;
+    int32_t m[9];
+};
+static const int GRADE_OUT_PAD = 4104;
+
+extern "C" int vp9hip_grade_create(vp9hip_ctx *c, const vp9hip_grade_desc *desc, vp9hip_grade **out)
+{
+    if (!c || !out) return VP9HIP_EINVAL;
+    *out = nullptr;
+    if (const int r = vp9hip_grade_check(desc)) return r;
+    const size_t n_in = (size_t) 1 << desc->bpp;
+    std::vector<uint16_t> host(n_in + GRADE_OUT_PAD, 0);
+    memcpy(host.data(), desc->in_lut, n_in * sizeof(uint16_t));
+    memcpy(host.data() + n_in, desc->out_lut, VP9HIP_GRADE_OUT_LUT * sizeof(uint16_t));
+    hipSetDevice(c->dev);
+    vp9hip_grade *g = new vp9hip_grade();
+    g->dev = c->dev; g->bpp = desc->bpp; g->out_max = desc->out_max;
+    memcpy(g->m, desc->m, sizeof(g->m));
+    if (hipMalloc((void **) &g->tables, host.size() * sizeof(uint16_t)) != hipSuccess) {
+        delete g;
+        return VP9HIP_ENOMEM;
+    }
+    if (hipMemcpy(g->tables, host.data(), host.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(g->tables);
+        delete g;
+        return VP9HIP_EEXTERNAL;
+    }
+    *out = g;
+    return 0;
+}
+
+extern "C" void vp9hip_grade_destroy(vp9hip_grade *g)
+{
+    if (!g) return;
+    hipSetDevice(g->dev);
+    hipFree(g->tables);
+    delete g;
+}
+
 // vp9hip_convert_frames_resampled and vp9hip_convert_frames_bicubic: a filter (VP9HIP_FILTER_*,
 // checked by the entry), a source and a destination rectangle per frame and the fill. Every
-// frame's rectangles are checked before the first launch.
+// frame's rectangles are checked before the first launch. grade: vp9hip_convert_frames_graded's,
+// checked by that entry; the launches are then the graded instantiations'.
 static int convert_resampled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d, const vp9hip_resample *rs,
-                             void *dst_dev, void *stream)
+                             void *dst_dev, void *stream, const vp9hip_grade *grade = nullptr)
 {
     const bool cubic = rs->filter == VP9HIP_FILTER_BICUBIC;
     const int OW = rs->out_width, OH = rs->out_height;
@@ -3325,7 +3371,7 @@ static int convert_resampled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip
     CvtResampleArgs s;
     int64_t stride;
     memset(&s, 0, sizeof(s));
-    const int r = convert_args(c, bufs, n, d, OW, OH, dst_dev, s.c, &stride);
+    const int r = convert_args(c, bufs, n, d, OW, OH, dst_dev, s.c, &stride, grade != nullptr);
     if (r < 0) return r;
     CvtArgs &a = s.c;
     const bool semi = d->format == VP9HIP_OUT_SEMIPLANAR;      // chroma keeps the subsampling; RGB resamples it to the output size
@@ -3366,6 +3412,12 @@ static int convert_resampled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip
     }
     CvtCubicArgs cu;
     cu.smax = (int32_t) maxv;
+    CvtGrade g;
+    memset(&g, 0, sizeof(g));
+    if (grade) {
+        g.in_lut = grade->tables; g.out_lut = grade->tables + ((size_t) 1 << grade->bpp);
+        memcpy(g.m, grade->m, sizeof(g.m));
+    }
     return convert_launches(c, bufs, n, a, dst_dev, stride, stream, [&](int i0, int k, hipStream_t st) {
         for (int i = 0; i < k; i++) {
             s.src_rect[i] = src[i0 + i];
@@ -3373,9 +3425,11 @@ static int convert_resampled(vp9hip_ctx *c, const int *bufs, int n, const vp9hip
         }
         if (cubic) {
             cu.r = s;
-            HIPCHK(vp9hip_convert_cubic_launch(cu, d->format, c->hb, k, st));
+            HIPCHK(grade ? vp9hip_convert_cubic_graded_launch(cu, g, d->format, c->hb, k, st)
+                         : vp9hip_convert_cubic_launch(cu, d->format, c->hb, k, st));
         } else
-            HIPCHK(vp9hip_convert_resample_launch(s, d->format, c->hb, rs->filter, k, st));
+            HIPCHK(grade ? vp9hip_convert_resample_graded_launch(s, g, d->format, c->hb, rs->filter, k, st)
+                         : vp9hip_convert_resample_launch(s, d->format, c->hb, rs->filter, k, st));
         return 0;
     });
 }
@@ -3394,6 +3448,18 @@ extern "C" int vp9hip_convert_frames_bicubic(vp9hip_ctx *c, const int *bufs, int
 {
     if (!rs || rs->filter != VP9HIP_FILTER_BICUBIC) return VP9HIP_EINVAL;
     return convert_resampled(c, bufs, n, d, rs, dst_dev, stream);
+}
+
+// Any of the three filters with a grade on the stored pixel (the graded instantiations of
+// k_convert_resample / k_convert_cubic).
+extern "C" int vp9hip_convert_frames_graded(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_out_desc *d,
+                                            const vp9hip_resample *rs, const vp9hip_grade *grade, void *dst_dev, void *stream)
+{
+    if (!c || !d || !rs || !grade || rs->filter < VP9HIP_FILTER_BOX || rs->filter > VP9HIP_FILTER_BICUBIC) return VP9HIP_EINVAL;
+    if (d->format != VP9HIP_OUT_RGB24 && d->format != VP9HIP_OUT_RGBP_U8 && d->format != VP9HIP_OUT_RGBP_F16) return VP9HIP_EINVAL;
+    if (grade->bpp != c->bpp || grade->dev != c->dev) return VP9HIP_EINVAL;
+    if (grade->out_max != (d->format == VP9HIP_OUT_RGBP_F16 ? 65535 : 255)) return VP9HIP_EINVAL;
+    return convert_resampled(c, bufs, n, d, rs, dst_dev, stream, grade);
 }
 
 extern "C" int vp9hip_flush(vp9hip_ctx *c)

@@ -63,7 +63,10 @@ extern "C" {
  * vp9hip_decoder_acc_warp_scaled) likewise: a new struct and new symbols. The accumulated
  * propagation (VP9HIP_PROP_*, vp9hip_prop_desc, vp9hip_prop_layout, vp9hip_acc_propagate,
  * vp9hip_acc_propagate_host, vp9hip_prop_launch_dev, vp9hip_decoder_acc_propagate) likewise: new
- * enums, a new struct and new symbols. */
+ * enums, a new struct and new symbols. The graded output (vp9hip_grade, vp9hip_grade_desc,
+ * vp9hip_grade_create, vp9hip_grade_destroy, vp9hip_convert_frames_graded,
+ * vp9hip_decoder_convert_graded, vp9hip_grade_host) and the WebM colour description
+ * (vp9h_webm_colour, vp9h_webm_read_colour) likewise: new structs and new symbols. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -501,6 +504,70 @@ int  vp9hip_convert_frames_bicubic(vp9hip_ctx *ctx, const int *bufs, int n, cons
  * out of range, cap < 0. */
 int  vp9hip_bicubic_weights(int n_src, int n_out, int o, int *first, int32_t *weights, int cap,
                             int64_t *sum, int64_t *abs_sum);
+
+/*
+ * Graded output: a colour pipeline (transfer curve -> 3x3 matrix -> transfer curve / tone map)
+ * on the stored pixel of the RGB formats, in the same launch as the crop, the resize and the
+ * matrix (DESIGN.md "Graded output"). Integer and exact: the device does LUT -> integer 3x3 ->
+ * LUT on integer codes with one stated rounding per stage; whatever float mathematics made the
+ * tables (PQ, HLG, sRGB, tone curves, primaries) ran once on the host.
+ *
+ * A grade is in_lut (2^bpp entries of u16), m[3][3] (int32, 14 fractional bits, |m| <= 2^16)
+ * and out_lut (4097 entries of u16, each <= out_max); out_max is 255 for RGB24 / RGBP_U8 and
+ * 65535 for RGBP_F16. Defined for the three RGB formats only.
+ *
+ * For every output pixel take the R, G, B codes the same call's arithmetic gives at the
+ * source's depth, vp9hip_out_coefs(..., out_bits = bpp): shift 14, clip to 2^bpp - 1, for the u8
+ * formats too (the reduction to 8 bits moves into out_lut); colour space 7 passes its planes
+ * through as without a grade. Then, for c = R, G, B and each output row r of m:
+ *   L_c = in_lut[code_c]
+ *   P_r = clip((m[r][0] L_R + m[r][1] L_G + m[r][2] L_B + 8192) >> 14, 0, 65535)
+ *                                      64-bit sum, arithmetic shift (floor)
+ *   i = P_r >> 4, f = P_r & 15
+ *   v_r = (out_lut[i] (16 - f) + out_lut[i + 1] f + 8) >> 4           i + 1 <= 4096
+ * v_r is stored as the u8, or as the half of v_r * float(1.0 / 65535) with the half format's two
+ * roundings. Fill pixels (dst_rects) are fill[0..2] through the same arithmetic, matrix and
+ * grade included. Nothing before the codes changes: the filters, rectangles, bounds and layouts
+ * are those of vp9hip_convert_frames_resampled / _bicubic.
+ *
+ * The property that needs no tables to check: with in_lut[c] = c << (16 - bpp), m = 16384 I,
+ * out_lut[i] = min(16 i, 65535) and RGBP_F16, v = c << (16 - bpp) exactly.
+ * The limit: linear light is indexed at 12 bits and interpolated, so a curve with an infinite
+ * slope at 0 (a pure power law) is off by up to about 1.6 u8 codes in its first segment; sRGB
+ * and BT.709 have a linear toe and are not affected. Per-channel curves only: operators that
+ * need the three channels at once (BT.2390 in ICtCp, max-RGB hue-preserving maps) are not
+ * expressible.
+ *
+ * vp9hip_grade_create validates the desc (bpp 8 / 10 / 12, out_max 255 or 65535, every out_lut
+ * entry <= out_max, every |m| <= 2^16, no NULL pointer: otherwise VP9HIP_EINVAL) and uploads the
+ * tables to device memory once; it may synchronise. vp9hip_grade_destroy frees them (NULL: no-op)
+ * and must not run while a conversion that uses the grade is in flight.
+ *
+ * vp9hip_convert_frames_graded: rs is the vp9hip_resample of the ungraded entries, any of the
+ * three filters (box and triangle take the resampling kernel, bicubic the cubic one); the
+ * visible size without a resize is the box filter with out_width == d->width, out_height ==
+ * d->height, which is the identity. One launch per 32 frames, returns without waiting. All
+ * checks of the ungraded entries apply, plus VP9HIP_EINVAL for SEMIPLANAR, a NULL grade, a
+ * grade whose bpp is not the configured one, or whose out_max is not the format's. All checks
+ * run before the first launch: a refused call writes nothing.
+ */
+typedef struct vp9hip_grade vp9hip_grade;
+typedef struct vp9hip_grade_desc {
+    int32_t bpp;                    /* 8, 10 or 12: in_lut has 1 << bpp entries */
+    int32_t out_max;                /* 255 (RGB24, RGBP_U8) or 65535 (RGBP_F16) */
+    const uint16_t *in_lut;
+    const int32_t *m;               /* 9 coefficients, row-major: m[3 r + c] */
+    const uint16_t *out_lut;        /* 4097 entries */
+} vp9hip_grade_desc;
+#define VP9HIP_GRADE_OUT_LUT 4097
+int  vp9hip_grade_create(vp9hip_ctx *ctx, const vp9hip_grade_desc *desc, vp9hip_grade **out);
+void vp9hip_grade_destroy(vp9hip_grade *g);
+int  vp9hip_convert_frames_graded(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip_out_desc *d,
+                                  const vp9hip_resample *rs, const vp9hip_grade *grade, void *dst_dev, void *stream);
+/* Host only: the C statement of the three stages. rgb_codes: n_pixels interleaved R, G, B codes
+ * (each < 2^bpp); v: n_pixels interleaved results. VP9HIP_EINVAL: what vp9hip_grade_create
+ * refuses, a NULL array, n_pixels < 0, or a code >= 2^bpp (nothing is written then). */
+int  vp9hip_grade_host(const vp9hip_grade_desc *desc, const uint16_t *rgb_codes, int64_t n_pixels, uint16_t *v);
 
 /* ---- motion export: the stream's own motion field and block modes as device tensors ----
  * The second product of the decode besides the pixels (FFmpeg's AV_FRAME_DATA_MOTION_VECTORS /
@@ -1479,6 +1546,27 @@ int  vp9h_webm_read_header(const uint8_t *buf, size_t size, vp9h_webm_info *info
  * Returns 0, VP9HIP_EOF at the end, or AVERROR_INVALIDDATA. */
 int  vp9h_webm_read_frame(const uint8_t *buf, size_t size, vp9h_webm_cursor *cur, const uint8_t **data,
                           uint32_t *frame_size, int64_t *pts, int *keyframe);
+/* The Colour element (0x55B0) of the first VP9 video track: what the VP9 header does not carry
+ * (transfer function, primaries, mastering levels) and what it does (matrix, range). The codes
+ * are those of ISO/IEC 23091-2 as Matroska stores them (transfer 16 = PQ, 18 = HLG, 1 = BT.709,
+ * 13 = sRGB; primaries 9 = BT.2020, 1 = BT.709, 5 = BT.601 625, 6 = BT.601 525; range 1 =
+ * limited, 2 = full). An absent field is 2 ("unspecified") for matrix, transfer and primaries
+ * and 0 for the others; an absent element is not an error and leaves present = 0. */
+typedef struct vp9h_webm_colour {
+    int32_t present;               /* the track has a Colour element                         */
+    int32_t matrix;                /* MatrixCoefficients 0x55B1                              */
+    int32_t bits_per_channel;      /* BitsPerChannel 0x55B2                                  */
+    int32_t range;                 /* Range 0x55B9                                           */
+    int32_t transfer;              /* TransferCharacteristics 0x55BA                         */
+    int32_t primaries;             /* Primaries 0x55BB                                       */
+    int32_t max_cll, max_fall;     /* MaxCLL 0x55BC, MaxFALL 0x55BD, cd/m^2                  */
+    double  luminance_max;         /* MasteringMetadata (0x55D0) LuminanceMax 0x55D9, cd/m^2 */
+    double  luminance_min;         /* LuminanceMin 0x55DA                                    */
+} vp9h_webm_colour;
+/* Reads it from the file's header (up to the first Cluster). Returns 0, VP9HIP_EINVAL for a
+ * NULL argument, or AVERROR_INVALIDDATA as vp9h_webm_read_header does (no V_VP9 track, a
+ * truncated or oversize element); never reads past size. */
+int  vp9h_webm_read_colour(const uint8_t *buf, size_t size, vp9h_webm_colour *out);
 
 /* ---- bitstream decoder: avcodec_send_packet / avcodec_receive_frame for VP9 -------------
  * The decode loop of vp9_decode_frame (vp9.c:1558-1865) over the host parse (vp9h_stream)
@@ -1538,6 +1626,11 @@ int  vp9hip_decoder_convert_resampled(vp9hip_decoder *dec, const vp9hip_decoded_
 int  vp9hip_decoder_convert_bicubic(vp9hip_decoder *dec, const vp9hip_decoded_frame *frames, int n, int format,
                                     const vp9hip_resample *rs, void *dst_dev, int64_t pitch,
                                     int64_t frame_stride, void *stream);
+/* The same through vp9hip_convert_frames_graded (any filter of rs; a grade made with
+ * vp9hip_grade_create on vp9hip_decoder_context), with the stream's matrix and range. */
+int  vp9hip_decoder_convert_graded(vp9hip_decoder *dec, const vp9hip_decoded_frame *frames, int n, int format,
+                                   const vp9hip_resample *rs, const vp9hip_grade *grade, void *dst_dev,
+                                   int64_t pitch, int64_t frame_stride, void *stream);
 /* Motion export (see vp9hip_set_export): flags = VP9HIP_EXPORT_MOTION makes every decoded frame,
  * hidden ones included, leave its motion field beside its pixels. Call before the first
  * vp9hip_decoder_send_packet; VP9HIP_EINVAL afterwards. The flags reach the context before it is
