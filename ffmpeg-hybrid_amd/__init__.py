@@ -169,7 +169,8 @@ ABI_SYMBOLS = ["vp9hip_open", "vp9hip_close", "vp9hip_configure", "vp9hip_submit
                "vp9hip_prop_layout", "vp9hip_acc_propagate", "vp9hip_acc_propagate_host", "vp9hip_prop_launch_dev",
                "vp9hip_decoder_acc_propagate",
                "vp9hip_grade_create", "vp9hip_grade_destroy", "vp9hip_convert_frames_graded",
-               "vp9hip_decoder_convert_graded", "vp9hip_grade_host", "vp9h_webm_read_colour"]
+               "vp9hip_decoder_convert_graded", "vp9hip_grade_host", "vp9h_webm_read_colour",
+               "vp9hip_frame_histograms", "vp9hip_frame_histograms_host", "vp9hip_decoder_histograms"]
 
 
 def lib():
@@ -385,6 +386,13 @@ def lib():
                                            [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p]
     L.vp9hip_decoder_metrics.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.POINTER(DecodedFrameInfo), ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    # frame histograms
+    L.vp9hip_frame_histograms.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(HistDesc),
+                                          ctypes.c_void_p, ctypes.c_void_p]
+    L.vp9hip_frame_histograms_host.argtypes = [vp3, ctypes.POINTER(ctypes.c_ssize_t * 3)] + [ctypes.c_int] * 3 + \
+                                              [ctypes.POINTER(HistDesc), ctypes.POINTER(Rect), ctypes.c_void_p]
+    L.vp9hip_decoder_histograms.argtypes = [vp, ctypes.POINTER(DecodedFrameInfo), ctypes.c_int, ctypes.POINTER(HistDesc),
+                                            ctypes.c_void_p, ctypes.c_void_p]
     # accumulated residual
     L.vp9hip_warp_layout.restype = ctypes.c_int64
     L.vp9hip_warp_layout.argtypes = [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int64 * 3)]
@@ -513,6 +521,13 @@ class Resample(ctypes.Structure):
                 ("src_rects", ctypes.POINTER(Rect)), ("dst_rects", ctypes.POINTER(Rect)), ("fill", ctypes.c_int32 * 3)]
 
 
+class HistDesc(ctypes.Structure):
+    """vp9hip_hist_desc: what is counted, the bins, the colour of RGBM, the size and the rectangles (or NULL)."""
+    _fields_ = [("what", ctypes.c_int32), ("bins_log2", ctypes.c_int32), ("colorspace", ctypes.c_int32),
+                ("full_range", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("rects", ctypes.POINTER(Rect))]
+
+
 class GradeDesc(ctypes.Structure):
     """vp9hip_grade_desc: the depth, the output's largest code and the three host tables."""
     _fields_ = [("bpp", ctypes.c_int32), ("out_max", ctypes.c_int32), ("in_lut", ctypes.c_void_p), ("m", ctypes.c_void_p),
@@ -528,6 +543,9 @@ MVT_FORMATS = {"i16": 0, "f16": 1}
 MVT_SOURCES = {"coded": 0, "acc": 1}
 # VP9HIP_FILTER_*: the names of their filter argument
 FILTERS = {"box": 0, "triangle": 1}
+# VP9HIP_HIST_*: the names histograms() takes for what, and their channels
+HIST_MODES = {"planes": 0, "rgbm": 1}
+HIST_CHANNELS = {"planes": ("y", "u", "v"), "rgbm": ("r", "g", "b", "m")}
 # VP9HIP_FILTER_BICUBIC, filter="bicubic": entries of its own (vp9hip_convert_frames_bicubic)
 FILTER_BICUBIC = 2
 
@@ -1400,6 +1418,108 @@ def frame_metrics_host(planes_a, planes_b, width, height, bpp, ss_h=1, ss_v=1, c
                                            ctypes.byref(bls) if pb is not None else None, int(width), int(height), int(bpp),
                                            int(ss_h), int(ss_v), out.ctypes.data, cmap.ctypes.data if cells else None))
     return (out, cmap) if cells else out
+
+
+def _hist_desc(fn, what, bins, colorspace, full_range, width, height, rects, n):
+    """(HistDesc, channels, bins) of histograms()' arguments; the rectangle array is kept alive
+    by the desc's _keep."""
+    if what not in HIST_MODES:
+        raise ValueError("%s: what is %s" % (fn, " or ".join(repr(k) for k in HIST_MODES)))
+    bins = int(bins)
+    if bins < 1 or bins & (bins - 1):
+        raise ValueError("%s: bins is a power of two" % fn)
+    d = HistDesc(HIST_MODES[what], bins.bit_length() - 1, int(colorspace), int(bool(full_range)), int(width), int(height), None)
+    if rects is not None:
+        d._keep = _rect_array("rects", rects, n)
+        d.rects = ctypes.cast(d._keep, ctypes.POINTER(Rect))
+    return d, len(HIST_CHANNELS[what]), bins
+
+
+def histograms_host(planes, width, height, bpp, ss_h=1, ss_v=1, what="planes", bins=256, colorspace=2, full_range=False,
+                    rect=None):
+    """The histograms of one host frame, vp9hip_frame_histograms_host, the C statement of the
+    definition in include/vp9hip.h "frame histograms": an int32 (C, B) array, channels Y, U, V
+    (what="planes") or R, G, B, max(R, G, B) at the source's depth (what="rgbm") by `bins` bins,
+    a power of two in 16 .. 2^bpp; a code's bin is min(c, 2^bpp - 1) >> (bpp - log2 bins). Over
+    the luma rectangle rect = (x, y, w, h) inside width x height (default: all of it) and the
+    chroma it covers. planes are three 2-D arrays, uint8 at 8 bits, else uint16 (rows may be
+    strided)."""
+    fn = "histograms_host"
+    dt = np.uint8 if bpp == 8 else np.uint16
+    d, C, B = _hist_desc(fn, what, bins, colorspace, full_range, width, height, None, 1)
+    sane = 1 <= width <= 16384 and 1 <= height <= 16384 and ss_h in (0, 1) and ss_v in (0, 1)
+    pl = []
+    for p, a in enumerate(planes):
+        a = np.asarray(a)
+        if a.ndim != 2 or a.dtype != dt:
+            raise ValueError("%s: planes must be 2-D %s arrays" % (fn, np.dtype(dt).name))
+        if a.strides[1] != a.itemsize or a.strides[0] < 0:
+            a = np.ascontiguousarray(a)
+        if sane:                                      # what the library refuses it does not read
+            pw, ph = (width, height) if p == 0 else ((width + ss_h) >> ss_h, (height + ss_v) >> ss_v)
+            if a.shape[0] < ph or a.shape[1] < pw:
+                raise ValueError("%s: plane %d is smaller than %d x %d" % (fn, p, pw, ph))
+        pl.append(a)
+    if len(pl) != 3:
+        raise ValueError("%s: three planes a frame" % fn)
+    out = np.full((C, min(B, 4096)), -0x5a5a, np.int32)
+    ptrs, ls = _plane_ptrs(pl)
+    r = Rect(*(int(v) for v in rect)) if rect is not None else None
+    _check("vp9hip_frame_histograms_host",
+           lib().vp9hip_frame_histograms_host(ctypes.byref(ptrs), ctypes.byref(ls), int(bpp), int(ss_h), int(ss_v),
+                                              ctypes.byref(d), ctypes.byref(r) if r is not None else None, out.ctypes.data))
+    return out
+
+
+def hist_percentile(h, num, den):
+    """The smallest bin k with den * sum(h[..., :k + 1]) >= num * sum(h[...]), for every leading
+    index of h (a tensor or array whose last axis is bins): int64, in integer arithmetic. num = 0
+    gives bin 0 if h[..., 0] > 0, else the first non-zero bin (0 for an all-zero row); num = den
+    gives the last non-zero bin."""
+    num, den = int(num), int(den)
+    if den < 1 or not 0 <= num <= den:
+        raise ValueError("hist_percentile: 0 <= num <= den, den >= 1")
+    if hasattr(h, "cumsum") and not isinstance(h, np.ndarray):       # a torch tensor: stays on its device
+        import torch
+        c = h.to(torch.int64).cumsum(-1)
+        ok = (den * c >= num * c[..., -1:]) & (c > 0)
+        first = ok.to(torch.int64).argmax(-1)
+        return torch.where(ok.any(-1), first, torch.zeros_like(first))
+    c = np.cumsum(np.asarray(h).astype(np.int64), axis=-1)
+    ok = (den * c >= num * c[..., -1:]) & (c > 0)
+    return np.where(ok.any(-1), ok.argmax(-1), 0).astype(np.int64)
+
+
+def light_levels(h_m, bpp, transfer, peak_nits=10000, white_nits=203, percentiles=((999, 1000),)):
+    """One frame's contribution to MaxCLL / MaxFALL from its max(R, G, B) histogram: h_m is the M
+    channel of histograms(what="rgbm", bins=1 << bpp) as host data, (B,) or (N, B), one bin per
+    code (fewer bins are a ValueError). A dict of float64 values, scalars or (N,):
+      "max_nits"  the display light (_eotf_nits of code / (2^bpp - 1): transfer "pq", "hlg",
+                  "bt709", "srgb", "linear"; peak_nits scales HLG, white_nits the SDR transfers)
+                  of the highest non-zero code,
+      "avg_nits"  sum h[c] nits(c) / sum h,
+      "p<num>/<den>" for each (num, den) of percentiles: nits of hist_percentile(h_m, num, den).
+    An empty histogram gives 0 for all three. The intended use, a tone map keyed to the content
+    and not to the mastering display:
+        levels = light_levels(dev.histograms(bufs, "rgbm", bins=1 << bpp)[0, 3].cpu().numpy(), bpp, "pq")
+        g = grade_for(colour, bpp, fmt, peak_nits=max(levels["p999/1000"], white_nits))"""
+    h = np.asarray(h_m)
+    bpp = int(bpp)
+    if bpp not in (8, 10, 12):
+        raise ValueError("light_levels: bpp is 8, 10 or 12")
+    if h.ndim not in (1, 2) or h.shape[-1] != 1 << bpp:
+        raise ValueError("light_levels: h_m is (B,) or (N, B) with one bin per code, B = %d" % (1 << bpp))
+    h = h.astype(np.int64)
+    nits = _eotf_nits(transfer, np.arange(1 << bpp, dtype=np.float64) / ((1 << bpp) - 1), float(peak_nits), float(white_nits))
+    nits = np.asarray(nits, np.float64)
+    total = h.sum(-1)
+    some = total > 0
+    top = hist_percentile(h, 1, 1)
+    out = {"max_nits": np.where(some, nits[top], 0.),
+           "avg_nits": (h * nits).sum(-1) / np.where(some, total, 1)}
+    for num, den in percentiles:
+        out["p%d/%d" % (num, den)] = np.where(some, nits[hist_percentile(h, num, den)], 0.)
+    return {k: (float(v) if h.ndim == 1 else v) for k, v in out.items()}
 
 
 # VP9HIP_WARP_*: the names acc_warp takes for interp and output
@@ -2316,6 +2436,55 @@ class Device:
             _check("vp9hip_frame_metrics", _enqueue_for_torch(main.value, stream, call))
         return (res, cmap) if cells else res
 
+    @staticmethod
+    def _hist_out(n, C, B, out):
+        """The (N, C, B) int32 destination of a histograms call; `out` is a contiguous int32 cuda
+        tensor of at least N * C * B elements, or None."""
+        import torch
+        need = max(n, 0) * C * min(B, 4096)
+        if out is None:
+            out = torch.empty(max(need, 1), dtype=torch.int32, device="cuda")
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and out.is_contiguous()
+                  and out.numel() >= need):
+            raise ValueError("histograms: out must be a contiguous int32 cuda tensor of at least %d elements" % need)
+        return out.view(-1)[:need].view(max(n, 0), C, min(B, 4096))
+
+    def histograms(self, bufs, what="planes", bins=256, colorspace=2, full_range=False, size=None, rects=None, out=None,
+                   stream=None):
+        """The histograms of the device buffers bufs on the GPU, one launch per 32 frames
+        (vp9hip_frame_histograms, the definition in include/vp9hip.h "frame histograms"): an
+        (N, C, B) int32 cuda tensor, channels Y, U, V (what="planes") or R, G, B, max(R, G, B) of
+        the conversion's codes at the source's depth (what="rgbm", with colorspace / full_range
+        as for convert) by B = `bins` bins, a power of two in 16 .. 2^bpp (one bin per code at
+        2^bpp). Over the top-left `size` = (width, height) luma samples (default: the configured
+        size), or over `rects`: one luma rectangle (x, y, w, h) inside it for every frame, or one
+        per frame, x / y multiples of the chroma subsampling. Any buffers in any order, repeats
+        allowed. `out` is a contiguous int32 cuda tensor to write the N * C * B counts into (else
+        one is allocated). The scene-cut distance of consecutive frames is
+        (h[1:] - h[:-1]).abs().sum((1, 2)); hist_percentile and light_levels read the tables.
+        Runs in the order of torch's current stream (or on `stream`, a hipStream_t handle; see
+        _enqueue_for_torch) and does not wait: order it after the frames' producer (sync(), or
+        vp9hip_slot_stream_wait), as for convert. Needs torch imported before the library was
+        loaded (see _torch_first)."""
+        if not _torch_first:
+            raise Vp9HipUnavailable("histograms: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        bufs = [int(b) for b in bufs]
+        n = len(bufs)
+        w, h = (int(x) for x in size) if size is not None else (self.w, self.h)
+        d, C, B = _hist_desc("histograms", what, bins, colorspace, full_range, w, h, rects, n)
+        res = self._hist_out(n, C, B, out)
+        arr = (ctypes.c_int * max(n, 1))(*bufs)
+        call = lambda st: lib().vp9hip_frame_histograms(self._c, arr, n, ctypes.byref(d), res.data_ptr(), st)
+        main = ctypes.c_void_p()
+        # an unconfigured context has no buffer to ask for its stream: the library refuses the call itself
+        if lib().vp9hip_frame_device(self._c, 0, (ctypes.c_void_p * 3)(), (ctypes.c_ssize_t * 3)(), None, None,
+                                     ctypes.byref(main)):
+            _check("vp9hip_frame_histograms", call(stream))
+        else:
+            _check("vp9hip_frame_histograms", _enqueue_for_torch(main.value, stream, call))
+        return res
+
     def acc_warp(self, bufs, root_bufs, output="residual", interp="nearest", mask=False, size=None, out=None, stream=None):
         """The accumulated residual of the pairs (bufs[i], root_bufs[i]) of device buffers on the GPU
         (vp9hip_acc_warp, the definition in include/vp9hip.h "accumulated residual"): frame
@@ -2749,6 +2918,32 @@ class Decoder:
         _check("vp9hip_decoder_metrics", _enqueue_for_torch(main.value, None, call))
         torch.cuda.current_stream().synchronize()
         return (res, cmap) if cells else res
+
+    def histograms(self, infos, what="planes", bins=256, rects=None, out=None):
+        """The histograms of frames of receive_frame(download=False) (their DecodedFrameInfos, all
+        of one size, depth, subsampling and, for what="rgbm", colour space and range, all still
+        held), as Device.histograms returns them (vp9hip_decoder_histograms): over the frames' own
+        size, or `rects` inside it, with the frames' own colour space and range (unknown: BT.709).
+        Runs on torch's current stream and waits for it; like metrics it releases nothing."""
+        if not _torch_first:
+            raise Vp9HipUnavailable("histograms: import torch before ffmpeg-hybrid_amd loads libvp9hip.so "
+                                    "(both use libamdhip64; torch's device init needs its own runtime loaded first)")
+        import torch
+        infos = list(infos)
+        n = len(infos)
+        if not n:
+            raise Vp9HipError("vp9hip_decoder_histograms", EINVAL)
+        f = infos[0]
+        d, C, B = _hist_desc("histograms", what, bins, -1, False, f.width, f.height, rects, n)
+        res = Device._hist_out(n, C, B, out)
+        arr = (DecodedFrameInfo * n)(*infos)
+        main = ctypes.c_void_p()
+        _check("vp9hip_frame_device", lib().vp9hip_frame_device(self.context(), 0, (ctypes.c_void_p * 3)(),
+                                                                (ctypes.c_ssize_t * 3)(), None, None, ctypes.byref(main)))
+        call = lambda st: lib().vp9hip_decoder_histograms(self._d, arr, n, ctypes.byref(d), res.data_ptr(), st)
+        _check("vp9hip_decoder_histograms", _enqueue_for_torch(main.value, None, call))
+        torch.cuda.current_stream().synchronize()
+        return res
 
     def acc_warp(self, infos, root_infos, output="residual", interp="nearest", mask=False):
         """The accumulated residual of the pairs (infos[i], root_infos[i]) of frames of

@@ -466,6 +466,32 @@ extern "C" int vp9hip_decoder_metrics(vp9hip_decoder *d, const vp9hip_decoded_fr
                                 cells_dev, stream);
 }
 
+// The histograms of received frames (vp9hip_frame_histograms), under the metrics' rules: complete
+// frames that stay the caller's, nothing ordered and nothing released; the size is the frames' own.
+extern "C" int vp9hip_decoder_histograms(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n,
+                                         const vp9hip_hist_desc *desc, int32_t *out_dev, void *stream)
+{
+    if (!d || !frames || n <= 0 || !desc || !d->configured) return VP9HIP_EINVAL;
+    std::vector<int> bufs(n);
+    const vp9hip_decoded_frame &f0 = frames[0];
+    const bool own = desc->colorspace < 0;
+    for (int i = 0; i < n; i++) {
+        const vp9hip_decoded_frame &f = frames[i];
+        if (f.buf < 0 || f.buf >= d->nbufs || d->pins[f.buf] <= 0) return VP9HIP_EINVAL;   // not held by the caller
+        if (f.width != f0.width || f.height != f0.height || f.bpp != f0.bpp || f.ss_h != f0.ss_h || f.ss_v != f0.ss_v)
+            return VP9HIP_EINVAL;
+        if (own && (f.colorspace != f0.colorspace || f.full_range != f0.full_range)) return VP9HIP_EINVAL;
+        bufs[i] = f.buf;
+    }
+    vp9hip_hist_desc o = *desc;
+    o.width = f0.width; o.height = f0.height;
+    if (own) {
+        o.colorspace = f0.colorspace == 0 || f0.colorspace == 6 ? 2 : f0.colorspace;   // unknown / reserved: BT.709
+        o.full_range = f0.full_range;
+    }
+    return vp9hip_frame_histograms(d->ctx, bufs.data(), n, &o, out_dev, stream);
+}
+
 // Motion export: the flags go to the context before it is configured (the first keyframe).
 extern "C" int vp9hip_decoder_set_export(vp9hip_decoder *d, int flags)
 {

@@ -46,6 +46,7 @@
 #include "vp9hip_motion.h"
 #include "vp9hip_mvacc.h"
 #include "vp9hip_residual.h"
+#include "vp9hip_hist.h"
 #include "vp9hip_metrics.h"
 #include "vp9hip_warp.h"
 #include "vp9hip_warp_scale.h"
@@ -3240,6 +3241,57 @@ extern "C" int vp9hip_frame_metrics(vp9hip_ctx *c, const int *bufs_a, const int 
         a.out = (unsigned long long *) out_dev + (size_t) i0 * 3 * VP9HIP_METRIC_FIELDS;
         a.cells = cells_dev ? cells_dev + (size_t) i0 * a.mh * a.mw : nullptr;
         HIPCHK(vp9hip_metrics_launch(a, c->hb, k, st));
+    }
+    return 0;
+}
+
+// Frame histograms (include/vp9hip.h "frame histograms"; k_hist in vp9hip_hist.hip): the frames
+// bufs[i] into out_dev, enqueued on `stream` (NULL: the current slot's main stream), under the
+// metrics' contract: everything is validated before the first launch, and the buffers' pointers
+// and the rectangles travel as kernel arguments, HIST_MAX_FRAMES per launch.
+extern "C" int vp9hip_frame_histograms(vp9hip_ctx *c, const int *bufs, int n, const vp9hip_hist_desc *d, int32_t *out_dev,
+                                       void *stream)
+{
+    if (!c || c->bufs.empty() || !bufs || n <= 0 || !d || !out_dev) return VP9HIP_EINVAL;
+    if (d->what != VP9HIP_HIST_PLANES && d->what != VP9HIP_HIST_RGBM) return VP9HIP_EINVAL;
+    if (d->bins_log2 < 4 || d->bins_log2 > c->bpp) return VP9HIP_EINVAL;
+    if (d->width < 1 || d->height < 1 || d->width > c->w || d->height > c->h) return VP9HIP_EINVAL;
+    if ((uintptr_t) out_dev & 3) return VP9HIP_EINVAL;
+    HistArgs a;
+    memset(&a, 0, sizeof(a));
+    if (d->what == VP9HIP_HIST_RGBM) {
+        if (vp9hip_out_coefs(d->colorspace, d->full_range, c->bpp, c->bpp, a.c, &a.shift) < 0) return VP9HIP_EINVAL;
+        a.rgb = d->colorspace == 7;
+        a.rnd = a.shift > 0 ? 1 << (a.shift - 1) : 0;
+        a.yoff = d->full_range ? 0 : 16 << (c->bpp - 8);
+        a.coff = 1 << (c->bpp - 1);
+    }
+    const vp9hip_rect whole = { 0, 0, d->width, d->height };
+    for (int i = 0; i < n; i++) {
+        if (bufs[i] < 0 || bufs[i] >= (int) c->bufs.size()) return VP9HIP_EINVAL;
+        const vp9hip_rect &r = d->rects ? d->rects[i] : whole;
+        if (r.w < 1 || r.h < 1 || r.x < 0 || r.y < 0 || r.x > d->width - r.w || r.y > d->height - r.h) return VP9HIP_EINVAL;
+        if ((r.x & ((1 << c->ss_h) - 1)) || (r.y & ((1 << c->ss_v) - 1))) return VP9HIP_EINVAL;
+    }
+    void *pl[3];
+    ptrdiff_t ls[3];
+    if (const int r = vp9hip_frame_device(c, bufs[0], pl, ls, nullptr, nullptr, nullptr)) return r;
+    for (int p = 0; p < 3; p++) a.off[p] = (int64_t) ((uint8_t *) pl[p] - (uint8_t *) pl[0]);
+    a.pitch[0] = (int32_t) ls[0]; a.pitch[1] = (int32_t) ls[1];
+    a.ss_h = c->ss_h; a.ss_v = c->ss_v;
+    a.what = d->what; a.bins_log2 = d->bins_log2; a.bpp = c->bpp;
+    const size_t per = (size_t) (d->what == VP9HIP_HIST_RGBM ? 4 : 3) << d->bins_log2;   // counts a frame
+    hipSetDevice(c->dev);
+    hipStream_t st = stream ? (hipStream_t) stream : c->st;
+    for (int i0 = 0; i0 < n; i0 += HIST_MAX_FRAMES) {
+        const int k = std::min(n - i0, HIST_MAX_FRAMES);
+        for (int i = 0; i < k; i++) {
+            vp9hip_frame_device(c, bufs[i0 + i], pl, ls, nullptr, nullptr, nullptr);
+            a.src[i] = (const uint8_t *) pl[0];
+            a.rect[i] = d->rects ? d->rects[i0 + i] : whole;
+        }
+        a.out = out_dev + (size_t) i0 * per;
+        HIPCHK(vp9hip_hist_launch(a, c->hb, k, st));
     }
     return 0;
 }

@@ -66,7 +66,10 @@ extern "C" {
  * enums, a new struct and new symbols. The graded output (vp9hip_grade, vp9hip_grade_desc,
  * vp9hip_grade_create, vp9hip_grade_destroy, vp9hip_convert_frames_graded,
  * vp9hip_decoder_convert_graded, vp9hip_grade_host) and the WebM colour description
- * (vp9h_webm_colour, vp9h_webm_read_colour) likewise: new structs and new symbols. */
+ * (vp9h_webm_colour, vp9h_webm_read_colour) likewise: new structs and new symbols. The frame
+ * histograms (VP9HIP_HIST_*, vp9hip_hist_desc, vp9hip_frame_histograms,
+ * vp9hip_frame_histograms_host, vp9hip_decoder_histograms) likewise: a new enum, a new struct and
+ * new symbols. */
 #define VP9HIP_ABI_VERSION 5
 
 /* FFmpeg AVERROR values used by the boundary (libavutil/error.h). */
@@ -950,7 +953,7 @@ int  vp9hip_motion_scaled_host(const int16_t *mv, const uint8_t *info, const vp9
  * cells[i][cy][cx] = sum |a - b| over the visible luma samples of the 16 x 16 cell (a partial
  * cell sums what is visible), int32_t (at most 256 * 65535 < 2^24), tight (n, MH, MW). The
  * cells of a pair sum to its plane 0 SAD. Not offered: other cell sizes (pool the map), chroma
- * maps, rectangles other than the top-left crop, SSIM / VMAF, histograms. */
+ * maps, rectangles other than the top-left crop, SSIM / VMAF. */
 enum { VP9HIP_METRIC_SUM_A,    /* sum a                                                   */
        VP9HIP_METRIC_SUM_B,    /* sum b                                                   */
        VP9HIP_METRIC_SUMSQ_A,  /* sum a^2                                                 */
@@ -983,6 +986,71 @@ int  vp9hip_frame_metrics_host(const void *const a[3], const ptrdiff_t linesize_
                                const void *const b[3], const ptrdiff_t linesize_b[3],
                                int width, int height, int bpp, int ss_h, int ss_v,
                                int64_t out[24], int32_t *cells);
+
+/* ---- frame histograms: per-plane and max-RGB code counts of device frames ----------------
+ * What the consumers after the metrics and the graded output read: the distribution of
+ * max(R, G, B) for a frame's light level (MaxCLL / MaxFALL, percentiles for a tone map's peak),
+ * the histogram distance of consecutive frames for shot boundaries, percentile levels of
+ * 10 / 12-bit sources. One launch reads n device frames once; every value is an integer count
+ * with one right answer.
+ *
+ * A frame is a buffer of a configured context, of depth bpp (8 / 10 / 12) and subsampling ss_h,
+ * ss_v. Each frame has a luma rectangle (x, y, w, h) under the rules of
+ * vp9hip_resample.src_rects: inside the width x height given to the call, w, h >= 1, x a
+ * multiple of 1 << ss_h and y of 1 << ss_v; its chroma rectangle is
+ * (x >> ss_h, y >> ss_v, (w + ss_h) >> ss_h, (h + ss_v) >> ss_v). NULL rects: the top-left
+ * width x height crop, as for the metrics.
+ *
+ * Bins: bins_log2 = k, 4 <= k <= bpp, B = 2^k. The bin of a code c is
+ * min(c, 2^bpp - 1) >> (bpp - k): k = bpp is one bin per code, and stored codes above the depth
+ * (only a consumer can have written them) land in the last bin.
+ *
+ * VP9HIP_HIST_PLANES (C = 3): channels Y, U, V, each the count per bin of the plane's samples
+ * inside its rectangle. Channel 0 sums to w h, channels 1 and 2 to cw ch.
+ *
+ * VP9HIP_HIST_RGBM (C = 4): for every luma position (x, y) of the rectangle take the R, G, B
+ * codes at the source's depth exactly as the graded output's definition above takes them: the
+ * conversion's arithmetic with vp9hip_out_coefs(colorspace, full_range, bpp, out_bits = bpp),
+ * chroma the nearest sample U[y >> ss_v][x >> ss_h], round half up, clip to 2^bpp - 1; colour
+ * space 7 passes its planes through (G, B, R); colour spaces 0 and 6 are VP9HIP_EINVAL.
+ * Channels R, G, B and M = max(R, G, B), each summing to w h. Defined for the source codes the
+ * conversion's own arithmetic is defined for: codes within the depth.
+ *
+ * The result of n frames is a tight (n, C, B) int32 array; every count is at most 2^28. It does
+ * not depend on what the destination held before, and only those bytes are written. Not
+ * offered: joint or 2-D histograms, histograms of a graded or resized output, weights. */
+enum { VP9HIP_HIST_PLANES,     /* Y, U, V                                                 */
+       VP9HIP_HIST_RGBM };     /* R, G, B, max(R, G, B) at the source's depth             */
+typedef struct vp9hip_hist_desc {
+    int32_t what;               /* VP9HIP_HIST_* */
+    int32_t bins_log2;          /* k: 4 .. bpp */
+    int32_t colorspace;         /* RGBM: as vp9hip_out_desc; PLANES: not read */
+    int32_t full_range;
+    int32_t width, height;      /* the visible luma size the rectangles lie in */
+    const vp9hip_rect *rects;   /* n entries, or NULL: the top-left width x height crop */
+} vp9hip_hist_desc;
+/* The histograms of the frames bufs[i], i < n, into out_dev (device memory, n * C * B * 4
+ * bytes), under the contract of vp9hip_frame_metrics: any buffers in any order, repeats
+ * allowed. n above 32 is split into launches of at most 32 frames. Enqueues on `stream` (NULL:
+ * the current slot's main stream) and returns without waiting; it orders nothing itself. The
+ * buffers' pointers and the rectangles travel as kernel arguments: no device table, no host
+ * wait, no allocation and no host read of device memory, so it can sit in a captured stream.
+ * The call zeroes out_dev itself (a memset on the same stream). Everything is checked before
+ * the first launch: a refused call writes nothing. VP9HIP_EINVAL: an unconfigured context, a
+ * buffer index out of range, n <= 0, NULL bufs, d or out_dev, `what` out of range, bins_log2
+ * outside 4 .. bpp, RGBM with colour space 0 or 6 (or any other vp9hip_out_coefs refuses),
+ * width / height outside 1 .. the configured size, a rectangle that breaks the rules above,
+ * out_dev not 4-byte aligned. */
+int  vp9hip_frame_histograms(vp9hip_ctx *ctx, const int *bufs, int n, const vp9hip_hist_desc *d,
+                             int32_t *out_dev, void *stream);
+/* Host only, no device: the C statement of the definition above for one host frame (linesize in
+ * bytes), one sample at a time: out[C][B]. d->rects is not read: `rect` is this frame's
+ * rectangle, or NULL for the d->width x d->height crop. VP9HIP_EINVAL: NULL planes, linesize, d
+ * or out, bpp not 8 / 10 / 12, ss not 0 / 1, sizes outside 1..16384, and what
+ * vp9hip_frame_histograms refuses of d and the rectangle; a refused call writes nothing. */
+int  vp9hip_frame_histograms_host(const void *const planes[3], const ptrdiff_t linesize[3],
+                                  int bpp, int ss_h, int ss_v, const vp9hip_hist_desc *d,
+                                  const vp9hip_rect *rect, int32_t *out);
 
 /* ---- accumulated residual: frame t minus the root frame displaced by the accumulated motion ----
  * The input CoViAR-style models read beside the accumulated motion, and the motion-compensated
@@ -1683,6 +1751,15 @@ int  vp9hip_decoder_motion_scaled(vp9hip_decoder *d, const vp9hip_decoded_frame 
 int  vp9hip_decoder_metrics(vp9hip_decoder *d, const vp9hip_decoded_frame *frames_a,
                             const vp9hip_decoded_frame *frames_b, int n,
                             int64_t *out_dev, int32_t *cells_dev, void *stream);
+/* The histograms of received frames through vp9hip_frame_histograms, under the rules of
+ * vp9hip_decoder_metrics: every frame must be of one size, depth and subsampling and held by
+ * the caller (a released frame is VP9HIP_EINVAL); the size is the frames' own (desc->width /
+ * height are not read; desc->rects lie inside it); it only enqueues and releases nothing. With
+ * desc->colorspace < 0 the colour space and range are the frames' own, as in
+ * vp9hip_decoder_residual_scaled: all frames must then share them, and an unknown colour space
+ * (0, 6) is treated as BT.709. */
+int  vp9hip_decoder_histograms(vp9hip_decoder *d, const vp9hip_decoded_frame *frames, int n,
+                               const vp9hip_hist_desc *desc, int32_t *out_dev, void *stream);
 /* The accumulated residual of the pairs (frames_a[i], frames_b[i]) of received frames through
  * vp9hip_acc_warp, under the rules of vp9hip_decoder_metrics: every frame of both arrays must be
  * of one size, depth and subsampling and held by the caller (a released frame is
